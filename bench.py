@@ -15,10 +15,15 @@ the ranks (flowsim_amd.shard.split_reaches; north_star quotes 65 536 reaches in 
 only collective is one RCCL gather of the boundary hydrographs to rank 0, inside the timed region.  Inputs
 are resident in HBM before the timed region.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement) with an extra object:
   roofline     - algorithmic HBM bytes of the step kernel / its HIP-event time, vs 8 TB/s
+A plain run does only that: set-up, warm-up, the timed steps, the line.  --full adds what takes runs of its own:
   cpu_baseline - the numpy/scipy oracle port (oracle/preissmann_oracle.py) on 1 host core on a
-                 bounded sample of the same workload (reported, not the optimisation target)
+                 bounded sample of the same workload (reported, not the optimisation target), and the C port
+                 on one core and on all cores (c3 on one process)
+  workloads    - the other configurations (EXTRA_WORKLOADS), after the default C3 shape on one GPU
+--dump-outputs DIR writes what the last timed step computed as DIR/*.npy (dump_outputs), so that two builds can be
+compared output for output on the same inputs.
 """
 import argparse
 import json
@@ -331,6 +336,35 @@ def run_extra_workload(spec, local):
         batch.close()
 
 
+DUMP_SEED = 20261016          # the reach sample of dump_outputs: the same reaches in every run of the same arguments
+
+
+def _reach_sample(n, cap):
+    """range(n) when it holds at most `cap` entries, else `cap` of them drawn once from DUMP_SEED, in order"""
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, cap, replace=False))
+
+
+def dump_outputs(out_dir, last_row, batch, last_its):
+    """What a caller of the timed path receives from its last step, as float32 / float64 .npy files (at most 56 MiB in all):
+      hydrograph_last_step.npy  [4, R]  depth[0], flow[0], depth[N-1], flow[N-1] of the last timed level for every gathered
+                                         reach, in the batch's dtype (a fixed sample of 2^19 reaches beyond that)
+      depth_last_step.npy,      [S, N]  the state after the last timed level, float64, on rank 0's reaches: all of them up to
+      flow_last_step.npy                 2^21 values per array, else a fixed sample of S reaches that fits
+      newton_iterations_last_step.npy  [B]  Newton iterations of the last timed level on rank 0's reaches, float64 (2^20 at most)
+    The samples depend on the sizes alone (DUMP_SEED), so runs with the same arguments write the same reaches."""
+    os.makedirs(out_dir, exist_ok=True)
+    row = last_row.cpu().numpy()
+    np.save(os.path.join(out_dir, "hydrograph_last_step.npy"), np.ascontiguousarray(row[:, _reach_sample(row.shape[1], 1 << 19)]))
+    h, Q = batch.state()
+    rows = _reach_sample(batch.B, max(1, (1 << 21) // batch.N))
+    np.save(os.path.join(out_dir, "depth_last_step.npy"), h[rows])
+    np.save(os.path.join(out_dir, "flow_last_step.npy"), Q[rows])
+    np.save(os.path.join(out_dir, "newton_iterations_last_step.npy"),
+            np.asarray(last_its, dtype=np.float64)[_reach_sample(batch.B, 1 << 20)])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -352,10 +386,17 @@ def main():
     ap.add_argument("--per-reach-geometry", action="store_true",
                     help="c4 only: every member gets its own copy of the node table (fs_batch_set_geometry_table_per_reach), as a "
                          "geometry Monte-Carlo would; the shared-table run is the default")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, the measurements that take runs of their own: the CPU baselines (c3 on one process) and, "
+                         "at the default C3 shape on one GPU, EXTRA_WORKLOADS under \"workloads\"")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the headline workload: without it a default run (C3 on one GPU) goes on to time EXTRA_WORKLOADS - C4, C5 in "
-                         "fp32 and fp64, the polyline ensemble, long reaches - and reports them under \"workloads\"")
+                    help="with --full: only the headline workload; without it a --full run at the default shape (C3 on one GPU) goes on "
+                         "to time EXTRA_WORKLOADS - C4, C5 in fp32 and fp64, the polyline ensemble, long reaches - and reports them under "
+                         "\"workloads\"")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed to DIR/*.npy (dump_outputs: the hydrograph row of every "
+                         "reach, its own Newton counts and its state on a fixed sample of reaches)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for --gpus > 1 (nccl = RCCL)")
     ap.add_argument("--dump-hydrographs", default=None,
                     help="rank 0 saves the gathered boundary hydrographs of the timed levels [K, 4, all reaches] to this .npy "
@@ -446,6 +487,8 @@ def main():
 
     st = batch.status()
     its = batch.iterations(Wm + 1, K)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gathered[K - 1], batch, its[K - 1])
     if os.environ.get("FS_STAMPS"):          # diagnostic builds (-DFS_STAMP, FS_LIB=...): cycle sums per phase, to stderr
         import ctypes as C
         out = np.zeros((B, 16, 12), dtype=np.uint64)
@@ -511,7 +554,7 @@ def main():
         }
         if comp is not None:           # informational second roofline: the kernel is bound by vector issue, not by HBM
             out["roofline_compute"] = comp
-        if not args.no_cpu_baseline and args.workload == "c3" and world == 1:      # reported at N=1 only
+        if args.full and not args.no_cpu_baseline and args.workload == "c3" and world == 1:      # reported at N=1 only
             host_cores = set(os.sched_getaffinity(0))
             out["cpu_baseline"] = cpu_baseline(N, dt, dx, theta, tol)
             out["cpu_baseline_c"] = cpu_baseline(N, dt, dx, theta, tol, compiled=True)
@@ -519,7 +562,7 @@ def main():
     headline = (args.workload == "c3" and args.dtype == "f64" and args.nodes == 4096 and args.reaches == 65536 and not strong and world == 1)
     batch.close()
     if rank == 0:
-        if headline and not args.no_extras:
+        if headline and args.full and not args.no_extras:
             # the other configurations, driver-observed in the same line (the C3 batch is closed: its 8 GiB are free again)
             out["workloads"] = []
             for spec in EXTRA_WORKLOADS:

@@ -17,4 +17,4 @@ echo -n "c5 f32: "; ARGS="--workload c5 --dtype f32 --nodes 512 --reaches 131072
 echo -n "c5 f64: "; ARGS="--workload c5 --dtype f64 --nodes 512 --reaches 131072 --steps 32 --warmup 4" bash tools/run_once.sh
 echo -n "c3 default: "; ARGS="--steps 20 --warmup 5" bash tools/run_once.sh
 } 2>&1 | tee gpurun_out/r3/extra_bench.txt
-python bench.py --steps 20 --warmup 5 > gpurun_out/r3/bench_default.json 2> gpurun_out/r3/bench_default.err; tail -c 600 gpurun_out/r3/bench_default.json
+python bench.py --full --steps 20 --warmup 5 > profiles/round3/bench_default.json; tail -c 600 profiles/round3/bench_default.json

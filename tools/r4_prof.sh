@@ -11,4 +11,4 @@ bash tools/profile.sh long_f64 --workload long --nodes 16384 --reaches 8192 --st
 FS_NO_TEAM=1 bash tools/profile.sh long_multipass_f64 --workload long --nodes 16384 --reaches 8192 --steps 8 --warmup 2 && echo "long multipass done"
 python tools/refresh_profiles.py c3_f64 --second c3_f64_k8 > gpurun_out/r4/refresh_c3.txt
 for t in c4_f64 c5_f32 c5_f64 irr_f64 long_f64 long_multipass_f64; do python tools/refresh_profiles.py $t > gpurun_out/r4/refresh_$t.txt; done
-python bench.py --steps 20 --warmup 5 > gpurun_out/r4/bench_default.json 2> gpurun_out/r4/bench_default.err; echo "bench rc $?"; tail -c 400 gpurun_out/r4/bench_default.json
+python bench.py --full --steps 20 --warmup 5 > profiles/round4/bench_default.json; echo "bench rc $?"; tail -c 400 profiles/round4/bench_default.json
