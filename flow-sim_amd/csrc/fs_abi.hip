@@ -746,62 +746,6 @@ int fs_batch_set_geometry_table(fs_batch *b, const double *table, const double *
 
 // polylines of one channel: validated and transposed into the vertex-major device layout ([P][N]; unused slots repeat the last
 // vertex so that no lane ever reads NaN).  Returns an error text or nullptr.
-// Stage table of one polyline (fs_poly.hpp): breakpoints = the distinct vertex elevations; for each interval between two of
-// them the polynomial coefficients of A, P, T and of the three roughness strips' (A, P) in u = stage - lower breakpoint, and
-// the number of wetted runs of >= 2 vertices.  Built per node as [KP] breakpoints + [P][FS_PT_BLOCK] (each interval's entry also carries its bounds and the node's constants);
-// pack_polylines lays the entries out node-minor for the device.
-static void build_stage_table(const double *xs, const double *zs, int c, double liml, double limr, int P, double *blk,
-                              const double node_const[5] /* n_left, n_main, n_right, curvature, z_min */) {
-  std::vector<double> lev(zs, zs + c);
-  std::sort(lev.begin(), lev.end());
-  lev.erase(std::unique(lev.begin(), lev.end()), lev.end());
-  const int K = (int)lev.size(), KP = fs::poly_table_bp(P);
-  const double inf = std::numeric_limits<double>::infinity();
-  for (int j = 0; j < KP; ++j) blk[j] = j < K ? lev[j] : inf;
-  const double xa = xs[0], xb = xs[c - 1];
-  for (int k = 0; k < P; ++k) {
-    double *co = blk + KP + (size_t)k * fs::FS_PT_BLOCK;
-    for (int q = 0; q < fs::FS_PT_BLOCK; ++q) co[q] = 0.0;
-    int runs = 0;
-    if (k < K) {
-      const double z0k = lev[k];
-      auto wet = [&](int v) { return zs[v] <= z0k; };          // wet for every stage of the open interval above lev[k]
-      for (int e = 0; e + 1 < c; ++e) {
-        const double x0 = xs[e], x1 = xs[e + 1], za = zs[e], zb = zs[e + 1];
-        const double dx = x1 - x0, dz = zb - za, len = std::sqrt(dx * dx + dz * dz);
-        const bool w0 = wet(e), w1 = wet(e + 1);
-        double a0 = 0, a1 = 0, a2 = 0, p0 = 0, p1 = 0, t0 = 0, t1 = 0;
-        if (w0 && w1) {                                        // A = dx (s - zmid) = dx (z0k - zmid) + dx u
-          a0 = dx * (z0k - 0.5 * (za + zb)); a1 = dx; p0 = len; t0 = dx;
-        } else if (w0 != w1) {                                 // water's edge: (dx / 2|dz|) (s - zw)^2, (len / |dz|) (s - zw), (dx / |dz|) (s - zw)
-          const double zw = w0 ? za : zb, adz = std::fabs(dz), d = z0k - zw;
-          const double cA = 0.5 * dx / adz, cP = len / adz, cT = dx / adz;
-          a0 = cA * d * d; a1 = 2.0 * cA * d; a2 = cA; p0 = cP * d; p1 = cP; t0 = cT * d; t1 = cT;
-        } else {
-          continue;
-        }
-        co[fs::FS_PT_A0] += a0; co[fs::FS_PT_A1] += a1; co[fs::FS_PT_A2] += a2; co[fs::FS_PT_P0] += p0; co[fs::FS_PT_P1] += p1;
-        co[fs::FS_PT_T0] += t0; co[fs::FS_PT_T1] += t1;
-        const bool in[3] = {x0 >= xa && x1 <= liml, x0 >= liml && x1 <= limr, x0 >= limr && x1 <= xb};      // cross_section.py:459
-        for (int sidx = 0; sidx < 3; ++sidx)
-          if (in[sidx]) {
-            double *o = co + fs::FS_PT_STRIP + 5 * sidx;
-            o[0] += a0; o[1] += a1; o[2] += a2; o[3] += p0; o[4] += p1;
-          }
-      }
-      int run = 0;
-      for (int v = 0; v < c; ++v) {
-        if (wet(v)) ++run;
-        if (!wet(v) || v == c - 1) { runs += run >= 2; run = 0; }
-      }
-    }
-    co[fs::FS_PT_NSUB] = (double)runs;
-    // what an evaluation that starts from this interval needs besides the coefficients (fs_poly.hpp: node_terms_poly_hinted)
-    co[fs::FS_PT_ZLO] = k < K ? lev[k] : inf; co[fs::FS_PT_ZHI] = k + 1 < K ? lev[k + 1] : inf;
-    for (int q = 0; q < 5; ++q) co[fs::FS_PT_NL + q] = node_const[q];
-  }
-}
-
 static const char *pack_polylines(const double *table, const int32_t *n_pts, int32_t max_pts, const double *x, const double *z,
                                   const double *limits, size_t N, double *xt, double *zt, double *lim, double *tz) {
   const size_t P = max_pts;
@@ -827,14 +771,9 @@ static const char *pack_polylines(const double *table, const int32_t *n_pts, int
                                   table[(size_t)FS_GEO_N_RIGHT * N + i], table[(size_t)FS_GEO_CURVATURE * N + i], zmin};
     if (!tz) continue;                 // no stage tables for this batch (set_irregular): the kernels walk the edges
     // the node's table, then into the device layout: breakpoints [N][KP], intervals [P][FS_PT_BLOCK / 2][N] pairs (fs_poly.hpp)
-    const size_t KP = fs::poly_table_bp(max_pts);
     std::vector<double> blk(fs::poly_table_stride(max_pts));
-    build_stage_table(x + i * P, z + i * P, c, limits[2 * i], limits[2 * i + 1], max_pts, blk.data(), node_const);
-    std::memcpy(tz + i * KP, blk.data(), KP * sizeof(double));
-    double *co = tz + N * KP;
-    for (size_t q = 0; q < P * fs::FS_PT_BLOCK; q += 2) {
-      co[((q / 2) * N + i) * 2] = blk[KP + q]; co[((q / 2) * N + i) * 2 + 1] = blk[KP + q + 1];
-    }
+    fs::build_stage_table(x + i * P, z + i * P, c, limits[2 * i], limits[2 * i + 1], max_pts, blk.data(), node_const);
+    fs::pack_stage_table_node(blk.data(), max_pts, N, i, tz);
   }
   return nullptr;
 }

@@ -17,6 +17,7 @@
 //     them: that is what its finite-difference dR/dA sees (:523-531).
 #pragma once
 #include "fs_device.hpp"
+#include "fs_stage_table.hpp"
 
 #ifndef FS_POLY_INLINE
 #define FS_POLY_INLINE 1   // polyline walk inlined into the fold (+37 % on the polyline ensemble): a call inside the Newton loop spills its caller
@@ -51,7 +52,7 @@ template <typename R> struct PolyNode {
   const R *x, *z;
   int stride, n;
   R nl, nm, nr, liml, limr, curv, zmin;
-  // Stage table (fs_abi.hip: build_stage_table; tz == nullptr: none, walk the edges).  Two parts per channel:
+  // Stage table (fs_stage_table.hpp: build_stage_table; tz == nullptr: none, walk the edges).  Two parts per channel:
   //   breakpoints  [N][KP]: the node's distinct vertex elevations, ascending, padded with +inf (KP a multiple of 16);
   //   intervals    [K][FS_PT_BLOCK / 2][N] 16-byte pairs: for interval k = (z_k, z_k+1] of a node FS_PT_NCOEF coefficients in
   //                u = stage - z_k, then what FS_PT_* lists.  NODE-MINOR: the lanes of a wave sit on consecutive nodes, and
@@ -65,23 +66,8 @@ template <typename R> struct PolyNode {
   int K, KP;
 };
 
-// Stage table.  Between two consecutive vertex elevations the set of wet vertices is fixed, and what properties() /
-// get_equivalent_n() sum edge by edge (cross_section.py:248-328, :449-500) are low-order polynomials of the stage:
-//   an edge wet at both ends adds   dx (s - zmid)            to A,  its length to P,  dx to T;
-//   a water's-edge edge adds        (dx / 2|dz|) (s - zw)^2  to A,  (len / |dz|) (s - zw) to P,  (dx / |dz|) (s - zw) to T
-// (zw: elevation of its wet end).  Expanded in u = s - tz[k] >= 0 every coefficient is a sum of non-negative terms - no
-// cancellation, so the 1e-6 finite differences of dR_dA / dA_dh (:523-538) survive.  Per interval: whole section A (3), P (2),
-// T (2), then A (3) and P (2) of the left, main and right roughness strips (an edge belongs to a strip by its two stations, :459).
-// An interval's block then carries what an evaluation inside it needs and nothing else has to be fetched: its own bounds (the
-// next evaluation of the node starts from the interval of the last one, node_terms_poly_hinted), the node's three Manning
-// values, its curvature and z_min.  32 doubles = two 128-byte lines, fetched with sixteen 16-byte loads off one address.
-enum { FS_PT_A0 = 0, FS_PT_A1, FS_PT_A2, FS_PT_P0, FS_PT_P1, FS_PT_T0, FS_PT_T1, FS_PT_STRIP = 7, FS_PT_NCOEF = 22, FS_PT_NSUB = 22,
-       FS_PT_ZLO = 23, FS_PT_ZHI = 24, FS_PT_NL = 25, FS_PT_NM = 26, FS_PT_NR = 27, FS_PT_CURV = 28, FS_PT_ZMIN = 29, FS_PT_USED = 30,
-       FS_PT_BLOCK = 32 };
-// doubles of one node's stage table for polylines of up to P vertices
-// (the breakpoints padded with +inf to a multiple of 16: the scan fetches them 16 at a time, eight 16-byte loads in flight)
-__host__ __device__ constexpr int poly_table_bp(int P) { return (P + 16) & ~15; }
-__host__ __device__ constexpr int poly_table_stride(int P) { return poly_table_bp(P) + P * FS_PT_BLOCK; }   // per node, both parts
+// Stage table layout (FS_PT_*, poly_table_bp, poly_table_stride) and its host-side builder: fs_stage_table.hpp.
+
 
 // vertices [lo, hi] of a node, optionally extended by a water's-edge point at elevation zc on
 // either side (the x_seg / z_seg of cross_section.py:352-365)

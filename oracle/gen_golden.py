@@ -483,6 +483,92 @@ def case_irregular():
     run("irr_mixed", ch, 0.65, 300, 500, 3 * 3600, hyd)
 
 
+def case_irr_edges():
+    """The reference's IrregularSection methods at vertex stages of the channels of tests/poly_edges.py: for each section and a
+    spread of its vertex elevations v, the stages v (bit for bit: z_min + h == v), v -+ 5e-7 and v -+ 2e-6 - where the reference
+    drops the two edges at a vertex on the surface (cross_section.py:262) and the 1e-6 finite differences straddle a vertex.
+    Probe only (tests/golden/irr_edges.npz); plus one full run of the on-vertex reach (irr_on_vertex.npz)."""
+    from src.hydromodel.cross_section import IrregularSection
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+    import poly_edges as PE
+    Q = 40.0
+    X, Z, cnt, lim, rough, rows = [], [], [], [], [], []
+    t0 = time.time()
+    for kind, N, seed in PE.CENSUS:
+        p = PE.BUILDERS[kind](N, np.random.default_rng(seed))
+        for i in sorted({0, N // 2, N - 1}):
+            x, z, r, _ = PE.node_section(p, i)
+            s = IrregularSection(x=x, z=z, n=r[1])
+            s.set_roughness_para(tuple(float(v) for v in r))
+            assert np.array_equal(s.x, x) and np.array_equal(s.z, z), (kind, i, "the reference reorders the stations")
+            j = len(X)
+            X.append(x); Z.append(z); cnt.append(len(x)); lim.append((s.left_fp_limit, s.right_fp_limit)); rough.append(r[:3])
+            lev = np.unique(z)[1:]                                       # (not the thalweg: nothing is wet there)
+            lev = lev[np.unique(np.linspace(0, len(lev) - 1, min(len(lev), 24)).round().astype(int))]
+            for v in lev:
+                for off in (0.0, 5e-7, -5e-7, 2e-6, -2e-6):
+                    h = (v + off) - s.z_min
+                    if off == 0.0 and s.z_min + h != v:
+                        continue                                         # (no depth lands on the vertex bit for bit)
+                    hw = s.z_min + h
+                    s._last_hw = None; s._last_hw_n = None
+                    rows.append([j, h, Q, s.area(hw), s.wetted_perimeter(hw), s.top_width(hw), s.dA_dh(hw),
+                                 s.get_equivalent_n(hw), s.conveyance(hw), s.dR_dA(hw), s.dK_dA(hw),
+                                 s.friction_slope(h, Q), s.dSf_dA(h, Q), s.dSf_dQ(h, Q),
+                                 s.curvature_slope(h, Q), s.dSc_dA(h, Q), s.dSc_dQ(h, Q)])
+    P = max(cnt)
+    n = len(X)
+    Xp = np.full((n, P), np.nan); Zp = np.full((n, P), np.nan)
+    for j in range(n):
+        Xp[j, :cnt[j]] = X[j]; Zp[j, :cnt[j]] = Z[j]
+    rough = np.array(rough)
+    out = dict(geo_irr_x=Xp, geo_irr_z=Zp, geo_irr_npts=np.array(cnt, dtype=np.int32), geo_irr_limits=np.array(lim),
+               geo_n_left=rough[:, 0], geo_n_main=rough[:, 1], geo_n_right=rough[:, 2], geo_curvature=np.zeros(n),
+               probe=np.array(rows, dtype=np.float64))
+    save("irr_edges", out, dict(N=n, kind="section_probe", ref_wall_s=time.time() - t0))      # data only: no run
+
+    # the on-vertex reach as the reference builds it: two polylines on the 2^-6 grid, a fixed depth downstream at a vertex
+    from src.hydromodel.channel import Channel
+    from src.hydromodel.boundary import Boundary
+    from src.hydromodel.preissmann import PreissmannSolver
+    from src.hydromodel.hydrograph import Hydrograph
+    p = PE.on_vertex(2, np.random.default_rng(1), fixed=True)
+    x, zu, r, _ = PE.node_section(p, 0)
+    zd = PE.node_section(p, 1)[1]
+    h0 = float(p.h0[0])
+    dx, nodes = 256, 16
+    L = dx * (nodes - 1)
+    S0 = PE.BED_STEP / dx
+    zu = zd + S0 * L
+    xs_u = IrregularSection(x=x, z=zu, n=r[1], bed_slope=S0); xs_u.set_roughness_para(tuple(float(v) for v in r))
+    xs_d = IrregularSection(x=x, z=zd, n=r[1], bed_slope=S0); xs_d.set_roughness_para(tuple(float(v) for v in r))
+    Q0 = float(p.Q0[0])
+    dt = 300
+    T = 6 * dt
+    hyd = Hydrograph(lambda t: Q0 * (1.0 + 0.5 * np.sin(0.5 * np.pi * min(max(t / dt - 2.0, 0.0) / 3.0, 2.0)) ** 2))
+    us = Boundary(condition='flow_hydrograph', bed_level=S0 * L, chainage=0, hydrograph=hyd, initial_depth=h0)
+    ds = Boundary(condition='fixed_depth', bed_level=0.0, chainage=L, initial_depth=h0)
+    ch = Channel(initial_flow=Q0, upstream_boundary=us, downstream_boundary=ds, interpolation_method='linear')
+    ch.set_cross_sections([0.0, L], [xs_u, xs_d])
+    sol = PreissmannSolver(channel=ch, theta=0.7, time_step=dt, spatial_step=dx, simulation_time=T)
+    o, wall = run_and_capture(sol, 1e-6)
+    o["us_target"] = sample_targets(hyd, sol.number_of_time_levels, sol.time_step)
+    xs = sol.channel.xs_at_node
+    rows = []
+    for i, s in enumerate(xs):
+        for v in np.unique(s.z)[1:5]:
+            h = v - s.z_min
+            s._last_hw = None; s._last_hw_n = None
+            hw = s.z_min + h
+            rows.append([i, h, Q0, s.area(hw), s.wetted_perimeter(hw), s.top_width(hw), s.dA_dh(hw),
+                         s.get_equivalent_n(hw), s.conveyance(hw), s.dR_dA(hw), s.dK_dA(hw),
+                         s.friction_slope(h, Q0), s.dSf_dA(h, Q0), s.dSf_dQ(h, Q0),
+                         s.curvature_slope(h, Q0), s.dSc_dA(h, Q0), s.dSc_dQ(h, Q0)])
+    o["probe"] = np.array(rows, dtype=np.float64)
+    save("irr_on_vertex", o, base_meta(sol, 1e-6, wall, ds_initial_depth=h0, us_initial_depth=h0))
+
+
 def case_storage_general():
     """fixed_depth behind a LumpedStorage with an area curve, a reservoir rating
     curve and entrance losses (lumped_storage.py:24-179, boundary.py:97-133, :152-164, :213-237):
@@ -981,6 +1067,7 @@ CASES = {
     "synthetic_trap_64": lambda: synthetic_trap("synthetic_trap_64", 4, 64, 5, 20260214),
     "bc_matrix": case_bc_matrix,
     "irregular": case_irregular,
+    "irr_edges": case_irr_edges,
     "storage_general": case_storage_general,
     "upstream_kinds": case_upstream_kinds,
     "irr_storage": case_irr_storage,

@@ -28,37 +28,45 @@ DH = 1e-6
 
 
 def properties(x, z, hw):
-    """(A, P, R, T) of the polyline below stage hw; cross_section.py:248-328, edge by edge.
+    """(A, P, R, T) of the polyline below stage hw; cross_section.py:248-328.
 
-    Every edge (j, j+1) is one of: both ends wet -> full trapezoid; one end wet and the other
-    strictly above the surface -> cut at the surface; anything else -> nothing."""
+    Wet segments (runs of vertices strictly below hw), each extended by its water's-edge points
+    where the neighbouring vertex is strictly above hw; a vertex exactly at hw ends a segment
+    without an edge point, so the edge next to it contributes nothing.  Each segment's A and P
+    are ONE np.sum over its edges and T is its extent, as in the reference: np.sum adds in
+    blocks of eight, and on sections of many stations a sequential sum differs from it in the
+    last bits - which the 1e-6 central differences of dR_dA / dA_dh magnify to ~1e-8."""
     x = np.asarray(x, dtype=np.float64); z = np.asarray(z, dtype=np.float64)
+    hw = float(hw)
     if hw <= np.min(z):
         return 0.0, 0.0, 0.0, 0.0
-    d = hw - z
+    below = (hw - z) > 0.0
+    n = x.size
     A = P = T = 0.0
-    for j in range(x.size - 1):
-        d0, d1 = d[j], d[j + 1]
-        w0, w1 = d0 > 0.0, d1 > 0.0
-        if w0 and w1:
-            dx = x[j + 1] - x[j]
-            A += 0.5 * (d0 + d1) * dx
-            P += np.sqrt(dx * dx + (z[j + 1] - z[j]) ** 2)
-            T += dx
-        elif w1 and z[j] > hw:                      # left water's edge, :289-296
-            t = (hw - z[j]) / (z[j + 1] - z[j])
-            xl = x[j] + t * (x[j + 1] - x[j])
-            dx = x[j + 1] - xl
-            A += 0.5 * d1 * dx
-            P += np.sqrt(dx * dx + (z[j + 1] - hw) ** 2)
-            T += dx
-        elif w0 and z[j + 1] > hw:                  # right water's edge, :298-305
-            t = (hw - z[j]) / (z[j + 1] - z[j])
-            xr = x[j] + t * (x[j + 1] - x[j])
-            dx = xr - x[j]
-            A += 0.5 * d0 * dx
-            P += np.sqrt(dx * dx + (hw - z[j]) ** 2)
-            T += dx
+    i = 0
+    while i < n:
+        if not below[i]:
+            i += 1
+            continue
+        i0 = i
+        while i + 1 < n and below[i + 1]:
+            i += 1
+        iN = i
+        xs, zs = x[i0:iN + 1], z[i0:iN + 1]
+        if i0 > 0 and z[i0 - 1] > hw:                    # left water's edge, :289-296
+            z0, z1, x0, x1 = z[i0 - 1], z[i0], x[i0 - 1], x[i0]
+            t = (hw - z0) / (z1 - z0)
+            xs = np.insert(xs, 0, x0 + t * (x1 - x0)); zs = np.insert(zs, 0, hw)
+        if iN < n - 1 and z[iN + 1] > hw:                # right water's edge, :298-305
+            z0, z1, x0, x1 = z[iN], z[iN + 1], x[iN], x[iN + 1]
+            t = (hw - z0) / (z1 - z0)
+            xs = np.append(xs, x0 + t * (x1 - x0)); zs = np.append(zs, hw)
+        d = np.maximum(hw - zs, 0.0)
+        dx = np.diff(xs)
+        A += np.sum(0.5 * (d[:-1] + d[1:]) * dx)
+        P += np.sum(np.sqrt(dx ** 2 + np.diff(zs) ** 2))
+        T += xs[-1] - xs[0]
+        i += 1
     R = A / P if P > 0.0 else 0.0
     return float(A), float(P), float(R), float(T)
 

@@ -488,10 +488,12 @@ def csr_pattern(N):
     return np.array(rows), np.array(cols)
 
 
-def newton_run(p: Problem, n_steps=None, trace=False):
+def newton_run(p: Problem, n_steps=None, trace=False, iterates=False):
     """Time loop x Newton loop, preissmann.py:101-163.  Returns dict(depth, flow [nt,N], iters[nt],
     status, norms).  The row written for level k is the iterate whose residual norm passed the
-    test, the updated vector seeds level k+1 (preissmann.py:128,146-154)."""
+    test, the updated vector seeds level k+1 (preissmann.py:128,146-154).  iterates=True adds
+    "iterates": a list of (k, h_old, h) for every Newton iteration - the old-level state and the
+    iterate whose node terms that iteration evaluated."""
     N = p.N
     nt = p.nt if n_steps is None else min(p.nt, n_steps + 1)
     depth = np.empty((nt, N))
@@ -507,6 +509,7 @@ def newton_run(p: Problem, n_steps=None, trace=False):
     stages = []
     status = 0
     old_terms = None
+    its = []
     for k in range(1, nt):
         it = 0
         while True:
@@ -515,6 +518,8 @@ def newton_run(p: Problem, n_steps=None, trace=False):
                 status = 1
                 break
             depth[k], flow[k] = x[0::2], x[1::2]
+            if iterates:
+                its.append((k, depth[k - 1].copy(), depth[k].copy()))
             R, data, new = assemble(p, depth[k], flow[k], depth[k - 1], flow[k - 1], k, store, old_terms)
             if J is None:
                 J = sp.coo_matrix((data, (rows, cols)), shape=(2 * N, 2 * N)).tocsr()
@@ -537,8 +542,11 @@ def newton_run(p: Problem, n_steps=None, trace=False):
         if store is not None:
             store["Y_prev"] = store["Y_eval"]
             stages.append(store["Y_eval"])
-    return dict(depth=depth, flow=flow, iters=iters, status=status, norms=norms,
-                x_next=x, storage_stage=np.array(stages))
+    out = dict(depth=depth, flow=flow, iters=iters, status=status, norms=norms,
+               x_next=x, storage_stage=np.array(stages))
+    if iterates:
+        out["iterates"] = its
+    return out
 
 
 # ------------------------------------------------------------------------------------------------

@@ -131,3 +131,33 @@ def hetero_batch_from_problems(problems, mode="table", history=True, monitor=Non
     b.set_boundary_per_reach(A.DOWNSTREAM, [boundary_spec(p.ds, p.nt) for p in problems])
     b.set_state(np.stack([pad(p.h0) for p in problems]), np.stack([pad(p.Q0) for p in problems]))
     return b
+
+
+def per_reach_polyline_batch(probs, history=True, monitor=True):
+    """ONE batch, every reach its own polylines (and stage tables), node count and boundary parameters; rows of a shorter reach
+    are padded by repeating its last node (include/flowsim_abi.h: fs_batch_set_geometry_irregular_per_reach).  history=False,
+    monitor=False: the shapes of the no-diagnostics kernels."""
+    B, N, L = len(probs), max(p.N for p in probs), max(p.nt for p in probs)
+    P = max(p.geo["irr_x"].shape[1] for p in probs)
+    p0 = probs[0]
+
+    def pad_nodes(a):
+        a = np.asarray(a)
+        return np.concatenate([a, np.repeat(a[-1:], N - len(a), axis=0)], axis=0)
+
+    def pad_pts(a, n_pts):          # [n, p] -> [n, P]: columns beyond a node's own count repeat its last station
+        a = np.asarray(a, dtype=np.float64)
+        return np.concatenate([a, np.repeat(a[:, -1:], P - a.shape[1], axis=1)], axis=1) if a.shape[1] < P else a
+    geo = {k: np.stack([pad_nodes(p.geo[k]) for p in probs]) for k in A.GEO_ROWS}
+    geo["irr_npts"] = np.stack([pad_nodes(p.geo["irr_npts"]) for p in probs]).astype(np.int32)
+    geo["irr_x"] = np.stack([pad_nodes(pad_pts(p.geo["irr_x"], None)) for p in probs])
+    geo["irr_z"] = np.stack([pad_nodes(pad_pts(p.geo["irr_z"], None)) for p in probs])
+    geo["irr_limits"] = np.stack([pad_nodes(p.geo["irr_limits"]) for p in probs])
+    b = PreissmannBatch(B, N, L, section_mode="irregular", history=history, monitor=monitor)
+    b.set_scheme(p0.theta, p0.dt, p0.dx, p0.tol, p0.max_iter)
+    b.set_geometry_irregular(geo)
+    b.set_reach_nodes([p.N for p in probs])
+    b.set_boundary_per_reach(A.UPSTREAM, [boundary_spec(p.us, p.nt) for p in probs])
+    b.set_boundary_per_reach(A.DOWNSTREAM, [boundary_spec(p.ds, p.nt) for p in probs])
+    b.set_state(np.stack([pad_nodes(p.h0) for p in probs]), np.stack([pad_nodes(p.Q0) for p in probs]))
+    return b

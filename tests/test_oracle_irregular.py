@@ -10,7 +10,9 @@ from conftest import GOLDEN
 from oracle import irregular_oracle as IO
 from oracle import preissmann_oracle as O
 
-CASES = ("irr_single", "irr_levee", "irr_mixed")
+CASES = ("irr_single", "irr_levee", "irr_mixed", "irr_edges", "irr_on_vertex")
+# irr_edges is probe-only: the sections of tests/poly_edges.py at vertex stages (exact, -+5e-7, -+2e-6), no run
+RUNS = ("irr_single", "irr_levee", "irr_mixed", "irr_on_vertex")
 # A, P, T exact to rounding; the finite-difference quantities (dh = 1e-6) carry ~1e-10 cancellation noise
 TOL = dict(A=1e-14, P=1e-14, T=1e-14, dA_dh=5e-9, n_eq=1e-14, K=1e-14, dR_dA=5e-9, dK_dA=5e-9,
            Sf=1e-13, dSf_dA=5e-9, dSf_dQ=1e-13, Sc=1e-13, dSc_dA=5e-9, dSc_dQ=1e-13)
@@ -44,7 +46,7 @@ def test_section_functions_match_reference_probe(name):
         assert multi > 0            # the sub-channel conveyance path (cross_section.py:372-447) was exercised
 
 
-@pytest.mark.parametrize("name", CASES)
+@pytest.mark.parametrize("name", RUNS)
 def test_newton_run_matches_reference(name):
     fx, meta = O.load_fixture(os.path.join(GOLDEN, name + ".npz"))
     p = O.problem_from_fixture(fx, meta)
