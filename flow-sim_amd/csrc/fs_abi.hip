@@ -33,15 +33,9 @@ struct TraceRange {
 }  // namespace
 
 #ifndef FS_MINIMAL
-// the full library: the kernels are instantiated in the fs_part_*.hip translation units
-FS_LIST_RECT(FS_DECLARE, double, FS_F64) FS_LIST_RECT(FS_DECLARE, float, FS_F32)
-FS_LIST_TRAP(FS_DECLARE, double, FS_F64) FS_LIST_TRAP(FS_DECLARE, float, FS_F32)
-FS_LIST_TABLE(FS_DECLARE, double, FS_F64) FS_LIST_TABLE(FS_DECLARE, float, FS_F32)
-FS_LIST_IRREGULAR(FS_DECLARE)
-FS_LIST_NODIAG(FS_DECLARE_NODIAG)
-FS_LIST_TAIL(FS_DECLARE_TAIL)
-FS_LIST_LONG(FS_DECLARE_LONG)
-FS_LIST_TEAM(FS_DECLARE_TEAM)
+// the library: the kernels are instantiated in the fs_part_*.hip translation units (an FS_MINIMAL build instantiates its few where the
+// table below takes their address)
+FS_ACTIVE_LIST(FS_DECLARE)
 #endif
 
 namespace {
@@ -55,8 +49,6 @@ int fail(const std::string &m) { g_err = m; return -1; }
     hipError_t e_ = (expr);                                                                 \
     if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_));   \
   } while (0)
-
-struct Shape { int M, W; };
 
 // Every entry point that allocates, copies, launches or frees runs with the batch's device current and puts the
 // caller's device back on the way out (two batches on different ordinals in one process, calls from another thread).
@@ -73,143 +65,11 @@ struct DeviceGuard {
   DeviceGuard guard_((b)->d.device);                                                        \
   if (!guard_.ok) return fail("hipSetDevice(" + std::to_string((b)->d.device) + ") failed")
 
-typedef FsLaunchFn LaunchFn;
-typedef const void *KernelPtr;
-
-// full   == 1: no per-row selects, valid only for N = 64*W*M
-// bck: boundary-kind class the kernel is compiled for (fs_kernel.hpp): -1 any, 0 any but FS_BC_STORAGE_CURVE,
-//      1 RECT_UNIFORM with bc_is_light() kinds on both ends, 2 + k flow hydrograph upstream and kind k downstream
-struct Entry { int dtype, sec, M, W, full, bck, diag; LaunchFn fn; KernelPtr kp; int longk; int tail = -1; int team = 0; };      // team: a reach as a team of workgroups (fs_kernel.hpp)   // diag == 0: no history / trace stores; longk: fs_long.hpp; tail >= 0: tail-only form, (N - 1) mod M == tail
-#define FS_TABLE_ROW(R, DT, SEC, M, W, FULL, BCK)                                             \
-  { DT, SEC, M, W, FULL, (int)(BCK), 1, &fs_launch<R, SEC, M, W, !(FULL), (int)(BCK)>,          \
-    (KernelPtr)&fs::preissmann_step_kernel<R, SEC, M, W, !(FULL), (int)(BCK)>, 0 },
-#define FS_TABLE_ROW_LONG(R, DT, SEC, M, W, BCK)                                                \
-  { DT, SEC, M, W, 0, (int)(BCK), 1, &fs_launch_long<R, SEC, M, W, (int)(BCK)>,                  \
-    (KernelPtr)&fs::preissmann_long_kernel<R, SEC, M, W, (int)(BCK)>, 1 },
-#define FS_TABLE_ROW_NODIAG(R, DT, SEC, M, W, FULL, BCK)                                       \
-  { DT, SEC, M, W, FULL, (int)(BCK), 0, &fs_launch<R, SEC, M, W, !(FULL), (int)(BCK), false>,    \
-    (KernelPtr)&fs::preissmann_step_kernel<R, SEC, M, W, !(FULL), (int)(BCK), false>, 0 },
-#define FS_TABLE_ROW_TAIL(R, DT, SEC, M, W, BCK, TAIL)                                            \
-  { DT, SEC, M, W, 0, (int)(BCK), 0, &fs_launch<R, SEC, M, W, true, (int)(BCK), false, TAIL>,      \
-    (KernelPtr)&fs::preissmann_step_kernel<R, SEC, M, W, true, (int)(BCK), false, TAIL>, 0, TAIL },
-#define FS_TABLE_ROW_TEAM(R, DT, SEC, M, W, FULL, BCK, DIAG)                                               \
-  { DT, SEC, M, W, FULL, (int)(BCK), DIAG, &fs_launch_team<R, SEC, M, W, !(FULL), (int)(BCK), (DIAG) != 0>,  \
-    (KernelPtr)&fs::preissmann_step_kernel<R, SEC, M, W, !(FULL), (int)(BCK), (DIAG) != 0, -1, true>, 0, -1, 1 },
-#define FS_ENTRY_X(R, DT, SEC, M, W, FULL, BCK) FS_TABLE_ROW(R, DT, SEC, M, W, FULL, BCK)
-#define FS_ENTRY(R, DT, SEC, M, W) FS_TABLE_ROW(R, DT, SEC, M, W, 0, 0)
-
-#if defined(FS_MINIMAL) && FS_MINIMAL == 2   // experiment builds: shapes for 512-node trapezoid reaches
-const Entry kEntries[] = {FS_ENTRY_X(float, FS_F32, FS_SEC_TRAP_UNIFORM, 8, 1, 1, false)
-                          FS_ENTRY_X(float, FS_F32, FS_SEC_TRAP_UNIFORM, 4, 2, 1, false)
-                          FS_ENTRY_X(float, FS_F32, FS_SEC_TRAP_UNIFORM, 2, 4, 1, false)
-                          FS_ENTRY_X(double, FS_F64, FS_SEC_TRAP_UNIFORM, 8, 1, 1, false)
-                          FS_ENTRY_X(double, FS_F64, FS_SEC_TRAP_UNIFORM, 4, 2, 1, false)
-                          FS_ENTRY_X(double, FS_F64, FS_SEC_TRAP_UNIFORM, 2, 4, 1, false)};
-#elif defined(FS_MINIMAL) && FS_MINIMAL == 3   // experiment builds: the polyline kernels
-const Entry kEntries[] = {FS_LIST_IRREGULAR(FS_TABLE_ROW)};
-#elif defined(FS_MINIMAL)   // experiment builds: just the flagship shapes
-const Entry kEntries[] = {FS_TABLE_ROW_NODIAG(double, FS_F64, FS_SEC_RECT_UNIFORM, 16, 4, 1, FS_BCK(FS_BC_NORMAL_DEPTH))
-                          FS_TABLE_ROW_NODIAG(double, FS_F64, FS_SEC_RECT_UNIFORM, 8, 8, 1, FS_BCK(FS_BC_NORMAL_DEPTH))
-                          FS_TABLE_ROW_NODIAG(double, FS_F64, FS_SEC_TABLE, 2, 1, 0, FS_BCK(FS_BC_RATING_BLEND))
-#ifndef FS_NO_TAIL
-                          FS_LIST_TAIL(FS_TABLE_ROW_TAIL)
-#endif
-                          FS_TABLE_ROW_NODIAG(double, FS_F64, FS_SEC_IRREGULAR, 2, 1, 0, FS_BCK(FS_BC_NORMAL_DEPTH))
-                          FS_ENTRY_X(double, FS_F64, FS_SEC_RECT_UNIFORM, 16, 4, 1, FS_BCK(FS_BC_NORMAL_DEPTH))
-                          FS_ENTRY_X(double, FS_F64, FS_SEC_RECT_UNIFORM, 16, 4, 1, true)
-                          FS_ENTRY_X(double, FS_F64, FS_SEC_RECT_UNIFORM, 16, 4, 0, true)
-                          FS_ENTRY_X(double, FS_F64, FS_SEC_RECT_UNIFORM, 8, 4, 1, true)
-                          FS_ENTRY_X(double, FS_F64, FS_SEC_RECT_UNIFORM, 8, 8, 1, true)
-                          FS_ENTRY_X(double, FS_F64, FS_SEC_RECT_UNIFORM, 4, 4, 1, true)
-                          FS_ENTRY_X(double, FS_F64, FS_SEC_RECT_UNIFORM, 8, 1, 0, true)
-                          FS_ENTRY_X(double, FS_F64, FS_SEC_RECT_UNIFORM, 4, 1, 0, true) FS_ENTRY_X(double, FS_F64, FS_SEC_RECT_UNIFORM, 2, 1, 0, true)
-                          FS_ENTRY(double, FS_F64, FS_SEC_RECT_UNIFORM, 4, 1) FS_ENTRY(double, FS_F64, FS_SEC_RECT_UNIFORM, 2, 1)
-                          FS_ENTRY(double, FS_F64, FS_SEC_TABLE, 2, 1) FS_ENTRY(double, FS_F64, FS_SEC_IRREGULAR, 2, 1)
-                          FS_ENTRY_X(double, FS_F64, FS_SEC_TRAP_UNIFORM, 8, 1, 1, false)
-                          FS_ENTRY_X(float, FS_F32, FS_SEC_TRAP_UNIFORM, 8, 1, 1, false)
-                          FS_ENTRY_X(float, FS_F32, FS_SEC_TRAP_UNIFORM, 8, 1, 1, FS_BCK(FS_BC_RATING_POWER))
-                          FS_TABLE_ROW_NODIAG(double, FS_F64, FS_SEC_TRAP_UNIFORM, 8, 1, 1, FS_BCK(FS_BC_RATING_POWER))
-                          FS_ENTRY_X(float, FS_F32, FS_SEC_RECT_UNIFORM, 8, 1, 1, true) FS_ENTRY_X(float, FS_F32, FS_SEC_RECT_UNIFORM, 8, 1, 0, true)
-                          FS_ENTRY(double, FS_F64, FS_SEC_TRAP_UNIFORM, 4, 1) FS_ENTRY(double, FS_F64, FS_SEC_TABLE, 4, 1)
-                          FS_TABLE_ROW_LONG(double, FS_F64, FS_SEC_RECT_UNIFORM, 8, 4, 0)
-                          FS_TABLE_ROW_TEAM(double, FS_F64, FS_SEC_RECT_UNIFORM, 16, 4, 0, 1, 1)
-                          FS_TABLE_ROW_TEAM(double, FS_F64, FS_SEC_RECT_UNIFORM, 16, 4, 0, FS_BCK(FS_BC_NORMAL_DEPTH), 0)
-                          FS_TABLE_ROW_TEAM(double, FS_F64, FS_SEC_RECT_UNIFORM, 16, 4, 1, FS_BCK(FS_BC_NORMAL_DEPTH), 0)
-#ifdef FS_TEAM_8X4
-                          FS_TABLE_ROW_TEAM(double, FS_F64, FS_SEC_RECT_UNIFORM, 8, 4, 0, 1, 1)
-#endif
-                          };
-#else
-const Entry kEntries[] = {FS_LIST_RECT(FS_TABLE_ROW, double, FS_F64) FS_LIST_TRAP(FS_TABLE_ROW, double, FS_F64)
-                          FS_LIST_TABLE(FS_TABLE_ROW, double, FS_F64) FS_LIST_RECT(FS_TABLE_ROW, float, FS_F32)
-                          FS_LIST_TRAP(FS_TABLE_ROW, float, FS_F32) FS_LIST_TABLE(FS_TABLE_ROW, float, FS_F32)
-                          FS_LIST_IRREGULAR(FS_TABLE_ROW) FS_LIST_NODIAG(FS_TABLE_ROW_NODIAG) FS_LIST_LONG(FS_TABLE_ROW_LONG)
-                          FS_LIST_TAIL(FS_TABLE_ROW_TAIL) FS_LIST_TEAM(FS_TABLE_ROW_TEAM)};
-#endif
-
-// usk / dsk: boundary kinds of the batch.  FS_KERNEL_SHAPE="M,W" and FS_KERNEL_GENERAL=1 (environment) narrow the
-// choice for experiments and tests.
+// the dispatch table: what each instantiation was compiled for (fs::KernelKey, fs_dispatch.hpp), its launcher and its kernel.  Which
+// entry a batch gets: fs::pick
+struct Entry { fs::KernelKey key; FsLaunchFn fn; const void *kp; };
+const Entry kEntries[] = {FS_ACTIVE_LIST(FS_TABLE_ROW)};
 constexpr int kNumEntries = (int)(sizeof(kEntries) / sizeof(kEntries[0]));
-
-// hetero: bit 0 = per-reach node counts (ragged kernels only), bit 1 = per-reach scheme or boundary kinds (kernels that read
-// them: boundary classes 0 and -1)
-bool entry_fits(const Entry &e, int dtype, int sec, int N, int usk, int dsk, bool need_diag, bool need_any, int hetero = 0) {
-  if ((hetero & 1) && (e.full || e.tail >= 0)) return false;      // per-reach node counts: the boundary row's place differs from reach to reach
-  if (e.tail >= 0 && (N - 1) % e.M != e.tail) return false;
-  if ((hetero & 2) && e.bck > 0) return false;
-  const bool light = fs::bc_is_light(usk) && fs::bc_is_light(dsk);
-  const bool beyond0 = usk >= FS_BC_STORAGE_CURVE || dsk >= FS_BC_STORAGE_CURVE;      // general storage / host rows: class -1 only
-  if (e.dtype != dtype || e.sec != sec) return false;
-  // rows of the scalar system: N - 1 cells + the downstream boundary row; a long-reach kernel makes up to 64 / W passes
-  const long cap = 64L * e.W * e.M * ((e.longk || e.team) ? 64 / e.W : 1);
-  if (cap < N || N > 32768) return false;
-  if (e.team && (N <= 4096 || N <= 64L * e.W * e.M || std::getenv("FS_NO_TEAM"))) return false;      // a team only where one workgroup does not hold the reach (FS_NO_TEAM=1: the multi-pass kernel instead)
-  if (e.team) { if (const char *tm = std::getenv("FS_TEAM_M")) { if (std::atoi(tm) != e.M) return false; } }      // experiments: rows per lane of the team kernel
-  if (e.longk && ((need_any && e.bck != -1) || (e.bck == 0 && beyond0))) return false;      // iteration budget / host rows: class -1 (tables, polylines)
-  if (e.full && (e.team ? N % (64L * e.W * e.M) != 0 : N != cap)) return false;      // (a team's: a whole number of lane grids)
-  if (!e.diag && need_diag) return false;
-  if (need_any && e.bck != -1) return false;
-  if (e.bck == 0 && beyond0) return false;
-  if (e.bck == 1 && (!light || sec != FS_SEC_RECT_UNIFORM)) return false;
-  if (e.bck >= 2 && (usk != FS_BC_FLOW_HYDROGRAPH || dsk != e.bck - 2)) return false;
-  return true;
-}
-
-// need_any: the caller needs a kernel of boundary class -1 (iteration budget, host rows)
-const Entry *pick_kernel(int dtype, int sec, int N, int usk, int dsk, bool need_diag, std::string *why, bool need_any = false,
-                         bool honour_index = true, int hetero = 0) {
-  if (const char *env = honour_index ? std::getenv("FS_KERNEL_INDEX") : nullptr) {      // tests: one specific instantiation or nothing
-    const int i = std::atoi(env);
-    if (i >= 0 && i < kNumEntries && entry_fits(kEntries[i], dtype, sec, N, usk, dsk, need_diag, need_any, hetero)) return &kEntries[i];
-    if (why) *why = "FS_KERNEL_INDEX=" + std::string(env) + " does not fit this batch";
-    return nullptr;
-  }
-  int wantM = 0, wantW = 0;
-  if (const char *env = std::getenv("FS_KERNEL_SHAPE")) std::sscanf(env, "%d,%d", &wantM, &wantW);
-  const char *gen = std::getenv("FS_KERNEL_GENERAL");
-  const bool general_only = gen && gen[0] == '1';
-  const Entry *best = nullptr;
-  for (const Entry &e : kEntries) {
-    if (!entry_fits(e, dtype, sec, N, usk, dsk, need_diag, need_any, hetero)) continue;
-    if (general_only && (!e.diag || e.bck >= 2)) continue;
-    if (wantM && (e.M != wantM || e.W != wantW)) continue;
-    // smallest capacity first; on ties prefer fewer waves per reach, then the more specific variant
-    auto rank = [](const Entry &x) { return x.full + (x.bck >= 2 ? 4 : x.bck == 1 ? 2 : x.bck == 0 ? 1 : 0) + (x.diag ? 0 : 8) + (x.tail >= 0 ? 16 : 0); };
-    const int spec = rank(e), bspec = best ? rank(*best) : 0;
-    // a kernel that keeps the reach on chip whenever one fits: one workgroup, else a team of them, else the multi-pass kernel
-    const int tier = e.longk ? 2 : (e.team ? 1 : 0), btier = best ? (best->longk ? 2 : (best->team ? 1 : 0)) : 0;
-    if (best && tier != btier) {
-      if (tier < btier) best = &e;
-      continue;
-    }
-    if (!best || e.M * e.W < best->M * best->W || (e.M * e.W == best->M * best->W && e.W < best->W) ||
-        (e.M == best->M && e.W == best->W && spec > bspec))
-      best = &e;
-  }
-  if (!best && why) *why = "no kernel instantiation for N=" + std::to_string(N) + " (supported: 2..32768 nodes for the uniform section "
-                           "modes, 2..16384 for tables and polylines)";
-  return best;
-}
 
 }  // namespace
 
@@ -537,16 +397,19 @@ int launch_steps(fs_batch *b, int n_steps, int iter_budget) {
   TraceRange range_(iter_budget > 0 ? "flowsim:iterate" : "flowsim:step");
   std::string why;
   const int hetero = (b->reach_nodes ? 1 : 0) | ((b->reach_scheme || b->kinds_per_reach[0] || b->kinds_per_reach[1]) ? 2 : 0);
-  const Entry *k = pick_kernel(b->d.dtype, b->d.section_mode, b->d.n_nodes, b->bc_kind[0], b->bc_kind[1],
-                               (b->d.flags & (FS_FLAG_HISTORY | FS_FLAG_TRACE | FS_FLAG_MONITOR)) != 0, &why, iter_budget > 0, true, hetero);
+  fs::Query q;
+  q.dtype = b->d.dtype; q.sec = b->d.section_mode; q.N = b->d.n_nodes; q.usk = b->bc_kind[0]; q.dsk = b->bc_kind[1];
+  q.need_diag = (b->d.flags & (FS_FLAG_HISTORY | FS_FLAG_TRACE | FS_FLAG_MONITOR)) != 0; q.need_any = iter_budget > 0; q.hetero = hetero;
+  const int chosen = fs::pick(kEntries, kNumEntries, q, fs::overrides_from_environment(), &why);
+  const Entry *k = chosen < 0 ? nullptr : &kEntries[chosen];
   if (!k && why.rfind("FS_KERNEL_INDEX", 0) == 0) return fail("fs_batch_step: " + why);
   if (!k && (b->bc_kind[0] == FS_BC_STORAGE_CURVE || b->bc_kind[1] == FS_BC_STORAGE_CURVE))
     return fail("fs_batch_step: FS_BC_STORAGE_CURVE needs section mode FS_SEC_TABLE or FS_SEC_IRREGULAR");
   if (!k) return fail("fs_batch_step: no kernel instantiation for this boundary kind at this size");
   b->kern = k;
   b->passes = 0;
-  if (k->longk) {      // a reach longer than one lane grid: passes of 64 W M rows, level constants in a scratch of the batch's own
-    const size_t chunk = (size_t)64 * k->W * k->M;
+  if (k->key.longk) {      // a reach longer than one lane grid: passes of 64 W M rows, level constants in a scratch of the batch's own
+    const size_t chunk = (size_t)64 * k->key.W * k->key.M;
     b->passes = (int)((b->d.n_nodes + chunk - 1) / chunk);
     // (uniform sections recompute their level constants, fs_long.hpp: no scratch)
     const bool recompute = FS_LONG_RECOMPUTE && (b->d.section_mode == FS_SEC_RECT_UNIFORM || b->d.section_mode == FS_SEC_TRAP_UNIFORM);
@@ -558,11 +421,11 @@ int launch_steps(fs_batch *b, int n_steps, int iter_budget) {
     }
   }
   b->team_size = 0;
-  if (k->team) {       // G workgroups per reach: their mailboxes and counters (the counters start every launch at zero)
-    const size_t chunk = (size_t)64 * k->W * k->M, B = b->d.n_reaches;
+  if (k->key.team) {       // G workgroups per reach: their mailboxes and counters (the counters start every launch at zero)
+    const size_t chunk = (size_t)64 * k->key.W * k->key.M, B = b->d.n_reaches;
     b->team_size = (int)((b->d.n_nodes + chunk - 1) / chunk);
     // (16 bytes per word: the tagged form posts (value, tag) pairs; zeroed once - a tag is never 0, launches count from 1)
-    const size_t need = B * 2 * ((size_t)b->team_size * k->W + 1) * fs::kTeamWords * 2;
+    const size_t need = B * 2 * ((size_t)b->team_size * k->key.W + 1) * fs::kTeamWords * 2;
     if (b->team_mail_elems < need) {
       if (b->team_mail) { (void)hipFree(b->team_mail); b->team_mail = nullptr; b->team_mail_elems = 0; }
       HIP_TRY(hipMalloc(&b->team_mail, need * sizeof(double)));
@@ -622,13 +485,17 @@ fs_batch *fs_batch_create(const fs_batch_desc *desc) {
     return nullptr;
   }
   std::string why;
-  const Entry *k = pick_kernel(desc->dtype, desc->section_mode, desc->n_nodes, FS_BC_FLOW_HYDROGRAPH, FS_BC_FLOW_HYDROGRAPH, true, &why,
-                               false, false);
-  if (!k) { fail("fs_batch_create: " + why); return nullptr; }
+  // a first choice, before the boundary kinds are known: is there a kernel for this size at all?  (FS_KERNEL_INDEX is for the steps.)
+  fs::Query q;
+  q.dtype = desc->dtype; q.sec = desc->section_mode; q.N = desc->n_nodes; q.usk = q.dsk = FS_BC_FLOW_HYDROGRAPH; q.need_diag = true;
+  fs::Overrides ov = fs::overrides_from_environment();
+  ov.force_index = false;
+  const int chosen = fs::pick(kEntries, kNumEntries, q, ov, &why);
+  if (chosen < 0) { fail("fs_batch_create: " + why); return nullptr; }
   fs_batch *b = new fs_batch();
   b->d = *desc;
   b->esz = desc->dtype == FS_F64 ? 8 : 4;
-  b->kern = k;
+  b->kern = &kEntries[chosen];
   int prev_dev = -1;
   if (hipGetDevice(&prev_dev) != hipSuccess) prev_dev = -1;
   auto bad = [&](const char *what, hipError_t e) {
@@ -1427,15 +1294,15 @@ int32_t fs_kernel_table_size(void) { return kNumEntries; }
 
 int fs_kernel_table_entry(int32_t i, int32_t *out) {
   if (i < 0 || i >= kNumEntries || !out) return fail("fs_kernel_table_entry: index out of range");
-  const Entry &e = kEntries[i];
+  const fs::KernelKey &e = kEntries[i].key;
   out[0] = e.dtype; out[1] = e.sec; out[2] = e.M; out[3] = e.W; out[4] = e.full; out[5] = e.bck; out[6] = e.diag; out[7] = e.longk;
   return 0;
 }
 
 int32_t fs_batch_kernel_index(fs_batch *b) { return (b && b->kern) ? (int32_t)(b->kern - kEntries) : -1; }
 
-int32_t fs_kernel_table_entry_tail(int32_t i) { return (i >= 0 && i < kNumEntries) ? kEntries[i].tail : -2; }
-int32_t fs_kernel_table_entry_team(int32_t i) { return (i >= 0 && i < kNumEntries) ? kEntries[i].team : -2; }
+int32_t fs_kernel_table_entry_tail(int32_t i) { return (i >= 0 && i < kNumEntries) ? kEntries[i].key.tail : -2; }
+int32_t fs_kernel_table_entry_team(int32_t i) { return (i >= 0 && i < kNumEntries) ? kEntries[i].key.team : -2; }
 
 int32_t fs_batch_poly_tables(fs_batch *b) { return (b && b->poly_x) ? (b->poly_K > 0 ? 1 : 0) : -1; }
 
@@ -1444,8 +1311,8 @@ int fs_batch_kernel_info(fs_batch *b, int32_t *cells_per_thread, int32_t *waves_
   if (!b) return fail("null handle");
   hipFuncAttributes at;
   HIP_TRY(hipFuncGetAttributes(&at, b->kern->kp));
-  if (cells_per_thread) *cells_per_thread = b->kern->M;
-  if (waves_per_reach) *waves_per_reach = b->kern->W;
+  if (cells_per_thread) *cells_per_thread = b->kern->key.M;
+  if (waves_per_reach) *waves_per_reach = b->kern->key.W;
   if (lds_bytes) *lds_bytes = (int32_t)at.sharedSizeBytes;
   if (vgprs) *vgprs = at.numRegs;
   return 0;

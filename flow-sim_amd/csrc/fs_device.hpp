@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/flowsim_abi.h"
+#include "fs_dispatch.hpp"      // bc_is_light: the dispatch asks it too
 
 namespace fs {
 
@@ -753,7 +754,7 @@ __device__ FS_BC_ATTR BCRow<R> bc_eval(const BCDesc<R> bc, int reach, int B, int
       r.dq = R(0) - (Y <= ymin ? R(0) : R(1) / area) * R(0.5) * dt;     // boundary.py:213-237
     } break;
     case FS_BC_STORAGE_CURVE: {
-      if (!WITH_SC) { r.res = R(0); r.dh = R(1); r.dq = R(0); break; }      // never launched (fs_abi.hip: pick_kernel)
+      if (!WITH_SC) { r.res = R(0); r.dh = R(1); r.dq = R(0); break; }      // never launched (fs_dispatch.hpp: fits)
       const R bed = bc_param(bc, FS_SC_BED_LEVEL, reach, B);             // (this kind's parameters stay in global memory)
       return bc_storage_curve(bc, reach, B, level, entry_props(general_props_call(sec, h)),
                               entry_props(general_props_call(sec, h + bed - sec.z)), h, Q, Qold, dt, Yprev, Ynew, flag);
@@ -771,11 +772,9 @@ __device__ FS_BC_ATTR BCRow<R> bc_eval(const BCDesc<R> bc, int reach, int B, int
 
 // Rectangular prismatic reaches: same rows with the closed-form conveyance of node_terms_rect and
 // no out-of-line call (a call inside the Newton loop makes the caller spill its register-resident
-// state around it).  Only the kinds that need no pow() are inlined (bc_is_light): the power rating
+// state around it).  Only the kinds that need no pow() are inlined (bc_is_light, fs_dispatch.hpp): the power rating
 // curve drags ~50 SGPR constants and ~300 instructions of pow() into the hot loop otherwise.
 // zsec = bed level of the boundary node's section.
-__host__ __device__ constexpr bool bc_is_light(int kind) { return kind != FS_BC_RATING_POWER && kind < FS_BC_STORAGE_CURVE; }
-
 // lp: this reach's parameters in LDS (typed pointer: ds_read, not a flat load through a generic one)
 template <typename R>
 __device__ __forceinline__ BCRow<R> bc_eval_rect(const BCDesc<R> &bc, LdsParams<R> lp, int level, R b, R n, R zsec,

@@ -315,11 +315,11 @@ int32_t fs_batch_last_launch_count(fs_batch *b);
 int fs_batch_kernel_info(fs_batch *b, int32_t *cells_per_thread, int32_t *waves_per_reach,
                          int32_t *lds_bytes, int32_t *vgprs);
 /* The dispatch table of the step kernel (what fs_batch_step chooses from): fs_kernel_table_size() entries,
- * entry i described by out[8] = dtype, section_mode, cells per lane M, waves per reach W, full (1: only
- * N == 64*W*M: the downstream boundary row takes the last row of the lane grid), boundary class (-1 any kind, 0 any but FS_BC_STORAGE_CURVE / FS_BC_HOST_ROW,
- * 1 closed-form rectangular rows, 2+k flow hydrograph upstream and kind k downstream), diag (0: compiled
- * without history / trace stores), long (1: the multi-pass kernel for reaches longer than one lane grid: capacity 64*M rows per
- * wave slot x 64 slots).  The environment
+ * entry i described by out[8] = dtype, section_mode, cells per lane M, waves per reach W, full (1: only N == 64*W*M),
+ * boundary class (-1 any kind, 0 any but FS_BC_STORAGE_CURVE / FS_BC_HOST_ROW, 1 closed-form rectangular rows, 2+k flow
+ * hydrograph upstream and kind k downstream), diag (0: no history / trace stores), long (1: the multi-pass kernel for reaches
+ * longer than one lane grid).  The fields in full, and how an entry is chosen: fs::KernelKey and fs::pick in
+ * flow-sim_amd/csrc/fs_dispatch.hpp.  The environment
  * variable FS_KERNEL_INDEX=i makes fs_batch_step use entry i or fail if it does not fit the batch (tests:
  * every instantiation is checked against the oracle). fs_batch_kernel_index: the entry the last step used. */
 int32_t fs_kernel_table_size(void);

@@ -169,7 +169,7 @@ def test_the_tail_only_form_gives_the_bits_of_the_ragged_kernel(monkeypatch):
 
 
 def test_dispatch_prefers_the_most_specific_instantiation():
-    """pick_kernel's ordering (fs_abi.hip): smallest capacity, then fewest waves per reach, then the most specific
+    """fs::pick's ordering (fs_dispatch.hpp; on the CPU: tests/test_dispatch.py): smallest capacity, then fewest waves per reach, then the most specific
     variant (boundary pair fixed > closed-form rows > general; no-history build when the batch keeps none)."""
     from flowsim_amd import BoundarySpec, PreissmannBatch
     from flowsim_amd import _abi as A

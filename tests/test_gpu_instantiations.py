@@ -1,4 +1,4 @@
-"""Every instantiation of the step kernel (csrc/fs_entries.hpp, exported as the dispatch table of the C ABI) is
+"""Every instantiation of the step kernel (csrc/fs_entry_list.hpp, exported as the dispatch table of the C ABI) is
 launched once and checked against the CPU oracle: fp64 to 1e-8 with identical Newton counts, fp32 to 5e-4 of the
 fp64 answer.
 

@@ -704,7 +704,7 @@ def test_kernels_compiled_for_a_boundary_pair_match_the_general_ones(case, monke
 @pytest.mark.parametrize("case", ["synthetic_rect_512", "gerd", "irr_mixed", "trap_512"])
 def test_batches_without_history_run_the_same_numbers(case, monkeypatch):
     """Batches created without FS_FLAG_HISTORY / FS_FLAG_TRACE get the instantiations compiled without those
-    stores (DIAG = false, fs_entries.hpp): same hydrographs to a few ulp, same iteration counts."""
+    stores (DIAG = 0, fs_entry_list.hpp): same hydrographs to a few ulp, same iteration counts."""
     from fixture_batch import batch_from_problems
     if case.startswith("trap"):
         probs, mode = _singular_pivot_problems(512, 5, 1e-6)[:3], "trap_uniform"

@@ -164,7 +164,7 @@ def common(p, nt=3):
     return q
 
 
-# per-reach channels and boundaries run on the kernels that read them: boundary classes 0 and -1 (fs_abi.hip: entry_fits, hetero)
+# per-reach channels and boundaries run on the kernels that read them: boundary classes 0 and -1 (fs_dispatch.hpp: fits, hetero)
 BATCH_ENTRIES = [e for e in ENTRIES if not e.get("long_reach") and e["boundary_class"] <= 0]
 
 
