@@ -1,10 +1,11 @@
 // fs_abi.hip - host side of libflowsim_hip.so: the C ABI declared in include/flowsim_abi.h.
 //
-// Owns the device buffers of a batch (SoA, reach-major state [B][N]; per-level tables [level][B]),
-// converts caller float64 host arrays to the batch dtype on upload, picks the kernel instantiation
-// (cells per lane M, waves per reach W) from N, and launches the fused step kernel on the
-// handle's HIP stream.  No CPU compute path exists here: without a HIP device every entry point
-// that needs one fails and says so.
+// Holds the device buffers of a batch (SoA, reach-major state [B][N]; per-level tables [level][B]) as fs::DeviceBuffer /
+// fs::PinnedBuffer members (fs_buffer.hpp: freed with the handle), converts caller float64 host arrays to the batch dtype on
+// upload, asks fs::pick (fs_dispatch.hpp) for the kernel instantiation and launches the fused step kernel on the handle's HIP
+// stream.  What needs no device - packing polylines and their stage tables, extending geometry tables, validating boundary
+// arguments - is fs_host_pack.hpp, which the CPU tests build on its own; the batch's arithmetic type is turned into a C++ type in one
+// place (with_real).  No CPU compute path exists here: without a HIP device every entry point that needs one fails and says so.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,7 +21,9 @@
 #include <thread>
 #include <vector>
 
+#include "fs_buffer.hpp"
 #include "fs_entries.hpp"
+#include "fs_host_pack.hpp"
 
 // ROCTx ranges around the phases a system trace should show (rocprofv3 --marker-trace): uploads, downloads, the step launch,
 // the post-processing launch.  Without a tool attached a push / pop is a few nanoseconds.
@@ -143,35 +146,42 @@ constexpr int kStageSlots = 3;
 constexpr size_t kStageMin = (size_t)8 << 20;         // smaller transfers: one plain copy
 
 struct Staging {
-  void *buf[kStageSlots] = {nullptr, nullptr, nullptr};
+  fs::PinnedBuffer buf[kStageSlots];
   hipEvent_t ev[kStageSlots] = {nullptr, nullptr, nullptr};
   bool ready = false;
   int init() {
     if (ready) return 0;
     for (int i = 0; i < kStageSlots; ++i) {
-      if (hipHostMalloc(&buf[i], kStageChunk, hipHostMallocDefault) != hipSuccess) return -1;
-      if (hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) != hipSuccess) return -1;
+      if (buf[i].ensure(kStageChunk) != hipSuccess) return -1;
+      if (!ev[i] && hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) != hipSuccess) return -1;
     }
     ready = true;
     return 0;
   }
-  void release() {
+  ~Staging() {
     for (int i = 0; i < kStageSlots; ++i) {
-      if (buf[i]) (void)hipHostFree(buf[i]);
+      buf[i].reset();
       if (ev[i]) (void)hipEventDestroy(ev[i]);
-      buf[i] = nullptr; ev[i] = nullptr;
     }
-    ready = false;
+  }
+};
+
+// the stream and the two timing events of a batch: a base of fs_batch, so that they outlive its buffers
+struct Timeline {
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  ~Timeline() {
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (stream) (void)hipStreamDestroy(stream);
   }
 };
 
 }  // namespace
 
-struct fs_batch {
+struct fs_batch : Timeline {
   fs_batch_desc d;
   size_t esz;                 // sizeof(real)
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = false;
   bool iterating = false;     // a level opened by fs_batch_iterate has not been closed yet
   int launches = 0;
@@ -182,60 +192,63 @@ struct fs_batch {
   double theta = 0.6, dt = 0, dx = 0, tol = 1e-4;
   int max_iter = 100;
   bool have_scheme = false, have_geo = false, have_state = false, have_bc[2] = {false, false};
-  // device buffers
-  void *hk = nullptr, *Qk = nullptr, *hg = nullptr, *Qg = nullptr;
-  void *geo_uniform = nullptr, *geo_table = nullptr, *n_override = nullptr;
-  void *poly_x = nullptr, *poly_z = nullptr, *poly_lim = nullptr;
-  int32_t *poly_n = nullptr;
-  void *poly_tz = nullptr;              // stage tables of the polylines (fs_poly.hpp)
+  // device buffers (an empty one reads as nullptr: the kernels take that as "not given")
+  fs::DeviceBuffer hk, Qk, hg, Qg;
+  fs::DeviceBuffer geo_uniform, geo_table, n_override;
+  fs::DeviceBuffer poly_x, poly_z, poly_lim, poly_n;     // poly_n: int32
+  fs::DeviceBuffer poly_tz;             // stage tables of the polylines (fs_poly.hpp)
   int poly_K = 0;
   size_t geo_reach_stride = 0, poly_reach_stride = 0;     // per-reach geometry (elements between the tables of two reaches), 0: shared
-  int32_t *reach_nodes = nullptr;       // [B] per-reach node counts (heterogeneous batch) or nullptr
+  fs::DeviceBuffer reach_nodes;         // int32 [B] per-reach node counts (heterogeneous batch) or empty
   std::vector<int32_t> reach_nodes_host;      // its host copy (empty: every reach has n_nodes): where a reach's last node is
   bool any_storage[2] = {false, false}; // some reach's boundary on this side is a storage kind (per-reach kinds: OR over the reaches)
-  void *reach_scheme = nullptr;         // [5][B] per-reach theta, dt, dx, tolerance, max_iter or nullptr
+  fs::DeviceBuffer reach_scheme;        // [5][B] per-reach theta, dt, dx, tolerance, max_iter or empty
   std::vector<double> rs_host[5];       // what the caller set per reach (empty: the batch-wide value of fs_batch_set_scheme)
-  int32_t *reach_kinds = nullptr;       // [2][B] per-reach boundary kinds or nullptr
+  fs::DeviceBuffer reach_kinds;         // int32 [2][B] per-reach boundary kinds or empty
   bool kinds_per_reach[2] = {false, false};
   bool some_host_rows[2] = {false, false};      // per-reach kinds with FS_BC_HOST_ROW among them: fs_batch_set_host_rows writes those reaches' rows only
-  void *rows_stage = nullptr;          // [3][B] what the caller handed to fs_batch_set_host_rows, before the masked merge into the parameters
-  void *bc_params[2] = {nullptr, nullptr}, *bc_target[2] = {nullptr, nullptr};
+  fs::DeviceBuffer rows_stage;          // [3][B] what the caller handed to fs_batch_set_host_rows, before the masked merge into the parameters
+  fs::DeviceBuffer bc_params[2], bc_target[2];
   int bc_kind[2] = {0, 0}, bc_stride[2] = {0, 0};
-  void *Yprev = nullptr, *stage_hist = nullptr, *trace = nullptr, *hydro = nullptr, *hist_h = nullptr, *hist_Q = nullptr;
-  int32_t *iters = nullptr, *status = nullptr;
-  int32_t *it_done = nullptr;          // [B] Newton iterations spent on the open level (fs_batch_iterate)
-  double *ends_dev = nullptr;          // [4][B] scratch of fs_batch_get_boundary_iterate (allocated on first use)
-  double *ends_pin = nullptr;          // its pinned host mirror
-  int32_t *open_dev = nullptr, *open_pin = nullptr;      // fs_batch_iterate: count of the reaches still iterating
-  void *derived[8] = {nullptr};        // device results of the last derive call, kept and reused
-  size_t derived_cap[8] = {0};         // their capacities in elements
-  unsigned long long *dbg = nullptr;
-  Staging stage;                       // pinned chunks for large host <-> device transfers
-  void *kc_scratch = nullptr;          // long reaches: level constants [B][4][passes * 64 W M]
-  size_t kc_scratch_elems = 0;
+  fs::DeviceBuffer Yprev, stage_hist, trace, hydro, hist_h, hist_Q;
+  fs::DeviceBuffer iters, status;       // int32
+  fs::DeviceBuffer it_done;             // int32 [B] Newton iterations spent on the open level (fs_batch_iterate)
+  fs::DeviceBuffer ends_dev;            // double [4][B] scratch of fs_batch_get_boundary_iterate (allocated on first use)
+  fs::PinnedBuffer ends_pin;            // its pinned host mirror
+  fs::DeviceBuffer open_dev;            // int32: fs_batch_iterate's count of the reaches still iterating
+  fs::PinnedBuffer open_pin;
+  fs::DeviceBuffer derived[8];          // device results of the last derive call, kept and reused (grown, never shrunk)
+  fs::DeviceBuffer dbg;
+  Staging stage;                        // pinned chunks for large host <-> device transfers
+  fs::DeviceBuffer kc_scratch;          // long reaches: level constants [B][4][passes * 64 W M]
   int passes = 0;
-  void *team_mail = nullptr;           // reaches stepped by teams of workgroups: mailboxes [B][2][G W + 1][kTeamWords]
-  size_t team_mail_elems = 0;
-  unsigned long long *team_sync = nullptr;      // [1 + B] ticket counter + per-reach post counters, zeroed before every launch
+  fs::DeviceBuffer team_mail;           // reaches stepped by teams of workgroups: mailboxes [B][2][G W + 1][kTeamWords]
+  fs::DeviceBuffer team_sync;           // uint64 [1 + B] ticket counter + per-reach post counters, zeroed before every launch
   int team_size = 0;
-  uint32_t team_epoch = 0;             // team launches made on this handle (the high half of the tagged mailbox's tags)
+  uint32_t team_epoch = 0;              // team launches made on this handle (the high half of the tagged mailbox's tags)
 };
 
 namespace {
 
-int upload(fs_batch *b, void **dst, const double *src, size_t n) {
+// the batch's arithmetic type as a C++ type: f(double()) or f(float())
+template <typename F> auto with_real(const fs_batch *b, F &&f) { return b->d.dtype == FS_F64 ? f(double()) : f(float()); }
+
+// one thread per item (reach, or node of the batch), 256 per block
+dim3 grid_256(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
+
+// n doubles of the caller's into device memory that holds at least n elements of the batch's type
+int upload_to(fs_batch *b, void *dst, const double *src, size_t n) {
   TraceRange range_("flowsim:upload");
-  if (!*dst) HIP_TRY(hipMalloc(dst, n * b->esz));
-  const bool f64 = b->d.dtype == FS_F64;
+  const bool f64 = b->esz == sizeof(double);
   if (f64 || n * b->esz < kStageMin || b->stage.init() != 0) {
     // fp64: the runtime's own pageable path (it pins and pipelines; ~55 GB/s here); small fp32 arrays: convert, then one copy
     if (f64) {
-      HIP_TRY(hipMemcpyAsync(*dst, src, n * sizeof(double), hipMemcpyHostToDevice, b->stream));
+      HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyHostToDevice, b->stream));
       HIP_TRY(hipStreamSynchronize(b->stream));
     } else {
       std::vector<float> tmp(n);
       for (size_t i = 0; i < n; ++i) tmp[i] = (float)src[i];
-      HIP_TRY(hipMemcpyAsync(*dst, tmp.data(), n * sizeof(float), hipMemcpyHostToDevice, b->stream));
+      HIP_TRY(hipMemcpyAsync(dst, tmp.data(), n * sizeof(float), hipMemcpyHostToDevice, b->stream));
       HIP_TRY(hipStreamSynchronize(b->stream));
     }
     return 0;
@@ -246,21 +259,27 @@ int upload(fs_batch *b, void **dst, const double *src, size_t n) {
   for (size_t off = 0; off < n; off += per, slot = (slot + 1) % kStageSlots) {
     const size_t cnt = std::min(per, n - off);
     HIP_TRY(hipEventSynchronize(b->stage.ev[slot]));              // the DMA that last read this slot is through
-    float *pin = (float *)b->stage.buf[slot];
+    float *pin = b->stage.buf[slot].get<float>();
     const double *sp = src + off;
     CopyPool::get().run(cnt, [&](size_t lo, size_t hi) { for (size_t i = lo; i < hi; ++i) pin[i] = (float)sp[i]; });
-    HIP_TRY(hipMemcpyAsync((char *)*dst + off * sizeof(float), pin, cnt * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync((char *)dst + off * sizeof(float), pin, cnt * sizeof(float), hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hipEventRecord(b->stage.ev[slot], b->stream));
   }
   HIP_TRY(hipStreamSynchronize(b->stream));
   return 0;
 }
 
-int download(fs_batch *b, double *dst, const void *src, size_t off_elems, size_t n) {
+// ... into a buffer of exactly that size
+int upload(fs_batch *b, fs::DeviceBuffer &dst, const double *src, size_t n) {
+  HIP_TRY(dst.ensure(n * b->esz));
+  return upload_to(b, dst.get(), src, n);
+}
+
+int download(fs_batch *b, double *dst, const fs::DeviceBuffer &src, size_t off_elems, size_t n) {
   TraceRange range_("flowsim:download");
   HIP_TRY(hipStreamSynchronize(b->stream));
-  const bool f64 = b->d.dtype == FS_F64;
-  const char *dev = (const char *)src + off_elems * b->esz;
+  const bool f64 = b->esz == sizeof(double);
+  const char *dev = src.get<const char>() + off_elems * b->esz;
   if (n * b->esz < kStageMin || b->stage.init() != 0) {
     if (f64) {
       HIP_TRY(hipMemcpy(dst, dev, n * 8, hipMemcpyDeviceToHost));
@@ -276,7 +295,7 @@ int download(fs_batch *b, double *dst, const void *src, size_t off_elems, size_t
   auto issue = [&](size_t c) -> hipError_t {
     const int slot = (int)(c % kStageSlots);
     const size_t off = c * per, cnt = std::min(per, n - off);
-    hipError_t e = hipMemcpyAsync(b->stage.buf[slot], dev + off * b->esz, cnt * b->esz, hipMemcpyDeviceToHost, b->stream);
+    hipError_t e = hipMemcpyAsync(b->stage.buf[slot].get(), dev + off * b->esz, cnt * b->esz, hipMemcpyDeviceToHost, b->stream);
     if (e == hipSuccess) e = hipEventRecord(b->stage.ev[slot], b->stream);
     return e;
   };
@@ -288,34 +307,14 @@ int download(fs_batch *b, double *dst, const void *src, size_t off_elems, size_t
     HIP_TRY(hipEventSynchronize(b->stage.ev[slot]));
     double *dp = dst + off;
     if (f64) {
-      const double *pin = (const double *)b->stage.buf[slot];
+      const double *pin = b->stage.buf[slot].get<const double>();
       CopyPool::get().run(cnt, [&](size_t lo, size_t hi) { std::memcpy(dp + lo, pin + lo, (hi - lo) * sizeof(double)); });
     } else {
-      const float *pin = (const float *)b->stage.buf[slot];
+      const float *pin = b->stage.buf[slot].get<const float>();
       CopyPool::get().run(cnt, [&](size_t lo, size_t hi) { for (size_t i = lo; i < hi; ++i) dp[i] = pin[i]; });
     }
   }
   return 0;
-}
-
-// The caller's TrapezoidalSection table [FS_GEO_NPARAM][N] plus the rows of what follows from it alone
-// (fs_device.hpp FS_GEOX_*: side-slope roots, bankfull geometry, reciprocal / -1.5-power roughnesses), computed here
-// once in double so that no node evaluation of any Newton iteration has to.
-std::vector<double> extend_table(const double *t, size_t N) {
-  std::vector<double> x((size_t)fs::FS_GEOX_NROWS * N, 0.0);
-  std::memcpy(x.data(), t, (size_t)FS_GEO_NPARAM * N * sizeof(double));
-  auto in = [&](int row, size_t i) { return t[(size_t)row * N + i]; };
-  for (size_t i = 0; i < N; ++i) {
-    const double b = in(FS_GEO_B_MAIN, i), m = in(FS_GEO_M_MAIN, i), hbf = in(FS_GEO_H_BANKFULL, i), mfp = in(FS_GEO_M_FP, i);
-    const double sm = std::sqrt(1.0 + m * m), Tb = b + 2.0 * m * hbf;
-    const double nm = in(FS_GEO_N_MAIN, i), nl = in(FS_GEO_N_LEFT, i), nr = in(FS_GEO_N_RIGHT, i);
-    auto put = [&](int row, double v) { x[(size_t)row * N + i] = v; };
-    put(fs::FS_GEOX_SM, sm); put(fs::FS_GEOX_SFP, std::sqrt(1.0 + mfp * mfp)); put(fs::FS_GEOX_TB, Tb);
-    put(fs::FS_GEOX_AM, (b + Tb) / 2.0 * hbf); put(fs::FS_GEOX_PM, b + 2.0 * hbf * sm);
-    put(fs::FS_GEOX_RNM, nm > 0 ? 1.0 / nm : 0.0); put(fs::FS_GEOX_KM15, nm > 0 ? std::pow(nm, -1.5) : 0.0);
-    put(fs::FS_GEOX_KL15, nl > 0 ? std::pow(nl, -1.5) : 0.0); put(fs::FS_GEOX_KR15, nr > 0 ? std::pow(nr, -1.5) : 0.0);
-  }
-  return x;
 }
 
 // the Newton vector at the two ends of every reach, as doubles: out[4][B] = h_0, Q_0, h_last, Q_last (fs_batch_get_boundary_iterate)
@@ -371,25 +370,26 @@ __global__ void broadcast_state(const R *h, const R *Q, R *hk, R *Qk, R *hg, R *
 template <typename R> void fill_args(const fs_batch *b, int n_steps, fs::KernelArgs<R> &a) {
   a.B = b->d.n_reaches; a.N = b->d.n_nodes; a.n_steps = n_steps; a.level0 = b->level; a.max_iter = b->max_iter;
   a.theta = (R)b->theta; a.dt = (R)b->dt; a.dx = (R)b->dx; a.tol = (R)b->tol;
-  a.hk = (R *)b->hk; a.Qk = (R *)b->Qk; a.hg = (R *)b->hg; a.Qg = (R *)b->Qg;
-  a.geo_uniform = (const R *)b->geo_uniform; a.geo_table = (const R *)b->geo_table;
-  a.n_override = (const R *)b->n_override;
-  a.poly_x = (const R *)b->poly_x; a.poly_z = (const R *)b->poly_z; a.poly_lim = (const R *)b->poly_lim; a.poly_n = b->poly_n;
-  a.poly_tz = (const R *)b->poly_tz; a.poly_K = b->poly_K;
+  a.hk = b->hk.get<R>(); a.Qk = b->Qk.get<R>(); a.hg = b->hg.get<R>(); a.Qg = b->Qg.get<R>();
+  a.geo_uniform = b->geo_uniform.get<R>(); a.geo_table = b->geo_table.get<R>();
+  a.n_override = b->n_override.get<R>();
+  a.poly_x = b->poly_x.get<R>(); a.poly_z = b->poly_z.get<R>(); a.poly_lim = b->poly_lim.get<R>(); a.poly_n = b->poly_n.get<int32_t>();
+  a.poly_tz = b->poly_tz.get<R>(); a.poly_K = b->poly_K;
   a.geo_reach_stride = (int64_t)b->geo_reach_stride; a.poly_reach_stride = (int64_t)b->poly_reach_stride;
-  a.reach_nodes = b->reach_nodes; a.reach_scheme = (const R *)b->reach_scheme;
-  a.reach_kinds = (b->kinds_per_reach[0] || b->kinds_per_reach[1]) ? b->reach_kinds : nullptr;
+  a.reach_nodes = b->reach_nodes.get<int32_t>(); a.reach_scheme = b->reach_scheme.get<R>();
+  a.reach_kinds = (b->kinds_per_reach[0] || b->kinds_per_reach[1]) ? b->reach_kinds.get<int32_t>() : nullptr;
   fs::BCDesc<R> *bc[2] = {&a.us, &a.ds};
   for (int s = 0; s < 2; ++s) {
     bc[s]->kind = b->bc_kind[s]; bc[s]->stride = b->bc_stride[s];
-    bc[s]->params = (const R *)b->bc_params[s]; bc[s]->target = (const R *)b->bc_target[s]; bc[s]->tgt = R(0);
+    bc[s]->params = b->bc_params[s].get<R>(); bc[s]->target = b->bc_target[s].get<R>(); bc[s]->tgt = R(0);
   }
-  a.Yprev = (R *)b->Yprev; a.stage_hist = (R *)b->stage_hist; a.trace = (R *)b->trace; a.hydro = (R *)b->hydro; a.iters = b->iters; a.status = b->status;
-  a.hist_h = (R *)b->hist_h; a.hist_Q = (R *)b->hist_Q;
-  a.dbg = b->dbg;
-  a.kc_scratch = (R *)b->kc_scratch; a.passes = b->passes;
-  a.team_size = b->team_size; a.team_mail = (R *)b->team_mail; a.team_sync = b->team_sync; a.team_epoch = b->team_epoch;
-  a.iter_budget = 0; a.it_done = b->it_done;
+  a.Yprev = b->Yprev.get<R>(); a.stage_hist = b->stage_hist.get<R>(); a.trace = b->trace.get<R>(); a.hydro = b->hydro.get<R>();
+  a.iters = b->iters.get<int32_t>(); a.status = b->status.get<int32_t>();
+  a.hist_h = b->hist_h.get<R>(); a.hist_Q = b->hist_Q.get<R>();
+  a.dbg = b->dbg.get<unsigned long long>();
+  a.kc_scratch = b->kc_scratch.get<R>(); a.passes = b->passes;
+  a.team_size = b->team_size; a.team_mail = b->team_mail.get<R>(); a.team_sync = b->team_sync.get<unsigned long long>(); a.team_epoch = b->team_epoch;
+  a.iter_budget = 0; a.it_done = b->it_done.get<int32_t>();
 }
 
 // picks the instantiation for the batch as it is now (the boundary kinds are known) and launches it on the handle's stream
@@ -414,11 +414,7 @@ int launch_steps(fs_batch *b, int n_steps, int iter_budget) {
     // (uniform sections recompute their level constants, fs_long.hpp: no scratch)
     const bool recompute = FS_LONG_RECOMPUTE && (b->d.section_mode == FS_SEC_RECT_UNIFORM || b->d.section_mode == FS_SEC_TRAP_UNIFORM);
     const size_t need = recompute ? 0 : (size_t)b->d.n_reaches * 4 * b->passes * chunk;
-    if (b->kc_scratch_elems < need) {
-      if (b->kc_scratch) { (void)hipFree(b->kc_scratch); b->kc_scratch = nullptr; b->kc_scratch_elems = 0; }
-      HIP_TRY(hipMalloc(&b->kc_scratch, need * b->esz));
-      b->kc_scratch_elems = need;
-    }
+    HIP_TRY(b->kc_scratch.reserve(need * b->esz));
   }
   b->team_size = 0;
   if (k->key.team) {       // G workgroups per reach: their mailboxes and counters (the counters start every launch at zero)
@@ -426,29 +422,110 @@ int launch_steps(fs_batch *b, int n_steps, int iter_budget) {
     b->team_size = (int)((b->d.n_nodes + chunk - 1) / chunk);
     // (16 bytes per word: the tagged form posts (value, tag) pairs; zeroed once - a tag is never 0, launches count from 1)
     const size_t need = B * 2 * ((size_t)b->team_size * k->key.W + 1) * fs::kTeamWords * 2;
-    if (b->team_mail_elems < need) {
-      if (b->team_mail) { (void)hipFree(b->team_mail); b->team_mail = nullptr; b->team_mail_elems = 0; }
-      HIP_TRY(hipMalloc(&b->team_mail, need * sizeof(double)));
-      HIP_TRY(hipMemsetAsync(b->team_mail, 0, need * sizeof(double), b->stream));
-      b->team_mail_elems = need;
-    }
+    bool grew = false;
+    HIP_TRY(b->team_mail.reserve(need * sizeof(double), &grew));
+    if (grew) HIP_TRY(hipMemsetAsync(b->team_mail.get(), 0, need * sizeof(double), b->stream));
     ++b->team_epoch;
-    if (!b->team_sync) HIP_TRY(hipMalloc((void **)&b->team_sync, (1 + B) * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(b->team_sync, 0, (1 + B) * sizeof(unsigned long long), b->stream));
+    HIP_TRY(b->team_sync.ensure((1 + B) * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(b->team_sync.get(), 0, (1 + B) * sizeof(unsigned long long), b->stream));
   }
   HIP_TRY(hipEventRecord(b->ev0, b->stream));
-  if (b->d.dtype == FS_F64) {
-    fs::KernelArgs<double> a; fill_args(b, n_steps, a);
+  with_real(b, [&](auto real) {
+    fs::KernelArgs<decltype(real)> a; fill_args(b, n_steps, a);
     a.iter_budget = iter_budget;
     b->kern->fn(&a, b->d.n_reaches, b->stream);
-  } else {
-    fs::KernelArgs<float> a; fill_args(b, n_steps, a);
-    a.iter_budget = iter_budget;
-    b->kern->fn(&a, b->d.n_reaches, b->stream);
-  }
+  });
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(b->ev1, b->stream));
   b->timed = true; b->launches = 1;
+  return 0;
+}
+
+// ---- steps that several entry points share ----
+
+int check_side(const char *entry, int32_t side) {
+  if (side != FS_UPSTREAM && side != FS_DOWNSTREAM) return fail(std::string(entry) + ": side must be FS_UPSTREAM or FS_DOWNSTREAM");
+  return 0;
+}
+
+int check_levels(const fs_batch *b, const char *entry, int32_t first, int32_t n) {
+  if (first < 0 || n < 1 || first + n > b->d.max_levels) return fail(std::string(entry) + ": level range out of bounds");
+  return 0;
+}
+
+int check_ready(const fs_batch *b, const char *entry) {
+  if (!b->have_scheme || !b->have_geo || !b->have_state || !b->have_bc[0] || !b->have_bc[1])
+    return fail(std::string(entry) + ": scheme, geometry, both boundaries and the initial state must be set first");
+  return 0;
+}
+
+// the per-reach Manning n of the main channel: the caller's, or none
+int set_n_override(fs_batch *b, const double *n_main_override) {
+  if (n_main_override) return upload(b, b->n_override, n_main_override, b->d.n_reaches);
+  b->n_override.reset();
+  return 0;
+}
+
+// a side's parameters and target hydrographs replaced by the caller's (params == nullptr: n_params rows of zeros; n_params == 0: none)
+int replace_bc_buffers(fs_batch *b, int side, const double *params, size_t n_params, const double *target) {
+  b->bc_params[side].reset();
+  b->bc_target[side].reset();
+  if (params) {
+    if (n_params > 0 && upload(b, b->bc_params[side], params, n_params)) return -1;
+  } else if (n_params > 0) {
+    HIP_TRY(b->bc_params[side].ensure(n_params * b->esz));
+    HIP_TRY(hipMemsetAsync(b->bc_params[side].get(), 0, n_params * b->esz, b->stream));
+  }
+  if (target && upload(b, b->bc_target[side], target, (size_t)b->d.max_levels * b->d.n_reaches)) return -1;
+  return 0;
+}
+
+// one kind into every slot of a side of reach_kinds
+int fill_side_kinds(fs_batch *b, int side, int kind) {
+  const size_t B = b->d.n_reaches;
+  const std::vector<int32_t> same(B, kind);
+  HIP_TRY(hipMemcpy(b->reach_kinds.get<int32_t>() + (size_t)side * B, same.data(), B * 4, hipMemcpyHostToDevice));
+  return 0;
+}
+
+// a new initial state is on the device: the per-level records start over
+int begin_at_level0(fs_batch *b) {
+  const size_t B = b->d.n_reaches, L = b->d.max_levels;
+  HIP_TRY(hipMemsetAsync(b->status.get(), 0, B * 4, b->stream));
+  HIP_TRY(hipMemsetAsync(b->iters.get(), 0, L * B * 4, b->stream));
+  HIP_TRY(hipMemsetAsync(b->Yprev.get(), 0, B * b->esz, b->stream));
+  if (b->trace) HIP_TRY(hipMemsetAsync(b->trace.get(), 0, L * FS_TRACE_CAP * B * b->esz, b->stream));
+  HIP_TRY(hipMemsetAsync(b->it_done.get(), 0, B * 4, b->stream));
+  b->level = 0; b->iterating = false; b->restart_level = 0;
+  b->have_state = true;
+  return 0;
+}
+
+// stream, events and the buffers every batch has, on the batch's device (which stays current)
+int init_batch(fs_batch *b) {
+  HIP_TRY(hipSetDevice(b->d.device));
+  HIP_TRY(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+  HIP_TRY(hipEventCreate(&b->ev0));
+  HIP_TRY(hipEventCreate(&b->ev1));
+  const size_t B = b->d.n_reaches, N = b->d.n_nodes, L = b->d.max_levels, esz = b->esz;
+  auto zeroed = [&](fs::DeviceBuffer &buf, size_t bytes) -> int {
+    HIP_TRY(buf.ensure(bytes));
+    HIP_TRY(hipMemsetAsync(buf.get(), 0, bytes, b->stream));
+    return 0;
+  };
+  for (fs::DeviceBuffer *p : {&b->hk, &b->Qk, &b->hg, &b->Qg}) HIP_TRY(p->ensure(B * N * esz));
+  if (zeroed(b->hydro, L * 4 * B * esz) || zeroed(b->iters, L * B * 4) || zeroed(b->status, B * 4) || zeroed(b->Yprev, B * esz) ||
+      zeroed(b->stage_hist, L * B * esz) || zeroed(b->it_done, B * 4)) return -1;
+  if ((b->d.flags & FS_FLAG_TRACE) && zeroed(b->trace, L * FS_TRACE_CAP * B * esz)) return -1;
+  if (b->d.flags & FS_FLAG_HISTORY) {
+    HIP_TRY(b->hist_h.ensure(L * B * N * esz));
+    HIP_TRY(b->hist_Q.ensure(L * B * N * esz));
+  }
+#ifdef FS_STAMP
+  if (zeroed(b->dbg, B * 16 * 12 * 8)) return -1;
+#endif
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  if (B * N * esz >= kStageMin) (void)b->stage.init();        // large batch: the pinned chunks exist before the first transfer is timed
   return 0;
 }
 
@@ -498,68 +575,21 @@ fs_batch *fs_batch_create(const fs_batch_desc *desc) {
   b->kern = &kEntries[chosen];
   int prev_dev = -1;
   if (hipGetDevice(&prev_dev) != hipSuccess) prev_dev = -1;
-  auto bad = [&](const char *what, hipError_t e) {
-    fail(std::string("fs_batch_create: ") + what + ": " + hipGetErrorString(e));
+  if (init_batch(b)) {
+    const std::string what = g_err;
     fs_batch_destroy(b);
-    if (prev_dev >= 0) (void)hipSetDevice(prev_dev);
-    return (fs_batch *)nullptr;
-  };
-  hipError_t e;
-  if ((e = hipSetDevice(desc->device)) != hipSuccess) return bad("hipSetDevice", e);
-  if ((e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking)) != hipSuccess) return bad("hipStreamCreate", e);
-  if ((e = hipEventCreate(&b->ev0)) != hipSuccess) return bad("hipEventCreate", e);
-  if ((e = hipEventCreate(&b->ev1)) != hipSuccess) return bad("hipEventCreate", e);
-  const size_t B = desc->n_reaches, N = desc->n_nodes, L = desc->max_levels;
-  void **state[4] = {&b->hk, &b->Qk, &b->hg, &b->Qg};
-  for (void **p : state)
-    if ((e = hipMalloc(p, B * N * b->esz)) != hipSuccess) return bad("hipMalloc(state)", e);
-  if ((e = hipMalloc(&b->hydro, L * 4 * B * b->esz)) != hipSuccess) return bad("hipMalloc(hydro)", e);
-  if ((e = hipMalloc((void **)&b->iters, L * B * 4)) != hipSuccess) return bad("hipMalloc(iters)", e);
-  if ((e = hipMalloc((void **)&b->status, B * 4)) != hipSuccess) return bad("hipMalloc(status)", e);
-  if ((e = hipMalloc(&b->Yprev, B * b->esz)) != hipSuccess) return bad("hipMalloc(Yprev)", e);
-  if ((e = hipMalloc(&b->stage_hist, L * B * b->esz)) != hipSuccess) return bad("hipMalloc(stage_hist)", e);
-  if ((e = hipMalloc((void **)&b->it_done, B * 4)) != hipSuccess) return bad("hipMalloc(it_done)", e);
-  if ((e = hipMemsetAsync(b->stage_hist, 0, L * B * b->esz, b->stream)) != hipSuccess) return bad("hipMemsetAsync", e);
-  if ((e = hipMemsetAsync(b->it_done, 0, B * 4, b->stream)) != hipSuccess) return bad("hipMemsetAsync", e);
-  if (desc->flags & FS_FLAG_TRACE) {
-    if ((e = hipMalloc(&b->trace, L * FS_TRACE_CAP * B * b->esz)) != hipSuccess) return bad("hipMalloc(trace)", e);
-    if ((e = hipMemsetAsync(b->trace, 0, L * FS_TRACE_CAP * B * b->esz, b->stream)) != hipSuccess) return bad("hipMemsetAsync", e);
+    b = nullptr;
+    fail("fs_batch_create: " + what);
   }
-  if (desc->flags & FS_FLAG_HISTORY) {
-    if ((e = hipMalloc(&b->hist_h, L * B * N * b->esz)) != hipSuccess) return bad("hipMalloc(history)", e);
-    if ((e = hipMalloc(&b->hist_Q, L * B * N * b->esz)) != hipSuccess) return bad("hipMalloc(history)", e);
-  }
-#ifdef FS_STAMP
-  if ((e = hipMalloc((void **)&b->dbg, B * 16 * 12 * 8)) != hipSuccess) return bad("hipMalloc(dbg)", e);
-  hipMemsetAsync(b->dbg, 0, B * 16 * 12 * 8, b->stream);
-#endif
-  if ((e = hipMemsetAsync(b->hydro, 0, L * 4 * B * b->esz, b->stream)) != hipSuccess) return bad("hipMemsetAsync", e);
-  if ((e = hipMemsetAsync(b->iters, 0, L * B * 4, b->stream)) != hipSuccess) return bad("hipMemsetAsync", e);
-  if ((e = hipMemsetAsync(b->status, 0, B * 4, b->stream)) != hipSuccess) return bad("hipMemsetAsync", e);
-  if ((e = hipMemsetAsync(b->Yprev, 0, B * b->esz, b->stream)) != hipSuccess) return bad("hipMemsetAsync", e);
-  if ((e = hipStreamSynchronize(b->stream)) != hipSuccess) return bad("hipStreamSynchronize", e);
-  if (B * N * b->esz >= kStageMin) (void)b->stage.init();        // large batch: the pinned chunks exist before the first transfer is timed
-  (void)hipSetDevice(prev_dev >= 0 ? prev_dev : desc->device);
+  if (prev_dev >= 0) (void)hipSetDevice(prev_dev);
   return b;
 }
 
+// (the buffers go while the stream and the events still exist: fs_batch's members before its base, Timeline)
 void fs_batch_destroy(fs_batch *b) {
   if (!b) return;
   DeviceGuard guard_(b->d.device);
   if (b->stream) (void)hipStreamSynchronize(b->stream);
-  void *bufs[] = {b->hk, b->Qk, b->hg, b->Qg, b->geo_uniform, b->geo_table, b->n_override, b->bc_params[0],
-                  b->bc_params[1], b->bc_target[0], b->bc_target[1], b->Yprev, b->stage_hist, b->trace, b->hydro, b->hist_h, b->hist_Q,
-                  b->iters, b->status, b->poly_x, b->poly_z, b->poly_lim, b->poly_n, b->it_done, b->dbg, b->reach_nodes,
-                  b->reach_scheme, b->reach_kinds, b->kc_scratch, b->poly_tz, b->ends_dev, b->open_dev, b->team_mail, b->team_sync};
-  for (void *p : bufs) if (p) (void)hipFree(p);
-  if (b->rows_stage) (void)hipFree(b->rows_stage);
-  if (b->ends_pin) (void)hipHostFree(b->ends_pin);
-  if (b->open_pin) (void)hipHostFree(b->open_pin);
-  for (void *p : b->derived) if (p) (void)hipFree(p);
-  b->stage.release();
-  if (b->ev0) (void)hipEventDestroy(b->ev0);
-  if (b->ev1) (void)hipEventDestroy(b->ev1);
-  if (b->stream) (void)hipStreamDestroy(b->stream);
   delete b;
 }
 
@@ -588,7 +618,7 @@ int fs_batch_set_geometry_uniform(fs_batch *b, const double *params) {
       return fail("fs_batch_set_geometry_uniform: width and Manning n must be positive");
     if (trap && !(params[FS_TU_SIDE_SLOPE * B + i] >= 0)) return fail("fs_batch_set_geometry_uniform: side slope must be >= 0");
   }
-  if (upload(b, &b->geo_uniform, params, (size_t)(trap ? FS_TU_NPARAM : FS_RU_NPARAM) * B)) return -1;
+  if (upload(b, b->geo_uniform, params, (size_t)(trap ? FS_TU_NPARAM : FS_RU_NPARAM) * B)) return -1;
   b->have_geo = true;
   return 0;
 }
@@ -597,110 +627,43 @@ int fs_batch_set_geometry_table(fs_batch *b, const double *table, const double *
   if (!b || !table) return fail("fs_batch_set_geometry_table: null argument");
   if (b->d.section_mode != FS_SEC_TABLE) return fail("fs_batch_set_geometry_table: batch was created with another section_mode");
   FS_ON_DEVICE(b);
-  {
-    const std::vector<double> x = extend_table(table, b->d.n_nodes);
-    if (b->geo_reach_stride) { (void)hipFree(b->geo_table); b->geo_table = nullptr; b->geo_reach_stride = 0; }
-    if (upload(b, &b->geo_table, x.data(), x.size())) return -1;
-  }
-  if (n_main_override) {
-    if (upload(b, &b->n_override, n_main_override, b->d.n_reaches)) return -1;
-  } else if (b->n_override) {
-    (void)hipFree(b->n_override); b->n_override = nullptr;
-  }
+  const std::vector<double> x = fs::extend_table(table, b->d.n_nodes);
+  b->geo_reach_stride = 0;
+  if (upload(b, b->geo_table, x.data(), x.size()) || set_n_override(b, n_main_override)) return -1;
   b->have_geo = true;
   return 0;
 }
 
-// polylines of one channel: validated and transposed into the vertex-major device layout ([P][N]; unused slots repeat the last
-// vertex so that no lane ever reads NaN).  Returns an error text or nullptr.
-static const char *pack_polylines(const double *table, const int32_t *n_pts, int32_t max_pts, const double *x, const double *z,
-                                  const double *limits, size_t N, double *xt, double *zt, double *lim, double *tz) {
-  const size_t P = max_pts;
-  for (size_t i = 0; i < N; ++i) {
-    const int c = n_pts[i];
-    if (c == 0) continue;
-    if (c < 2 || c > max_pts) return "fs_batch_set_geometry_irregular: n_pts must be 0 or 2..max_pts";
-    double zmin = z[i * P];
-    for (int j = 0; j < c; ++j) {
-      const double xv = x[i * P + j], zv = z[i * P + j];
-      if (!(xv == xv) || !(zv == zv)) return "x and z must have the same shape";            // cross_section.py:222 (NaN padding inside the count)
-      if (j && xv < x[i * P + j - 1]) return "fs_batch_set_geometry_irregular: x must be ascending (IrregularSection sorts it, cross_section.py:231)";
-      zmin = zv < zmin ? zv : zmin;
-    }
-    if (table[(size_t)FS_GEO_Z_BED * N + i] != zmin)
-      return "fs_batch_set_geometry_irregular: table row Z_BED must hold min(z) of a polyline node (IrregularSection.z_min)";
-    for (size_t j = 0; j < P; ++j) {
-      const size_t src = i * P + (j < (size_t)c ? j : (size_t)c - 1);
-      xt[j * N + i] = x[src]; zt[j * N + i] = z[src];
-    }
-    lim[i] = limits[2 * i]; lim[N + i] = limits[2 * i + 1];
-    const double node_const[5] = {table[(size_t)FS_GEO_N_LEFT * N + i], table[(size_t)FS_GEO_N_MAIN * N + i],
-                                  table[(size_t)FS_GEO_N_RIGHT * N + i], table[(size_t)FS_GEO_CURVATURE * N + i], zmin};
-    if (!tz) continue;                 // no stage tables for this batch (set_irregular): the kernels walk the edges
-    // the node's table, then into the device layout: breakpoints [N][KP], intervals [P][FS_PT_BLOCK / 2][N] pairs (fs_poly.hpp)
-    std::vector<double> blk(fs::poly_table_stride(max_pts));
-    fs::build_stage_table(x + i * P, z + i * P, c, limits[2 * i], limits[2 * i + 1], max_pts, blk.data(), node_const);
-    fs::pack_stage_table_node(blk.data(), max_pts, N, i, tz);
-  }
-  return nullptr;
-}
-
 // n_sets = 1: one channel shared by the batch; n_sets = B: one per reach (tables [B][NPARAM][N], n_pts [B][N], x / z [B][N][P],
-// limits [B][N][2])
+// limits [B][N][2]).  What goes to the device, and whether with stage tables: fs::plan_irregular
 static int set_irregular(fs_batch *b, const double *table, const int32_t *n_pts, int32_t max_pts, const double *x, const double *z,
                          const double *limits, const double *n_main_override, size_t n_sets) {
   if (!b || !table || !n_pts || !x || !z || !limits) return fail("fs_batch_set_geometry_irregular: null argument");
   if (b->d.section_mode != FS_SEC_IRREGULAR) return fail("fs_batch_set_geometry_irregular: batch was created with another section_mode");
   if (max_pts < 2) return fail("fs_batch_set_geometry_irregular: max_pts must be >= 2");
   FS_ON_DEVICE(b);
-  const size_t N = b->d.n_nodes, P = max_pts, per = (size_t)fs::FS_GEOX_NROWS * N;
-  std::vector<double> xt(n_sets * P * N, 0.0), zt(n_sets * P * N, 0.0), lim(n_sets * 2 * N, 0.0), tabs(n_sets * per);
-  // Stage tables: poly_table_stride(P) numbers per node (about 10 KB at 40 stations) - times N, times one set per reach for
-  // per-reach channels.  Beyond a bound (FS_POLY_TABLE_MAX_BYTES, default 8 GiB: staged once on the host, then resident in HBM)
-  // the batch gets no tables and every evaluation walks its polyline's edges (fs_poly.hpp: poly_K = 0, the round-2 path - same
-  // results, about five times the instructions); FS_POLY_WALK=1 forces that path.  fs_batch_poly_tables() says which one it is.
-  const size_t tstride = (size_t)fs::poly_table_stride(max_pts);
-  size_t table_cap = (size_t)8 << 30;
-  if (const char *env = std::getenv("FS_POLY_TABLE_MAX_BYTES")) table_cap = (size_t)std::strtoull(env, nullptr, 10);
-  const double table_bytes = (double)n_sets * (double)N * (double)tstride * sizeof(double);
-  const bool walk = std::getenv("FS_POLY_WALK") != nullptr || table_bytes > (double)table_cap;
-  std::vector<double> tz;
-  try {
-    if (!walk) tz.assign(n_sets * N * tstride, std::numeric_limits<double>::infinity());
-  } catch (const std::bad_alloc &) {
-    return fail("fs_batch_set_geometry_irregular: no host memory to stage " + std::to_string((size_t)(table_bytes / (1 << 20))) +
-                " MiB of stage tables (lower FS_POLY_TABLE_MAX_BYTES to fall back to the edge walk)");
-  }
-  for (size_t r = 0; r < n_sets; ++r) {
-    const double *tab_r = table + r * FS_GEO_NPARAM * N;
-    if (const char *err = pack_polylines(tab_r, n_pts + r * N, max_pts, x + r * N * P, z + r * N * P, limits + r * 2 * N, N,
-                                         xt.data() + r * P * N, zt.data() + r * P * N, lim.data() + r * 2 * N,
-                                         walk ? nullptr : tz.data() + r * N * tstride))
-      return fail(err);
-    const std::vector<double> ext = extend_table(tab_r, N);
-    std::memcpy(tabs.data() + r * per, ext.data(), per * sizeof(double));
-  }
-  void **old[] = {&b->geo_table, &b->poly_x, &b->poly_z, &b->poly_lim, &b->poly_tz};
-  for (void **q : old) if (*q) { (void)hipFree(*q); *q = nullptr; }
-  if (b->poly_n) { (void)hipFree(b->poly_n); b->poly_n = nullptr; }
+  const size_t N = b->d.n_nodes, P = max_pts;
+  fs::PolyTableLimits how;
+  if (const char *env = std::getenv("FS_POLY_TABLE_MAX_BYTES")) how.max_bytes = (size_t)std::strtoull(env, nullptr, 10);
+  how.force_walk = std::getenv("FS_POLY_WALK") != nullptr;
+  fs::IrregularPlan plan;
+  const std::string err = fs::plan_irregular(table, n_pts, max_pts, x, z, limits, N, n_sets, how, plan);
+  if (!err.empty()) return fail(err);
+  for (fs::DeviceBuffer *q : {&b->geo_table, &b->poly_x, &b->poly_z, &b->poly_lim, &b->poly_tz, &b->poly_n}) q->reset();
   b->poly_K = 0;
-  if (!walk) {
-    if (upload(b, &b->poly_tz, tz.data(), tz.size()))
-      return fail("fs_batch_set_geometry_irregular: " + std::to_string((size_t)(table_bytes / (1 << 20))) + " MiB of stage tables do not fit the "
+  if (!plan.walk) {
+    if (upload(b, b->poly_tz, plan.tz.data(), plan.tz.size()))
+      return fail("fs_batch_set_geometry_irregular: " + std::to_string(plan.table_mib) + " MiB of stage tables do not fit the "
                   "device (" + g_err + "); lower FS_POLY_TABLE_MAX_BYTES to fall back to the edge walk");
     b->poly_K = (int)P;
   }
-  if (upload(b, &b->geo_table, tabs.data(), tabs.size()) || upload(b, &b->poly_x, xt.data(), xt.size()) ||
-      upload(b, &b->poly_z, zt.data(), zt.size()) || upload(b, &b->poly_lim, lim.data(), lim.size())) return -1;
-  HIP_TRY(hipMalloc((void **)&b->poly_n, n_sets * N * 4));
-  HIP_TRY(hipMemcpy(b->poly_n, n_pts, n_sets * N * 4, hipMemcpyHostToDevice));
-  b->geo_reach_stride = n_sets > 1 ? per : 0;
+  if (upload(b, b->geo_table, plan.tabs.data(), plan.tabs.size()) || upload(b, b->poly_x, plan.xt.data(), plan.xt.size()) ||
+      upload(b, b->poly_z, plan.zt.data(), plan.zt.size()) || upload(b, b->poly_lim, plan.lim.data(), plan.lim.size())) return -1;
+  HIP_TRY(b->poly_n.ensure(n_sets * N * 4));
+  HIP_TRY(hipMemcpy(b->poly_n.get(), n_pts, n_sets * N * 4, hipMemcpyHostToDevice));
+  b->geo_reach_stride = n_sets > 1 ? (size_t)fs::FS_GEOX_NROWS * N : 0;
   b->poly_reach_stride = n_sets > 1 ? P * N : 0;
-  if (n_main_override) {
-    if (upload(b, &b->n_override, n_main_override, b->d.n_reaches)) return -1;
-  } else if (b->n_override) {
-    (void)hipFree(b->n_override); b->n_override = nullptr;
-  }
+  if (set_n_override(b, n_main_override)) return -1;
   b->have_geo = true;
   return 0;
 }
@@ -728,17 +691,12 @@ int fs_batch_set_geometry_table_per_reach(fs_batch *b, const double *tables, con
   const size_t B = b->d.n_reaches, N = b->d.n_nodes, per = (size_t)fs::FS_GEOX_NROWS * N;
   std::vector<double> all(B * per);
   for (size_t r = 0; r < B; ++r) {
-    const std::vector<double> x = extend_table(tables + r * FS_GEO_NPARAM * N, N);
+    const std::vector<double> x = fs::extend_table(tables + r * FS_GEO_NPARAM * N, N);
     std::memcpy(all.data() + r * per, x.data(), per * sizeof(double));
   }
-  if (b->geo_table) { (void)hipFree(b->geo_table); b->geo_table = nullptr; }
-  if (upload(b, &b->geo_table, all.data(), all.size())) return -1;
+  if (upload(b, b->geo_table, all.data(), all.size())) return -1;
   b->geo_reach_stride = per;
-  if (n_main_override) {
-    if (upload(b, &b->n_override, n_main_override, B)) return -1;
-  } else if (b->n_override) {
-    (void)hipFree(b->n_override); b->n_override = nullptr;
-  }
+  if (set_n_override(b, n_main_override)) return -1;
   b->have_geo = true;
   return 0;
 }
@@ -751,42 +709,34 @@ int fs_batch_set_reach_nodes(fs_batch *b, const int32_t *n_nodes) {
   // already on the device and has not been stepped, the row follows them
   auto refresh_row0 = [&]() -> int {
     if (!b->have_state || b->level != 0) return 0;
-    const dim3 grid((unsigned)((B + 255) / 256));
-    if (b->d.dtype == FS_F64)
-      hipLaunchKernelGGL((refresh_level0_downstream<double>), grid, dim3(256), 0, b->stream, (const double *)b->hk, (const double *)b->Qk,
-                         b->reach_nodes, (double *)b->hydro, B, (size_t)b->d.n_nodes);
-    else
-      hipLaunchKernelGGL((refresh_level0_downstream<float>), grid, dim3(256), 0, b->stream, (const float *)b->hk, (const float *)b->Qk,
-                         b->reach_nodes, (float *)b->hydro, B, (size_t)b->d.n_nodes);
+    with_real(b, [&](auto real) {
+      using R = decltype(real);
+      hipLaunchKernelGGL((refresh_level0_downstream<R>), grid_256(B), dim3(256), 0, b->stream, b->hk.get<const R>(), b->Qk.get<const R>(),
+                         b->reach_nodes.get<const int32_t>(), b->hydro.get<R>(), B, (size_t)b->d.n_nodes);
+    });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(b->stream));
     return 0;
   };
   if (!n_nodes) {
-    if (b->reach_nodes) { (void)hipFree(b->reach_nodes); b->reach_nodes = nullptr; }
+    b->reach_nodes.reset();
     b->reach_nodes_host.clear();
     return refresh_row0();
   }
   for (size_t r = 0; r < B; ++r)
     if (n_nodes[r] < 2 || n_nodes[r] > b->d.n_nodes) return fail("fs_batch_set_reach_nodes: every reach needs 2 <= nodes <= n_nodes of the batch");
-  if (!b->reach_nodes) HIP_TRY(hipMalloc((void **)&b->reach_nodes, B * 4));
-  HIP_TRY(hipMemcpy(b->reach_nodes, n_nodes, B * 4, hipMemcpyHostToDevice));
+  HIP_TRY(b->reach_nodes.ensure(B * 4));
+  HIP_TRY(hipMemcpy(b->reach_nodes.get(), n_nodes, B * 4, hipMemcpyHostToDevice));
   b->reach_nodes_host.assign(n_nodes, n_nodes + B);
   return refresh_row0();
 }
 
-// the [5][B] array the kernels of boundary classes 0 and -1 read: per-reach values where the caller gave them, the batch's elsewhere
+// the [5][B] array of per-reach scheme values (fs::merge_reach_scheme) on the device, or none
 static int rebuild_reach_scheme(fs_batch *b) {
-  const size_t B = b->d.n_reaches;
-  if (b->reach_scheme) { (void)hipFree(b->reach_scheme); b->reach_scheme = nullptr; }
-  bool any = false;
-  for (auto &v : b->rs_host) any = any || !v.empty();
-  if (!any) return 0;
   const double wide[5] = {b->theta, b->dt, b->dx, b->tol, (double)b->max_iter};
-  std::vector<double> v(5 * B);
-  for (int i = 0; i < 5; ++i)
-    for (size_t r = 0; r < B; ++r) v[i * B + r] = b->rs_host[i].empty() ? wide[i] : b->rs_host[i][r];
-  return upload(b, &b->reach_scheme, v.data(), v.size());
+  const std::vector<double> v = fs::merge_reach_scheme(b->rs_host, wide, b->d.n_reaches);
+  b->reach_scheme.reset();
+  return v.empty() ? 0 : upload(b, b->reach_scheme, v.data(), v.size());
 }
 
 int fs_batch_set_reach_scheme(fs_batch *b, const double *theta, const double *dt, const double *dx) {
@@ -823,59 +773,24 @@ int fs_batch_set_bc_per_reach(fs_batch *b, int32_t side, const int32_t *kinds, c
 int fs_batch_set_bc_per_reach_wide(fs_batch *b, int32_t side, const int32_t *kinds, const double *params, int32_t n_params,
                                    const double *target) {
   if (!b || !kinds || !params) return fail("fs_batch_set_bc_per_reach: null argument");
-  if (side != FS_UPSTREAM && side != FS_DOWNSTREAM) return fail("fs_batch_set_bc_per_reach: side must be FS_UPSTREAM or FS_DOWNSTREAM");
+  if (check_side("fs_batch_set_bc_per_reach", side)) return -1;
   if (n_params < FS_BC_MAX_PARAMS) return fail("fs_batch_set_bc_per_reach: at least FS_BC_MAX_PARAMS parameter rows");
   FS_ON_DEVICE(b);
   const size_t B = b->d.n_reaches;
   const bool tables = b->d.section_mode == FS_SEC_TABLE || b->d.section_mode == FS_SEC_IRREGULAR;
-  bool need_target = false;
-  for (size_t r = 0; r < B; ++r) {
-    if (kinds[r] == FS_BC_STORAGE_CURVE) {   // a general reservoir behind THIS reach: its FS_SC_* rows, its own area curve of its own length
-      if (!tables) return fail("fs_batch_set_bc_per_reach: FS_BC_STORAGE_CURVE needs section mode FS_SEC_TABLE or FS_SEC_IRREGULAR");
-      if (side != FS_DOWNSTREAM) return fail("fs_batch_set_bc: the storage boundary is downstream only");
-      auto at = [&](int i) { return params[(size_t)i * B + r]; };
-      const int nc = n_params > FS_SC_N_CURVE ? (int)at(FS_SC_N_CURVE) : -1;
-      if (nc < 0 || nc == 1 || FS_SC_NFIXED + 2 * nc > n_params)
-        return fail("fs_batch_set_bc_per_reach: an FS_BC_STORAGE_CURVE reach needs FS_SC_NFIXED + 2*n_curve parameter rows (n_curve 0 or >= 2)");
-      for (int j = 0; j + 1 < nc; ++j)
-        if (!(at(FS_SC_NFIXED + j + 1) > at(FS_SC_NFIXED + j))) return fail("fs_batch_set_bc: area-curve stages must be increasing");
-      if (nc == 0 && !(at(FS_SC_SURFACE_AREA) > 0)) return fail("Insufficient arguments for boundary condition.");
-      continue;
-    }
-    if (kinds[r] == FS_BC_HOST_ROW) {      // a plugin without a device form on THIS reach (round 4: until then a batch-wide kind only)
-      if (!tables) return fail("fs_batch_set_bc_per_reach: FS_BC_HOST_ROW needs section mode FS_SEC_TABLE or FS_SEC_IRREGULAR");
-      continue;
-    }
-    if (kinds[r] < 0 || kinds[r] > FS_BC_STORAGE) return fail("Invalid boundary condition.");        // boundary.py:33
-    if (kinds[r] == FS_BC_STORAGE && side != FS_DOWNSTREAM) return fail("fs_batch_set_bc: the storage boundary is downstream only");
-    need_target = need_target || kinds[r] == FS_BC_FLOW_HYDROGRAPH || kinds[r] == FS_BC_STAGE_HYDROGRAPH;
-  }
-  if (need_target && !target) return fail("Insufficient arguments for boundary condition.");                     // boundary.py:87
-  if (b->bc_params[side]) { (void)hipFree(b->bc_params[side]); b->bc_params[side] = nullptr; }
-  if (b->bc_target[side]) { (void)hipFree(b->bc_target[side]); b->bc_target[side] = nullptr; }
-  if (upload(b, &b->bc_params[side], params, (size_t)n_params * B)) return -1;
-  if (target && upload(b, &b->bc_target[side], target, (size_t)b->d.max_levels * B)) return -1;
+  fs::SideKinds sk;
+  if (const char *err = fs::check_bc_per_reach(side, kinds, params, n_params, target != nullptr, B, tables, sk)) return fail(err);
+  if (replace_bc_buffers(b, side, params, (size_t)n_params * B, target)) return -1;
   if (!b->reach_kinds) {
-    HIP_TRY(hipMalloc((void **)&b->reach_kinds, 2 * B * 4));
-    HIP_TRY(hipMemset(b->reach_kinds, 0, 2 * B * 4));
+    HIP_TRY(b->reach_kinds.ensure(2 * B * 4));
+    HIP_TRY(hipMemset(b->reach_kinds.get(), 0, 2 * B * 4));
   }
-  HIP_TRY(hipMemcpy(b->reach_kinds + (size_t)side * B, kinds, B * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b->reach_kinds.get<int32_t>() + (size_t)side * B, kinds, B * 4, hipMemcpyHostToDevice));
   // the other side, if it was set for the whole batch, keeps its one kind in every slot
   const int other = 1 - side;
-  if (b->have_bc[other] && !b->kinds_per_reach[other]) {
-    std::vector<int32_t> same(B, b->bc_kind[other]);
-    HIP_TRY(hipMemcpy(b->reach_kinds + (size_t)other * B, same.data(), B * 4, hipMemcpyHostToDevice));
-  }
-  b->bc_kind[side] = kinds[0]; b->bc_stride[side] = 1; b->kinds_per_reach[side] = true;
-  b->any_storage[side] = false; b->some_host_rows[side] = false;
-  for (size_t r = 0; r < B; ++r) {
-    b->any_storage[side] = b->any_storage[side] || fs::bc_is_storage(kinds[r]);
-    b->some_host_rows[side] = b->some_host_rows[side] || kinds[r] == FS_BC_HOST_ROW;
-  }
-  // one host-evaluated reach makes the batch one that advances with fs_batch_iterate on the kernels of boundary class -1, one general
-  // reservoir makes it one for those kernels too: the side's representative kind (what the dispatch and fs_batch_step look at) says so
-  for (size_t r = 0; r < B; ++r) if (kinds[r] == FS_BC_STORAGE_CURVE) b->bc_kind[side] = FS_BC_STORAGE_CURVE;
-  if (b->some_host_rows[side]) b->bc_kind[side] = FS_BC_HOST_ROW;
+  if (b->have_bc[other] && !b->kinds_per_reach[other] && fill_side_kinds(b, other, b->bc_kind[other])) return -1;
+  b->bc_kind[side] = sk.kind; b->bc_stride[side] = 1; b->kinds_per_reach[side] = true;
+  b->any_storage[side] = sk.any_storage; b->some_host_rows[side] = sk.some_host_rows;
   b->have_bc[side] = true;
   return 0;
 }
@@ -883,62 +798,19 @@ int fs_batch_set_bc_per_reach_wide(fs_batch *b, int32_t side, const int32_t *kin
 int fs_batch_set_bc(fs_batch *b, int32_t side, int32_t kind, const double *params, int32_t n_params,
                     int32_t per_reach, const double *target) {
   if (!b) return fail("null handle");
-  if (side != FS_UPSTREAM && side != FS_DOWNSTREAM) return fail("fs_batch_set_bc: side must be FS_UPSTREAM or FS_DOWNSTREAM");
+  if (check_side("fs_batch_set_bc", side)) return -1;
   FS_ON_DEVICE(b);
-  static const int need[] = {0, 1, 1, 2, 4, 5, 10, 5};
-  if (kind < 0 || kind > FS_BC_HOST_ROW) return fail("Invalid boundary condition.");        // boundary.py:33
-  if (kind == FS_BC_HOST_ROW) {
-    if (b->d.section_mode != FS_SEC_TABLE && b->d.section_mode != FS_SEC_IRREGULAR)
-      return fail("fs_batch_set_bc: FS_BC_HOST_ROW needs section mode FS_SEC_TABLE or FS_SEC_IRREGULAR");
-    if (n_params != 3 || !per_reach) return fail("fs_batch_set_bc: FS_BC_HOST_ROW takes params[3][B] (per_reach = 1) or NULL");
-    const size_t B = b->d.n_reaches;
-    if (b->bc_params[side]) { (void)hipFree(b->bc_params[side]); b->bc_params[side] = nullptr; }
-    if (b->bc_target[side]) { (void)hipFree(b->bc_target[side]); b->bc_target[side] = nullptr; }
-    if (params) { if (upload(b, &b->bc_params[side], params, 3 * B)) return -1; }
-    else {
-      HIP_TRY(hipMalloc(&b->bc_params[side], 3 * B * b->esz));
-      HIP_TRY(hipMemsetAsync(b->bc_params[side], 0, 3 * B * b->esz, b->stream));
-    }
-    b->bc_kind[side] = kind; b->bc_stride[side] = 1; b->have_bc[side] = true;
-    b->kinds_per_reach[side] = false; b->any_storage[side] = false; b->some_host_rows[side] = false;
-    if (b->reach_kinds) {          // the other side has per-reach kinds: this side's one kind goes into every slot
-      std::vector<int32_t> same(B, kind);
-      HIP_TRY(hipMemcpy(b->reach_kinds + (size_t)side * B, same.data(), B * 4, hipMemcpyHostToDevice));
-    }
-    return 0;
-  }
-  if (kind == FS_BC_STORAGE_CURVE) {
-    // shared by the batch (params[n_params]) or - round 4 - one reservoir per reach (per_reach = 1: params[n_params][B], every reach its own
-    // scalars, area curve and outflow rating curve; the curves of a batch have the same number of points)
-    if (!params || n_params < FS_SC_NFIXED) return fail("Insufficient arguments for boundary condition.");
-    const size_t Bn = per_reach ? (size_t)b->d.n_reaches : 1;
-    auto at = [&](int i, size_t r) { return per_reach ? params[(size_t)i * Bn + r] : params[i]; };
-    for (size_t r = 0; r < Bn; ++r) {
-      const int nc = (int)at(FS_SC_N_CURVE, r);
-      if (nc < 0 || nc == 1 || n_params != FS_SC_NFIXED + 2 * nc)
-        return fail("fs_batch_set_bc: FS_BC_STORAGE_CURVE needs FS_SC_NFIXED + 2*n_curve parameters (n_curve 0 or >= 2; per reach: the same n_curve for all)");
-      for (int j = 0; j + 1 < nc; ++j)
-        if (!(at(FS_SC_NFIXED + j + 1, r) > at(FS_SC_NFIXED + j, r)))
-          return fail("fs_batch_set_bc: area-curve stages must be increasing");
-      if (nc == 0 && !(at(FS_SC_SURFACE_AREA, r) > 0)) return fail("Insufficient arguments for boundary condition.");
-    }
-  } else if (n_params != need[kind]) return fail("Insufficient arguments for boundary condition.");      // boundary.py:83
-  if (n_params > 0 && !params) return fail("Insufficient arguments for boundary condition.");
-  if ((kind == FS_BC_FLOW_HYDROGRAPH || kind == FS_BC_STAGE_HYDROGRAPH) && !target)
-    return fail("Insufficient arguments for boundary condition.");                                // boundary.py:87
-  if (fs::bc_is_storage(kind) && side != FS_DOWNSTREAM) return fail("fs_batch_set_bc: the storage boundary is downstream only");
   const size_t B = b->d.n_reaches;
-  if (b->bc_params[side]) { (void)hipFree(b->bc_params[side]); b->bc_params[side] = nullptr; }
-  if (b->bc_target[side]) { (void)hipFree(b->bc_target[side]); b->bc_target[side] = nullptr; }
-  if (n_params > 0 && upload(b, &b->bc_params[side], params, per_reach ? n_params * B : (size_t)n_params)) return -1;
-  if (target && upload(b, &b->bc_target[side], target, (size_t)b->d.max_levels * B)) return -1;
-  b->bc_kind[side] = kind; b->bc_stride[side] = per_reach ? 1 : 0;
+  const bool tables = b->d.section_mode == FS_SEC_TABLE || b->d.section_mode == FS_SEC_IRREGULAR;
+  if (const char *err = fs::check_bc(side, kind, params, n_params, per_reach, target != nullptr, B, tables)) return fail(err);
+  if (kind == FS_BC_HOST_ROW) {      // params[3][B], or NULL: zeros until fs_batch_set_host_rows
+    if (replace_bc_buffers(b, side, params, 3 * B, nullptr)) return -1;
+  } else if (replace_bc_buffers(b, side, params, per_reach ? n_params * B : (size_t)n_params, target)) return -1;
+  b->bc_kind[side] = kind; b->bc_stride[side] = (kind == FS_BC_HOST_ROW || per_reach) ? 1 : 0;
   b->have_bc[side] = true;
   b->kinds_per_reach[side] = false; b->any_storage[side] = fs::bc_is_storage(kind); b->some_host_rows[side] = false;
-  if (b->reach_kinds) {          // the other side has per-reach kinds: this side's one kind goes into every slot
-    std::vector<int32_t> same(B, kind);
-    HIP_TRY(hipMemcpy(b->reach_kinds + (size_t)side * B, same.data(), B * 4, hipMemcpyHostToDevice));
-  }
+  // the other side has per-reach kinds: this side's one kind goes into every slot
+  if (b->reach_kinds && fill_side_kinds(b, side, kind)) return -1;
   return 0;
 }
 
@@ -947,12 +819,12 @@ int fs_batch_set_state(fs_batch *b, const double *h, const double *Q) {
   FS_ON_DEVICE(b);
   const size_t B = b->d.n_reaches, N = b->d.n_nodes;
   // each array crosses the bus once; the Newton start vector and level 0 of the history are device-to-device copies
-  if (upload(b, &b->hk, h, B * N) || upload(b, &b->Qk, Q, B * N)) return -1;
-  HIP_TRY(hipMemcpyAsync(b->hg, b->hk, B * N * b->esz, hipMemcpyDeviceToDevice, b->stream));
-  HIP_TRY(hipMemcpyAsync(b->Qg, b->Qk, B * N * b->esz, hipMemcpyDeviceToDevice, b->stream));
+  if (upload(b, b->hk, h, B * N) || upload(b, b->Qk, Q, B * N)) return -1;
+  HIP_TRY(hipMemcpyAsync(b->hg.get(), b->hk.get(), B * N * b->esz, hipMemcpyDeviceToDevice, b->stream));
+  HIP_TRY(hipMemcpyAsync(b->Qg.get(), b->Qk.get(), B * N * b->esz, hipMemcpyDeviceToDevice, b->stream));
   if (b->hist_h) {   // level 0 of the history = initial conditions (solver.py:61-63)
-    HIP_TRY(hipMemcpyAsync(b->hist_h, b->hk, B * N * b->esz, hipMemcpyDeviceToDevice, b->stream));
-    HIP_TRY(hipMemcpyAsync(b->hist_Q, b->Qk, B * N * b->esz, hipMemcpyDeviceToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(b->hist_h.get(), b->hk.get(), B * N * b->esz, hipMemcpyDeviceToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(b->hist_Q.get(), b->Qk.get(), B * N * b->esz, hipMemcpyDeviceToDevice, b->stream));
   }
   std::vector<double> row(4 * B);
   for (size_t r = 0; r < B; ++r) {
@@ -960,50 +832,30 @@ int fs_batch_set_state(fs_batch *b, const double *h, const double *Q) {
     row[0 * B + r] = h[r * N]; row[1 * B + r] = Q[r * N];
     row[2 * B + r] = h[r * N + last]; row[3 * B + r] = Q[r * N + last];
   }
-  void *p = b->hydro;
-  if (upload(b, &p, row.data(), 4 * B)) return -1;
-  HIP_TRY(hipMemsetAsync(b->status, 0, B * 4, b->stream));
-  HIP_TRY(hipMemsetAsync(b->iters, 0, (size_t)b->d.max_levels * B * 4, b->stream));
-  HIP_TRY(hipMemsetAsync(b->Yprev, 0, B * b->esz, b->stream));
-  if (b->trace) HIP_TRY(hipMemsetAsync(b->trace, 0, (size_t)b->d.max_levels * FS_TRACE_CAP * B * b->esz, b->stream));
-  HIP_TRY(hipMemsetAsync(b->it_done, 0, B * 4, b->stream));
-  b->level = 0; b->iterating = false; b->restart_level = 0;
-  b->have_state = true;
-  return 0;
+  if (upload_to(b, b->hydro.get(), row.data(), 4 * B)) return -1;
+  return begin_at_level0(b);
 }
 
 int fs_batch_set_state_uniform(fs_batch *b, const double *h, const double *Q) {
   if (!b || !h || !Q) return fail("fs_batch_set_state_uniform: null argument");
   FS_ON_DEVICE(b);
   const size_t B = b->d.n_reaches, N = b->d.n_nodes;
-  void *dh = nullptr, *dQ = nullptr;
-  struct Tmp { void *&a, *&c; ~Tmp() { if (a) (void)hipFree(a); if (c) (void)hipFree(c); } } tmp_{dh, dQ};
-  if (upload(b, &dh, h, B) || upload(b, &dQ, Q, B)) return -1;
-  const dim3 grid((unsigned)((B * N + 255) / 256));
-  if (b->d.dtype == FS_F64)
-    hipLaunchKernelGGL((broadcast_state<double>), grid, dim3(256), 0, b->stream, (const double *)dh, (const double *)dQ,
-                       (double *)b->hk, (double *)b->Qk, (double *)b->hg, (double *)b->Qg, (double *)b->hist_h,
-                       (double *)b->hist_Q, (double *)b->hydro, B, N);
-  else
-    hipLaunchKernelGGL((broadcast_state<float>), grid, dim3(256), 0, b->stream, (const float *)dh, (const float *)dQ,
-                       (float *)b->hk, (float *)b->Qk, (float *)b->hg, (float *)b->Qg, (float *)b->hist_h,
-                       (float *)b->hist_Q, (float *)b->hydro, B, N);
+  fs::DeviceBuffer dh, dQ;
+  if (upload(b, dh, h, B) || upload(b, dQ, Q, B)) return -1;
+  with_real(b, [&](auto real) {
+    using R = decltype(real);
+    hipLaunchKernelGGL((broadcast_state<R>), grid_256(B * N), dim3(256), 0, b->stream, dh.get<const R>(), dQ.get<const R>(), b->hk.get<R>(),
+                       b->Qk.get<R>(), b->hg.get<R>(), b->Qg.get<R>(), b->hist_h.get<R>(), b->hist_Q.get<R>(), b->hydro.get<R>(), B, N);
+  });
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemsetAsync(b->status, 0, B * 4, b->stream));
-  HIP_TRY(hipMemsetAsync(b->iters, 0, (size_t)b->d.max_levels * B * 4, b->stream));
-  HIP_TRY(hipMemsetAsync(b->Yprev, 0, B * b->esz, b->stream));
-  HIP_TRY(hipMemsetAsync(b->it_done, 0, B * 4, b->stream));
-  if (b->trace) HIP_TRY(hipMemsetAsync(b->trace, 0, (size_t)b->d.max_levels * FS_TRACE_CAP * B * b->esz, b->stream));
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  b->level = 0; b->iterating = false; b->restart_level = 0;
-  b->have_state = true;
+  if (begin_at_level0(b)) return -1;
+  HIP_TRY(hipStreamSynchronize(b->stream));      // (dh and dQ go when this returns)
   return 0;
 }
 
 int fs_batch_step(fs_batch *b, int32_t n_steps) {
   if (!b) return fail("null handle");
-  if (!b->have_scheme || !b->have_geo || !b->have_state || !b->have_bc[0] || !b->have_bc[1])
-    return fail("fs_batch_step: scheme, geometry, both boundaries and the initial state must be set first");
+  if (check_ready(b, "fs_batch_step")) return -1;
   if (n_steps < 1) return fail("fs_batch_step: n_steps must be >= 1");
   if (b->level + n_steps >= b->d.max_levels) return fail("fs_batch_step: would run past max_levels");
   if (b->bc_kind[0] == FS_BC_HOST_ROW || b->bc_kind[1] == FS_BC_HOST_ROW)
@@ -1018,30 +870,28 @@ int fs_batch_step(fs_batch *b, int32_t n_steps) {
 
 int fs_batch_iterate(fs_batch *b, int32_t *n_open) {
   if (!b) return fail("null handle");
-  if (!b->have_scheme || !b->have_geo || !b->have_state || !b->have_bc[0] || !b->have_bc[1])
-    return fail("fs_batch_iterate: scheme, geometry, both boundaries and the initial state must be set first");
+  if (check_ready(b, "fs_batch_iterate")) return -1;
   if (b->level + 1 >= b->d.max_levels) return fail("fs_batch_iterate: would run past max_levels");
   if (b->d.section_mode != FS_SEC_TABLE && b->d.section_mode != FS_SEC_IRREGULAR)
     return fail("fs_batch_iterate: section mode FS_SEC_TABLE or FS_SEC_IRREGULAR required");
   FS_ON_DEVICE(b);
   if (launch_steps(b, 1, 1)) return -1;
   b->iterating = true;
-  // how many reaches are still open: counted on the device, four bytes come back (until round 3: two B-sized downloads per iteration)
+  // how many reaches are still open: counted on the device, four bytes come back
   const size_t B = b->d.n_reaches;
-  if (!b->open_dev) {
-    HIP_TRY(hipMalloc((void **)&b->open_dev, sizeof(int32_t)));
-    HIP_TRY(hipHostMalloc((void **)&b->open_pin, sizeof(int32_t), hipHostMallocDefault));
-  }
-  HIP_TRY(hipMemsetAsync(b->open_dev, 0, sizeof(int32_t), b->stream));
-  hipLaunchKernelGGL(count_open_reaches, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, b->stream, b->it_done, b->status, b->open_dev, B);
+  HIP_TRY(b->open_dev.ensure(sizeof(int32_t)));
+  HIP_TRY(b->open_pin.ensure(sizeof(int32_t)));
+  HIP_TRY(hipMemsetAsync(b->open_dev.get(), 0, sizeof(int32_t), b->stream));
+  hipLaunchKernelGGL(count_open_reaches, grid_256(B), dim3(256), 0, b->stream, b->it_done.get<const int32_t>(), b->status.get<const int32_t>(),
+                     b->open_dev.get<int32_t>(), B);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(b->open_pin, b->open_dev, sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(hipMemcpyAsync(b->open_pin.get(), b->open_dev.get(), sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
   HIP_TRY(hipStreamSynchronize(b->stream));
-  const int32_t open = *b->open_pin;
+  const int32_t open = *b->open_pin.get<int32_t>();
   if (open == 0) {      // every reach has accepted the level (or failed on it): next level, counters back to zero
     b->level += 1;
     b->iterating = false;
-    HIP_TRY(hipMemsetAsync(b->it_done, 0, B * 4, b->stream));
+    HIP_TRY(hipMemsetAsync(b->it_done.get(), 0, B * 4, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
   }
   if (n_open) *n_open = open;
@@ -1050,20 +900,18 @@ int fs_batch_iterate(fs_batch *b, int32_t *n_open) {
 
 int fs_batch_set_host_rows(fs_batch *b, int32_t side, const double *rows) {
   if (!b || !rows) return fail("fs_batch_set_host_rows: null argument");
-  if (side != FS_UPSTREAM && side != FS_DOWNSTREAM) return fail("fs_batch_set_host_rows: side must be FS_UPSTREAM or FS_DOWNSTREAM");
+  if (check_side("fs_batch_set_host_rows", side)) return -1;
   if (!b->have_bc[side] || b->bc_kind[side] != FS_BC_HOST_ROW) return fail("fs_batch_set_host_rows: this side is not an FS_BC_HOST_ROW boundary");
   FS_ON_DEVICE(b);
   const size_t B = b->d.n_reaches;
-  if (!b->kinds_per_reach[side]) return upload(b, &b->bc_params[side], rows, 3 * B);
+  if (!b->kinds_per_reach[side]) return upload(b, b->bc_params[side], rows, 3 * B);
   // per-reach kinds: entries of reaches whose boundary the device evaluates are ignored
-  if (upload(b, &b->rows_stage, rows, 3 * B)) return -1;
-  const dim3 grid((unsigned)((B + 255) / 256));
-  if (b->d.dtype == FS_F64)
-    hipLaunchKernelGGL((merge_host_rows<double>), grid, dim3(256), 0, b->stream, (double *)b->bc_params[side], (const double *)b->rows_stage,
-                       b->reach_kinds + (size_t)side * B, B);
-  else
-    hipLaunchKernelGGL((merge_host_rows<float>), grid, dim3(256), 0, b->stream, (float *)b->bc_params[side], (const float *)b->rows_stage,
-                       b->reach_kinds + (size_t)side * B, B);
+  if (upload(b, b->rows_stage, rows, 3 * B)) return -1;
+  with_real(b, [&](auto real) {
+    using R = decltype(real);
+    hipLaunchKernelGGL((merge_host_rows<R>), grid_256(B), dim3(256), 0, b->stream, b->bc_params[side].get<R>(), b->rows_stage.get<const R>(),
+                       b->reach_kinds.get<const int32_t>() + (size_t)side * B, B);
+  });
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -1072,24 +920,19 @@ int fs_batch_get_boundary_iterate(fs_batch *b, double *out) {
   if (!b || !out) return fail("fs_batch_get_boundary_iterate: null argument");
   if (!b->have_state) return fail("fs_batch_get_boundary_iterate: no state yet");
   FS_ON_DEVICE(b);
-  // one gather kernel and one transfer through a pinned buffer per call (it is made once per Newton iteration): until round 3 this
-  // was four strided hipMemcpy2D of one element per reach
+  // one gather kernel and one transfer through a pinned buffer per call (it is made once per Newton iteration)
   const size_t B = b->d.n_reaches, N = b->d.n_nodes;
-  if (!b->ends_dev) {
-    HIP_TRY(hipMalloc((void **)&b->ends_dev, 4 * B * sizeof(double)));
-    HIP_TRY(hipHostMalloc((void **)&b->ends_pin, 4 * B * sizeof(double), hipHostMallocDefault));
-  }
-  const dim3 grid((unsigned)((B + 255) / 256));
-  if (b->d.dtype == FS_F64)
-    hipLaunchKernelGGL((gather_boundary_iterate<double>), grid, dim3(256), 0, b->stream, (const double *)b->hg, (const double *)b->Qg,
-                       b->reach_nodes, b->ends_dev, B, N);
-  else
-    hipLaunchKernelGGL((gather_boundary_iterate<float>), grid, dim3(256), 0, b->stream, (const float *)b->hg, (const float *)b->Qg,
-                       b->reach_nodes, b->ends_dev, B, N);
+  HIP_TRY(b->ends_dev.ensure(4 * B * sizeof(double)));
+  HIP_TRY(b->ends_pin.ensure(4 * B * sizeof(double)));
+  with_real(b, [&](auto real) {
+    using R = decltype(real);
+    hipLaunchKernelGGL((gather_boundary_iterate<R>), grid_256(B), dim3(256), 0, b->stream, b->hg.get<const R>(), b->Qg.get<const R>(),
+                       b->reach_nodes.get<const int32_t>(), b->ends_dev.get<double>(), B, N);
+  });
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(b->ends_pin, b->ends_dev, 4 * B * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(hipMemcpyAsync(b->ends_pin.get(), b->ends_dev.get(), 4 * B * sizeof(double), hipMemcpyDeviceToHost, b->stream));
   HIP_TRY(hipStreamSynchronize(b->stream));
-  std::memcpy(out, b->ends_pin, 4 * B * sizeof(double));
+  std::memcpy(out, b->ends_pin.get(), 4 * B * sizeof(double));
   return 0;
 }
 
@@ -1103,13 +946,13 @@ int fs_batch_restart(fs_batch *b, int32_t level, const double *h, const double *
   if (fs_batch_set_state(b, h, Q)) return -1;
   FS_ON_DEVICE(b);
   const size_t B = b->d.n_reaches, N = b->d.n_nodes;
-  if (upload(b, &b->hg, h_guess, B * N) || upload(b, &b->Qg, Q_guess, B * N)) return -1;
-  if (storage_stage && upload(b, &b->Yprev, storage_stage, B)) return -1;
+  if (upload(b, b->hg, h_guess, B * N) || upload(b, b->Qg, Q_guess, B * N)) return -1;
+  if (storage_stage && upload(b, b->Yprev, storage_stage, B)) return -1;
   if (level > 0) {     // the boundary row of `level` (fs_batch_set_state wrote it to row 0) moves to its own row
-    HIP_TRY(hipMemcpyAsync((char *)b->hydro + (size_t)level * 4 * B * b->esz, b->hydro, 4 * B * b->esz, hipMemcpyDeviceToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(b->hydro.get<char>() + (size_t)level * 4 * B * b->esz, b->hydro.get(), 4 * B * b->esz, hipMemcpyDeviceToDevice, b->stream));
     if (b->hist_h) {
-      HIP_TRY(hipMemcpyAsync((char *)b->hist_h + (size_t)level * B * N * b->esz, b->hist_h, B * N * b->esz, hipMemcpyDeviceToDevice, b->stream));
-      HIP_TRY(hipMemcpyAsync((char *)b->hist_Q + (size_t)level * B * N * b->esz, b->hist_Q, B * N * b->esz, hipMemcpyDeviceToDevice, b->stream));
+      HIP_TRY(hipMemcpyAsync(b->hist_h.get<char>() + (size_t)level * B * N * b->esz, b->hist_h.get(), B * N * b->esz, hipMemcpyDeviceToDevice, b->stream));
+      HIP_TRY(hipMemcpyAsync(b->hist_Q.get<char>() + (size_t)level * B * N * b->esz, b->hist_Q.get(), B * N * b->esz, hipMemcpyDeviceToDevice, b->stream));
     }
     HIP_TRY(hipStreamSynchronize(b->stream));
   }
@@ -1144,7 +987,7 @@ int fs_batch_get_guess(fs_batch *b, double *h, double *Q) {
 int fs_batch_get_hydrographs(fs_batch *b, int32_t first, int32_t n, double *out) {
   if (!b || !out) return fail("fs_batch_get_hydrographs: null argument");
   FS_ON_DEVICE(b);
-  if (first < 0 || n < 1 || first + n > b->d.max_levels) return fail("fs_batch_get_hydrographs: level range out of bounds");
+  if (check_levels(b, "fs_batch_get_hydrographs", first, n)) return -1;
   const size_t B = b->d.n_reaches;
   return download(b, out, b->hydro, (size_t)first * 4 * B, (size_t)n * 4 * B);
 }
@@ -1152,10 +995,10 @@ int fs_batch_get_hydrographs(fs_batch *b, int32_t first, int32_t n, double *out)
 int fs_batch_get_iterations(fs_batch *b, int32_t first, int32_t n, int32_t *out) {
   if (!b || !out) return fail("fs_batch_get_iterations: null argument");
   FS_ON_DEVICE(b);
-  if (first < 0 || n < 1 || first + n > b->d.max_levels) return fail("fs_batch_get_iterations: level range out of bounds");
+  if (check_levels(b, "fs_batch_get_iterations", first, n)) return -1;
   const size_t B = b->d.n_reaches;
   HIP_TRY(hipStreamSynchronize(b->stream));
-  HIP_TRY(hipMemcpy(out, b->iters + (size_t)first * B, (size_t)n * B * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out, b->iters.get<int32_t>() + (size_t)first * B, (size_t)n * B * 4, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -1163,7 +1006,7 @@ int fs_batch_get_status(fs_batch *b, int32_t *out) {
   if (!b || !out) return fail("fs_batch_get_status: null argument");
   FS_ON_DEVICE(b);
   HIP_TRY(hipStreamSynchronize(b->stream));
-  HIP_TRY(hipMemcpy(out, b->status, (size_t)b->d.n_reaches * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out, b->status.get(), (size_t)b->d.n_reaches * 4, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -1171,7 +1014,7 @@ int fs_batch_get_history(fs_batch *b, int32_t first, int32_t n, double *h, doubl
   if (!b || !h || !Q) return fail("fs_batch_get_history: null argument");
   FS_ON_DEVICE(b);
   if (!b->hist_h) return fail("fs_batch_get_history: batch was created without FS_FLAG_HISTORY");
-  if (first < 0 || n < 1 || first + n > b->d.max_levels) return fail("fs_batch_get_history: level range out of bounds");
+  if (check_levels(b, "fs_batch_get_history", first, n)) return -1;
   if (b->restart_level > 0 && first < b->restart_level)
     return fail("fs_batch_get_history: this batch was restarted at level " + std::to_string(b->restart_level) + "; the history before it was not restored");
   const size_t per = (size_t)b->d.n_reaches * b->d.n_nodes;
@@ -1188,7 +1031,7 @@ int fs_batch_get_residual_trace(fs_batch *b, int32_t first, int32_t n, double *o
   if (!b || !out) return fail("fs_batch_get_residual_trace: null argument");
   FS_ON_DEVICE(b);
   if (!b->trace) return fail("fs_batch_get_residual_trace: batch was created without FS_FLAG_TRACE");
-  if (first < 0 || n < 1 || first + n > b->d.max_levels) return fail("fs_batch_get_residual_trace: level range out of bounds");
+  if (check_levels(b, "fs_batch_get_residual_trace", first, n)) return -1;
   const size_t per = (size_t)FS_TRACE_CAP * b->d.n_reaches;
   return download(b, out, b->trace, first * per, n * per);
 }
@@ -1196,7 +1039,7 @@ int fs_batch_get_residual_trace(fs_batch *b, int32_t first, int32_t n, double *o
 int fs_batch_get_storage_stages(fs_batch *b, int32_t first, int32_t n, double *out) {
   if (!b || !out) return fail("fs_batch_get_storage_stages: null argument");
   FS_ON_DEVICE(b);
-  if (first < 0 || n < 1 || first + n > b->d.max_levels) return fail("fs_batch_get_storage_stages: level range out of bounds");
+  if (check_levels(b, "fs_batch_get_storage_stages", first, n)) return -1;
   const size_t B = b->d.n_reaches;
   return download(b, out, b->stage_hist, (size_t)first * B, (size_t)n * B);
 }
@@ -1204,7 +1047,7 @@ int fs_batch_get_storage_stages(fs_batch *b, int32_t first, int32_t n, double *o
 int fs_batch_derive_device(fs_batch *b, int32_t first, int32_t n, int32_t fields) {
   if (!b) return fail("null handle");
   if (!b->hist_h) return fail("fs_batch_derive: batch was created without FS_FLAG_HISTORY");
-  if (first < 0 || n < 1 || first + n > b->d.max_levels) return fail("fs_batch_derive: level range out of bounds");
+  if (check_levels(b, "fs_batch_derive", first, n)) return -1;
   if ((fields & FS_DERIVE_ALL) == 0) return fail("fs_batch_derive: no field requested");
   if (b->restart_level > 0 && first < b->restart_level)
     return fail("fs_batch_derive: this batch was restarted at level " + std::to_string(b->restart_level) +
@@ -1215,34 +1058,21 @@ int fs_batch_derive_device(fs_batch *b, int32_t first, int32_t n, int32_t fields
   void *dev[8] = {nullptr};
   for (int f = 0; f < 8; ++f) {
     if (!(fields & (1 << f))) continue;
-    const size_t need = f == 7 ? BN : BN * n;
-    if (b->derived_cap[f] < need) {          // grown, never shrunk: a later call of the same size allocates nothing
-      if (b->derived[f]) { (void)hipFree(b->derived[f]); b->derived[f] = nullptr; b->derived_cap[f] = 0; }
-      HIP_TRY(hipMalloc(&b->derived[f], need * b->esz));
-      b->derived_cap[f] = need;
-    }
-    dev[f] = b->derived[f];
+    HIP_TRY(b->derived[f].reserve((f == 7 ? BN : BN * n) * b->esz));
+    dev[f] = b->derived[f].get();
   }
   const size_t per_thread = 16 / b->esz;           // one 16-byte access per thread, level and field
-  const dim3 grid((unsigned)(((BN + per_thread - 1) / per_thread + 255) / 256));
   HIP_TRY(hipEventRecord(b->ev0, b->stream));      // fs_batch_last_step_ms() then reports this kernel
-  if (b->d.dtype == FS_F64) {
-    fs::DeriveArgs<double> a{b->d.n_reaches, b->d.n_nodes, first, n, b->d.section_mode, (const double *)b->hist_h,
-                             (const double *)b->hist_Q, (const double *)b->geo_uniform, (const double *)b->geo_table,
-                             (const double *)b->poly_x, (const double *)b->poly_z, b->poly_n,
-                             (int64_t)b->geo_reach_stride, (int64_t)b->poly_reach_stride,
-                             (double *)dev[0], (double *)dev[1], (double *)dev[2], (double *)dev[3], (double *)dev[4],
-                             (double *)dev[5], (double *)dev[6], (double *)dev[7], b->reach_nodes};
-    hipLaunchKernelGGL((fs::derive_fields_kernel<double, 2>), grid, dim3(256), 0, b->stream, a);
-  } else {
-    fs::DeriveArgs<float> a{b->d.n_reaches, b->d.n_nodes, first, n, b->d.section_mode, (const float *)b->hist_h,
-                            (const float *)b->hist_Q, (const float *)b->geo_uniform, (const float *)b->geo_table,
-                            (const float *)b->poly_x, (const float *)b->poly_z, b->poly_n,
-                            (int64_t)b->geo_reach_stride, (int64_t)b->poly_reach_stride,
-                            (float *)dev[0], (float *)dev[1], (float *)dev[2], (float *)dev[3], (float *)dev[4],
-                            (float *)dev[5], (float *)dev[6], (float *)dev[7], b->reach_nodes};
-    hipLaunchKernelGGL((fs::derive_fields_kernel<float, 4>), grid, dim3(256), 0, b->stream, a);
-  }
+  with_real(b, [&](auto real) {
+    using R = decltype(real);
+    fs::DeriveArgs<R> a{b->d.n_reaches, b->d.n_nodes, first, n, b->d.section_mode, b->hist_h.get<const R>(), b->hist_Q.get<const R>(),
+                        b->geo_uniform.get<const R>(), b->geo_table.get<const R>(), b->poly_x.get<const R>(), b->poly_z.get<const R>(),
+                        b->poly_n.get<const int32_t>(), (int64_t)b->geo_reach_stride, (int64_t)b->poly_reach_stride,
+                        (R *)dev[0], (R *)dev[1], (R *)dev[2], (R *)dev[3], (R *)dev[4], (R *)dev[5], (R *)dev[6], (R *)dev[7],
+                        b->reach_nodes.get<const int32_t>()};
+    hipLaunchKernelGGL((fs::derive_fields_kernel<R, (int)(16 / sizeof(R))>), grid_256((BN + per_thread - 1) / per_thread), dim3(256), 0,
+                       b->stream, a);
+  });
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(b->ev1, b->stream));
   b->timed = true; b->launches = 1;
@@ -1250,7 +1080,7 @@ int fs_batch_derive_device(fs_batch *b, int32_t first, int32_t n, int32_t fields
 }
 
 void *fs_batch_derived_device_ptr(fs_batch *b, int32_t field_index) {
-  return (b && field_index >= 0 && field_index < 8) ? b->derived[field_index] : nullptr;
+  return (b && field_index >= 0 && field_index < 8) ? b->derived[field_index].get() : nullptr;
 }
 
 int fs_batch_derive(fs_batch *b, int32_t first, int32_t n, double *level, double *area, double *top_width,
@@ -1267,7 +1097,7 @@ int fs_batch_derive(fs_batch *b, int32_t first, int32_t n, double *level, double
   return 0;
 }
 
-void *fs_batch_hydrograph_device_ptr(fs_batch *b) { return b ? b->hydro : nullptr; }
+void *fs_batch_hydrograph_device_ptr(fs_batch *b) { return b ? b->hydro.get() : nullptr; }
 void *fs_batch_stream(fs_batch *b) { return b ? (void *)b->stream : nullptr; }
 
 double fs_batch_last_step_ms(fs_batch *b) {
@@ -1285,7 +1115,7 @@ int32_t fs_batch_last_launch_count(fs_batch *b) { return b ? b->launches : 0; }
 int fs_debug_stamps(fs_batch *b, unsigned long long *out) {
   if (!b || !out || !b->dbg) return fail("fs_debug_stamps: not available");
   HIP_TRY(hipStreamSynchronize(b->stream));
-  HIP_TRY(hipMemcpy(out, b->dbg, (size_t)b->d.n_reaches * 16 * 12 * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out, b->dbg.get(), (size_t)b->d.n_reaches * 16 * 12 * 8, hipMemcpyDeviceToHost));
   return 0;
 }
 #endif

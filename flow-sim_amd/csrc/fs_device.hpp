@@ -12,6 +12,7 @@
 #include <stdint.h>
 #include "../../include/flowsim_abi.h"
 #include "fs_dispatch.hpp"      // bc_is_light: the dispatch asks it too
+#include "fs_host_pack.hpp"     // FS_GEOX_*, bc_is_storage: the host side of the ABI asks them too
 
 namespace fs {
 
@@ -227,9 +228,7 @@ template <typename R> struct NodeTerms {
   R rT;   // 1 / T: the continuity row's dh coefficient is T/(2dt) on both nodes (preissmann.py:431-447), its reciprocal scales
 };        // the node's momentum entries into the characteristic-like unknowns of the solve (below)
 
-// rows the library appends to the caller's FS_GEO_* table on upload (fs_abi.hip: extend_table): geometry-only quantities
-enum { FS_GEOX_SM = FS_GEO_NPARAM, FS_GEOX_SFP, FS_GEOX_TB, FS_GEOX_AM, FS_GEOX_PM, FS_GEOX_RNM, FS_GEOX_KM15, FS_GEOX_KL15,
-       FS_GEOX_KR15, FS_GEOX_NROWS };
+// (the rows FS_GEOX_* that the library appends to the caller's FS_GEO_* table on upload: fs_host_pack.hpp, extend_table)
 
 // trapezoidal section parameters at one node (cross_section.py:569-613) ...
 template <typename R> struct SecParams {
@@ -683,8 +682,6 @@ template <typename R> __device__ __forceinline__ EntryProps<R> entry_props(const
   e.A = g.A; e.Rh = g.Rh; e.neq = g.neq; e.dRdA = g.dRdA; e.dAdh = g.T;
   return e;
 }
-
-__host__ __device__ constexpr bool bc_is_storage(int kind) { return kind == FS_BC_STORAGE || kind == FS_BC_STORAGE_CURVE; }
 
 // sec: section of the boundary node; Qold: flow[k-1] at that node; Yprev: storage stage of level
 // k-1; level: k.  Ynew returns the storage stage implied by this evaluation (boundary.py:126-131).

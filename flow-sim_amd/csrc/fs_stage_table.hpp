@@ -1,6 +1,6 @@
 // fs_stage_table.hpp - the stage table of a polyline node: its layout (FS_PT_*, poly_table_bp / poly_table_stride, read by
 // fs_poly.hpp on the device) and its construction on the host (build_stage_table, pack_stage_table_node, called by
-// fs_abi.hip: pack_polylines).  Plain C++ apart from the __host__ __device__ marks under hipcc: tests/stage_table/ builds the
+// fs_host_pack.hpp: pack_polylines).  Plain C++ apart from the __host__ __device__ marks under hipcc: tests/stage_table/ builds the
 // builder with the system compiler under AddressSanitizer / UBSan and checks every coefficient against the CPU oracle.
 #pragma once
 #include <algorithm>

@@ -7,7 +7,9 @@ instead):
     fixture of the trapezoid family + fresh 700-node inputs);
   * the host side of the C ABI (flow-sim_amd/csrc/fs_abi.hip: descriptor validation, kernel dispatch table, error texts,
     NULL handles) - a host-only clang build of the same source with -fsanitize=address,undefined - driven by two plain-C
-    programs: tests/c_abi/host_paths.c and tests/c_abi/smoke.c (which on a box without a GPU ends in "no HIP device")."""
+    programs: tests/c_abi/host_paths.c and tests/c_abi/smoke.c (which on a box without a GPU ends in "no HIP device").  What
+    that side computes without a device (fs_host_pack.hpp: pack_polylines, extend_table, the boundary checks) has its own
+    sanitized build: tests/test_host_pack.py."""
 import os
 import shutil
 import subprocess

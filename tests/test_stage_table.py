@@ -2,7 +2,7 @@
 checked coefficient by coefficient against the CPU oracle (oracle/irregular_oracle.py) - until now the tables were only checked
 through the end-to-end GPU comparison.
 
-tests/stage_table/stage_table_driver.cpp runs the very builder and node-minor packing that fs_abi.hip (pack_polylines) runs;
+tests/stage_table/stage_table_driver.cpp runs the very builder and node-minor packing that fs_host_pack.hpp (pack_polylines) runs;
 the sections are those of tests/poly_edges.py (vertices exactly on a breakpoint, flat berms, vertical walls, elevations closer
 than 1e-6, strip limits on and between stations, up to 245 stations) plus the three reference-generated irr_* fixtures.  For
 every node, every interval and three stages inside it: A, P, T and each roughness strip's (A, P) against properties() of the
