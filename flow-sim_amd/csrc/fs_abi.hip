@@ -223,7 +223,7 @@ struct fs_batch : Timeline {
   fs::DeviceBuffer kc_scratch;          // long reaches: level constants [B][4][passes * 64 W M]
   int passes = 0;
   fs::DeviceBuffer team_mail;           // reaches stepped by teams of workgroups: mailboxes [B][2][G W + 1][kTeamWords]
-  fs::DeviceBuffer team_sync;           // uint64 [1 + B] ticket counter + per-reach post counters, zeroed before every launch
+  fs::DeviceBuffer team_sync;           // uint64 [1]: the ticket counter, zeroed before every launch
   int team_size = 0;
   uint32_t team_epoch = 0;              // team launches made on this handle (the high half of the tagged mailbox's tags)
 };
@@ -412,12 +412,12 @@ int launch_steps(fs_batch *b, int n_steps, int iter_budget) {
     const size_t chunk = (size_t)64 * k->key.W * k->key.M;
     b->passes = (int)((b->d.n_nodes + chunk - 1) / chunk);
     // (uniform sections recompute their level constants, fs_long.hpp: no scratch)
-    const bool recompute = FS_LONG_RECOMPUTE && (b->d.section_mode == FS_SEC_RECT_UNIFORM || b->d.section_mode == FS_SEC_TRAP_UNIFORM);
+    const bool recompute = b->d.section_mode == FS_SEC_RECT_UNIFORM || b->d.section_mode == FS_SEC_TRAP_UNIFORM;
     const size_t need = recompute ? 0 : (size_t)b->d.n_reaches * 4 * b->passes * chunk;
     HIP_TRY(b->kc_scratch.reserve(need * b->esz));
   }
   b->team_size = 0;
-  if (k->key.team) {       // G workgroups per reach: their mailboxes and counters (the counters start every launch at zero)
+  if (k->key.team) {       // G workgroups per reach: their mailboxes and the ticket counter (which starts every launch at zero)
     const size_t chunk = (size_t)64 * k->key.W * k->key.M, B = b->d.n_reaches;
     b->team_size = (int)((b->d.n_nodes + chunk - 1) / chunk);
     // (16 bytes per word: the tagged form posts (value, tag) pairs; zeroed once - a tag is never 0, launches count from 1)
@@ -426,8 +426,8 @@ int launch_steps(fs_batch *b, int n_steps, int iter_budget) {
     HIP_TRY(b->team_mail.reserve(need * sizeof(double), &grew));
     if (grew) HIP_TRY(hipMemsetAsync(b->team_mail.get(), 0, need * sizeof(double), b->stream));
     ++b->team_epoch;
-    HIP_TRY(b->team_sync.ensure((1 + B) * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(b->team_sync.get(), 0, (1 + B) * sizeof(unsigned long long), b->stream));
+    HIP_TRY(b->team_sync.ensure(sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(b->team_sync.get(), 0, sizeof(unsigned long long), b->stream));
   }
   HIP_TRY(hipEventRecord(b->ev0, b->stream));
   with_real(b, [&](auto real) {

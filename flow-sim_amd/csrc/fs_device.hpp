@@ -21,12 +21,6 @@ constexpr double kG = 9.80665;  // scipy.constants.g (hydraulics.py:2)
 // ---------------------------------------------------------------------------------------------
 // scalar helpers
 // ---------------------------------------------------------------------------------------------
-#ifndef FS_RCP_F32_NR
-#define FS_RCP_F32_NR 0
-#endif
-#ifndef FS_RCP_NR
-#define FS_RCP_NR 1
-#endif
 // fused multiply-add in the working precision (__builtin_fma on floats is the double one: two conversions in, one out)
 __device__ __forceinline__ double fma_(double a, double b, double c) { return __builtin_fma(a, b, c); }
 __device__ __forceinline__ float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
@@ -35,45 +29,23 @@ __device__ __forceinline__ double frcp(double x) {
   // v_rcp_f64 seed (measured on gfx950: 2^-24.4 relative, tools/micro/rcp_prec.hip) + Newton steps:
   // one step leaves <= 2.3e-15 relative (~10 ulp), two steps are correctly rounded.  The kernel's
   // reciprocals feed Jacobian entries and friction terms whose effect on the accepted iterate is
-  // orders below the 1e-8 parity bar, so one step is the default.
-  double r = __builtin_amdgcn_rcp(x);
-#pragma unroll
-  for (int i = 0; i < FS_RCP_NR; ++i) {
-    const double e = __builtin_fma(-x, r, 1.0);
-    r = __builtin_fma(r, e, r);
-  }
-  return r;
+  // orders below the 1e-8 parity bar, so one step it is.
+  const double r = __builtin_amdgcn_rcp(x);
+  const double e = __builtin_fma(-x, r, 1.0);
+  return __builtin_fma(r, e, r);
 }
 __device__ __forceinline__ float frcp(float x) {
-#if FS_RCP_F32_NR
-  float r = __builtin_amdgcn_rcpf(x);
-  float e = __builtin_fmaf(-x, r, 1.0f);
-  return __builtin_fmaf(r, e, r);
-#else
   return __builtin_amdgcn_rcpf(x);          // v_rcp_f32 is accurate to 1 ulp: no Newton step
-#endif
 }
 
 // 1/sqrt(x): v_rsq_f64 seed r (single-precision accurate, e = 1 - x r^2 ~ 1e-7) and ONE third-order correction
 // r (1 - e)^(-1/2) = r (1 + e/2 + 3 e^2/8 + O(e^3)): the neglected term is below double rounding, five instructions where two Newton
-// steps (r += r/2 (1 - x r^2), FS_RSQ_THIRD=0) take eight
-#ifndef FS_RSQ_THIRD
-#define FS_RSQ_THIRD 1
-#endif
+// steps (r += r/2 (1 - x r^2)) take eight
 __device__ __forceinline__ double frsq(double x) {
-  double r = __builtin_amdgcn_rsq(x);
-#if FS_RSQ_THIRD
+  const double r = __builtin_amdgcn_rsq(x);
   const double e = __builtin_fma(-(x * r), r, 1.0);
   const double p = __builtin_fma(e, 0.375, 0.5);
   return __builtin_fma(r * e, p, r);
-#else
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const double e = __builtin_fma(-(x * r), r, 1.0);
-    r = __builtin_fma(r * 0.5, e, r);
-  }
-  return r;
-#endif
 }
 __device__ __forceinline__ float frsq(float x) {
   float r = __builtin_amdgcn_rsqf(x);
@@ -98,52 +70,14 @@ __device__ __forceinline__ float rcbrt_pos(float x) {
   return __builtin_fmaf(y * (1.0f / 3.0f), e, y);
 }
 
-// ---------------------------------------------------------------------------------------------
-// Explicit AGPR residency.  gfx950 has a unified 512-entry register file per lane but VALU
-// operands must be architectural VGPRs (256); the other half is reachable only through
-// v_accvgpr_read/write.  Values that are written once per Newton iteration and read once much
-// later (the per-node elimination records) are parked there on purpose with the "a" inline-asm
-// register class instead of leaving the choice to the spiller (which sends the overflow to
-// scratch memory once both halves are full).
-// ---------------------------------------------------------------------------------------------
-#ifndef FS_PARK
-#define FS_PARK 0   // measured: letting the register allocator place these beats forcing AGPRs
-#endif
-template <typename R> struct Parked;
-#if !FS_PARK
+// A value written once per Newton iteration and read once much later (the per-node elimination records).  The register
+// allocator places it: forcing these into AGPRs (v_accvgpr_write / read through the "a" inline-asm register class) was measured
+// and lost against its choice.
 template <typename R> struct Parked {
   R v;
   __device__ __forceinline__ void put(R x) { v = x; }
   __device__ __forceinline__ R get() const { return v; }
 };
-#else
-template <> struct Parked<double> {
-  uint32_t lo, hi;
-  __device__ __forceinline__ void put(double v) {
-    const uint32_t l = (uint32_t)__double2loint(v), h = (uint32_t)__double2hiint(v);
-    asm("v_accvgpr_write_b32 %0, %1" : "=a"(lo) : "v"(l));
-    asm("v_accvgpr_write_b32 %0, %1" : "=a"(hi) : "v"(h));
-  }
-  __device__ __forceinline__ double get() const {
-    uint32_t l, h;
-    asm("v_accvgpr_read_b32 %0, %1" : "=v"(l) : "a"(lo));
-    asm("v_accvgpr_read_b32 %0, %1" : "=v"(h) : "a"(hi));
-    return __hiloint2double((int)h, (int)l);
-  }
-};
-template <> struct Parked<float> {
-  uint32_t w;
-  __device__ __forceinline__ void put(float v) {
-    const uint32_t x = __float_as_uint(v);
-    asm("v_accvgpr_write_b32 %0, %1" : "=a"(w) : "v"(x));
-  }
-  __device__ __forceinline__ float get() const {
-    uint32_t x;
-    asm("v_accvgpr_read_b32 %0, %1" : "=v"(x) : "a"(w));
-    return __uint_as_float(x);
-  }
-};
-#endif
 
 // |x| as the operand modifier of the instruction that consumes it (a compare-and-select costs four instructions per use)
 __device__ __forceinline__ double fabs_(double x) { return __builtin_fabs(x); }
@@ -154,14 +88,9 @@ __device__ __forceinline__ double clamp01_(double x) { return __builtin_fmin(__b
 __device__ __forceinline__ float clamp01_(float x) { return __builtin_fminf(__builtin_fmaxf(x, 0.0f), 1.0f); }
 // x^b as exp(b log x) for x > 0 (|error| ~ b |log x| ulp: 1e-15 .. 1e-14 relative, against a parity bar of 1e-8): two
 // libm calls of ~50 instructions instead of pow()'s ~300 with its special cases, once per Newton iteration in the rating row
-#ifndef FS_POW_EXPLOG
-#define FS_POW_EXPLOG 1
-#endif
-__device__ __forceinline__ double pow_(double a, double b) { return (FS_POW_EXPLOG && a > 0.0) ? exp(b * log(a)) : pow(a, b); }
-// the same without the fallback (no branch): NaN for a < 0, as pow() gives for the non-integer exponents of a rating curve
-#ifndef FS_POW_SHORT
-#define FS_POW_SHORT 1   // pow_pos(double): log and exp written out below (~65 instructions) instead of the two libm calls (~150 in the rating row of every Newton iteration: a tenth of C5 fp64)
-#endif
+__device__ __forceinline__ double pow_(double a, double b) { return a > 0.0 ? exp(b * log(a)) : pow(a, b); }
+// the same without the fallback (no branch): NaN for a < 0, as pow() gives for the non-integer exponents of a rating curve.
+// pow_pos(double): log and exp written out below (~65 instructions) instead of the two libm calls (~150 in the rating row of every Newton iteration: a tenth of C5 fp64)
 // log(x), x > 0 finite: x = 2^e m with m in [sqrt(1/2), sqrt(2)), log m = 2 atanh(f), f = (m - 1) / (m + 1), |f| <= 0.1716: ten terms of the
 // odd series (f^21 / 21 < 2e-17 relative), the quotient corrected once, e ln 2 in two parts (the high one exact for |e| < 2^20).  Measured
 // against long double over x in 1e-4 .. 1e4: 3.2e-16 relative, 3.1e-16 within 2e-4 of 1 (tools/micro/pow_model.c).
@@ -200,12 +129,8 @@ __device__ __forceinline__ double exp_short(double y) {
 // x^b for the rating rows: 4.1e-15 relative over x in 1e-4 .. 1e4, b in 0.2 .. 5 - what exp(b * log(x)) of libm gives on the same grid (the rounding
 // of b log x dominates both); 0 for x = 0 and NaN for x < 0 as before
 __device__ __forceinline__ double pow_pos(double a, double b) {
-#if FS_POW_SHORT
   const double v = exp_short(b * log_pos(a));
   return a > 0.0 ? v : (a == 0.0 ? 0.0 : __builtin_nan(""));
-#else
-  return exp(b * log(a));
-#endif
 }
 __device__ __forceinline__ float pow_pos(float a, float b) { return __builtin_amdgcn_exp2f(b * __builtin_amdgcn_logf(a)); }
 // fp32 is the throughput mode (tolerance 1e-3, no parity bar): x^b as exp2(b log2 x) on the transcendental unit, ~1e-6 relative,
@@ -312,26 +237,10 @@ template <typename R> __device__ __forceinline__ R conv_(R A, R n, R Rh) { retur
 template <typename R> struct GeneralProps { R A, rA, P, Rh, T, rT, K, rK, neq, dRdA, dKdA, dKdA_K, y13; };
 
 // General trapezoid family (rectangle / simple / compound), straight from the reference including
-// the over-bank area inconsistency and the frozen-n_eq dK/dA.  Kept out of line: it is
-// pow()-heavy and only the boundary rows and the TABLE geometry mode use it.
-// general boundary rows (bc_eval) in line or out of line
-#ifndef FS_BC_INLINE
-#define FS_BC_INLINE 1   // (0, like FS_GENERAL_INLINE 0: experiment switches, to be built with -mllvm -enable-ipra=0, profiles/round3/polyline_calls.txt)
-                         // measured on the one-wave-per-reach kernels: C4 +8 %, C5 +4 % (fp64) / +15 % (fp32); a call inside the Newton loop spills the caller around it
-#endif
-#if FS_BC_INLINE
-#define FS_BC_ATTR __forceinline__
-#else
-#define FS_BC_ATTR __noinline__
-#endif
-#ifndef FS_GENERAL_INLINE
-#define FS_GENERAL_INLINE 1   // inline the general section evaluation into the fold (measured on C4: 4.5e6 -> 7.1e6)
-#endif
-#if FS_GENERAL_INLINE
-#define FS_GEN_ATTR __forceinline__
-#else
-#define FS_GEN_ATTR __noinline__
-#endif
+// the over-bank area inconsistency and the frozen-n_eq dK/dA.  Only the boundary rows and the TABLE geometry
+// mode use it.  Everything is in line, as the build requires (tools/check_isa.py): a call inside the Newton loop spills the
+// caller around it.  Measured: the general boundary rows (bc_eval) in line, on the one-wave-per-reach kernels, C4 +8 %,
+// C5 +4 % (fp64) / +15 % (fp32); the general section evaluation in line in the fold, C4 4.5e6 -> 7.1e6.
 // x^-1.5 for x > 0
 template <typename R> __device__ __forceinline__ R pm15_(R x) { const R r = frsq(x); return r * r * r; }
 
@@ -347,25 +256,13 @@ template <typename R> __device__ __forceinline__ void sec_derive(SecParams<R> &s
 
 // K_i^1.5 of one sub-section, K_i = A_i R_i^(2/3) / n_i (hydraulics.py:15-26):  A_i^2.5 / (P_i n_i^1.5) - one reciprocal
 // root and one reciprocal instead of an x^(2/3), a division by n and an x^1.5
-#ifndef FS_K15_ONE_RSQ
-#define FS_K15_ONE_RSQ 1   // A^2.5 / P = A^3 / sqrt(A P^2): one reciprocal root in place of a reciprocal root and a reciprocal
-#endif
+// (A^2.5 / P = A^3 / sqrt(A P^2): one reciprocal root in place of a reciprocal root and a reciprocal)
 template <typename R> __device__ __forceinline__ R k15_(R A, R P, R n15) {
-#if FS_K15_ONE_RSQ
   return (A > R(0) && P > R(0)) ? (A * A) * (A * frsq(A * (P * P))) * n15 : R(0);
-#else
-  return (A > R(0) && P > R(0)) ? A * A * fsqrt_pos(A) * frcp(P) * n15 : R(0);
-#endif
 }
 
-#ifndef FS_GEN_RCP3
-#define FS_GEN_RCP3 1
-#endif
-#ifndef FS_GEN_RK_ALG
-#define FS_GEN_RK_ALG 1
-#endif
 template <typename R>
-__device__ FS_GEN_ATTR GeneralProps<R> general_props(const SecParams<R> s, R h) {
+__device__ __forceinline__ GeneralProps<R> general_props(const SecParams<R> s, R h) {
   GeneralProps<R> g;
   const R d = fmax_(R(0), h);
   R T = fma_(R(2) * s.m, d, s.b);
@@ -385,16 +282,11 @@ __device__ FS_GEN_ATTR GeneralProps<R> general_props(const SecParams<R> s, R h) 
     T = (s.bl + s.Tb + s.br) + R(2) * s.mfp * dfp;
     dPdh = R(2) * s.sfp;
     const R A_m = fma_(s.Tb, dfp, s.Am);                            // :694 (column included)
-#if FS_GEN_RK_ALG
     const R S15 = k15_(A_l, P_l, s.kl15) + k15_(A_m, s.Pm, s.km15) + k15_(A_r, P_r, s.kr15);
     cK = S15 > R(0) ? rcbrt_pos(S15) : R(0);                       // K = S^(2/3) = S S^(-1/3), 1/K = (S^(-1/3))^2
     K = S15 * cK;                                                  // :741-754
-#else
-    K = p23_(k15_(A_l, P_l, s.kl15) + k15_(A_m, s.Pm, s.km15) + k15_(A_r, P_r, s.kr15));      // :741-754
-#endif
   }
   // divisions are reciprocal (v_rcp_f64 + one Newton step, 2e-15) times multiply: an IEEE fp64 divide is ~14 instructions
-#if FS_GEN_RCP3
   // 1/P, 1/T and 1/A from ONE reciprocal of their product: two v_rcp_f64 and their refinements less per node (C4 +1.8 %).  As before a dry node
   // (A = 0) gets rA = 0 and keeps 1/P, 1/T; a section without width at its bed (P = T = 0 when dry) gets zeros
   const bool wet = A > R(0);
@@ -402,41 +294,30 @@ __device__ FS_GEN_ATTR GeneralProps<R> general_props(const SecParams<R> s, R h) 
   const R PT = P * T;
   const R r3 = PT > R(0) ? frcp(PT * As) : R(0);
   const R rP = r3 * (T * As), rT = r3 * (P * As);
-#else
-  const R rP = P > R(0) ? frcp(P) : R(0), rT = T > R(0) ? frcp(T) : R(0);
-#endif
   g.Rh = A * rP;
   const R y13 = g.Rh > R(0) ? rcbrt_pos(g.Rh) : R(0);            // R^(-1/3)
   const R R23 = g.Rh * y13;
   // in bank K = A R^(2/3) / n_main; the reference's round trip (K^1.5)^(2/3) for a compound section in bank (:747-754)
   // is the identity, and its equivalent n = A R^(2/3) / K (:710-739) is n_main there
   if (!over) K = A * R23 * s.rnm;
-#if FS_GEN_RK_ALG && FS_GEN_RCP3
   // 1/K without a reciprocal: in bank n / (A R^(2/3)) = n (1/A) (R^(-1/3))^2, over bank the square of the sum's reciprocal cube root
   // (0 where K is 0: a dry node has 1/A = 0, an empty sum has cK = 0)
   const R rA_ = wet ? r3 * PT : R(0);
   g.rK = over ? cK * cK : s.nm * rA_ * (y13 * y13);
-#else
-  g.rK = K > R(0) ? frcp(K) : R(0);
-#endif
   g.neq = over ? A * R23 * g.rK : s.nm;
   g.dRdA = (P <= R(0) || T <= R(0)) ? R(0) : (P - A * (dPdh * rT)) * (rP * rP);   // :766-790
   // dK/dA = (R^(2/3) + (2/3) A R^(-1/3) dR/dA) / n_eq with the frozen n_eq = A R^(2/3) / K (:756-764), so
   // dK/dA / K = 1/A + (2/3) (P/A) dR/dA: neither K nor n_eq has to be divided by
-#if FS_GEN_RCP3
   g.rA = wet ? r3 * PT : R(0);
-#else
-  g.rA = A > R(0) ? frcp(A) : R(0);
-#endif
   g.dKdA_K = g.rA * fma_(R(2.0 / 3.0) * P, g.dRdA, R(1));
   g.dKdA = K * g.dKdA_K;
   g.A = A; g.P = P; g.T = T; g.rT = rT; g.K = K; g.y13 = y13;
   return g;
 }
 
-// out-of-line copy for the boundary rows (executed by two lanes per reach: keep it out of the hot code)
+// the boundary rows' evaluation (executed by two lanes per reach)
 template <typename R>
-__device__ FS_BC_ATTR GeneralProps<R> general_props_call(const SecParams<R> s, R h) { return general_props(s, h); }
+__device__ __forceinline__ GeneralProps<R> general_props_call(const SecParams<R> s, R h) { return general_props(s, h); }
 
 // Curvature slope Sc and its derivatives (cross_section.py:145-175 over hydraulics.py:94-153) added to
 // (Se, dSe/dA, dSe/dQ).  T = geometric top width, dAdh = what the section reports as dA/dh (the same
@@ -479,7 +360,7 @@ __device__ __forceinline__ void add_curvature(R curv, R A, R rA, R T, R rT, R dA
 }
 
 template <typename R>
-__device__ FS_GEN_ATTR NodeTerms<R> node_terms_general(const SecParams<R> s, R h, R Q) {
+__device__ __forceinline__ NodeTerms<R> node_terms_general(const SecParams<R> s, R h, R Q) {
   const GeneralProps<R> g = general_props(s, h);
   NodeTerms<R> t;
   const R iK2 = g.rK * g.rK;
@@ -693,7 +574,7 @@ template <typename R> __device__ __forceinline__ EntryProps<R> entry_props(const
 // 4 instructions and a full memory wait per parameter, in a row one lane evaluates while the others wait (C4: +7.7 %).
 template <typename R> using LdsParams = const __attribute__((address_space(3))) R *;
 template <bool WITH_SC = true, typename R>
-__device__ FS_BC_ATTR BCRow<R> bc_eval(const BCDesc<R> bc, int reach, int B, int level, const SecParams<R> sec,
+__device__ __forceinline__ BCRow<R> bc_eval(const BCDesc<R> bc, int reach, int B, int level, const SecParams<R> sec,
                                          R h, R Q, R Qold, R dt, R Yprev, R *Ynew, int *flag) {
   BCRow<R> r;
   auto p = [&](int i) { return ((LdsParams<R>)bc.params)[i]; };      // kinds <= FS_BC_STORAGE only (bc_storage_curve reads its own)
@@ -883,11 +764,7 @@ __device__ __forceinline__ void merge(const Seg<R> &X, const Seg<R> &Y, Seg<R> &
   const R ru2 = fma_(-Y.u1, X.rc, Y.ru);          // Y's rows on m_{b-1} instead of p_b
   const R rd2 = fma_(-Y.d1, X.rc, Y.rd);
   const R det = fma_(X.d3, Y.u1, X.d2);           // | d2 d3 ; -u1' 1 |
-#ifdef FS_FAKE_TREE_RCP      // timing experiment only (wrong numbers): the merge without its reciprocal - what a reciprocal-free tree could gain at most
-  const R r = det;
-#else
   const R r = frcp(det);
-#endif
   const R g2 = X.d3 * r;
   const R A1 = r * X.d1, A2 = g2 * Y.u3, A3 = fma_(r, X.rd, -(g2 * ru2));
   e.A1 = A1; e.A2 = A2; e.A3 = A3; e.rc = X.rc;
@@ -924,16 +801,10 @@ __device__ __forceinline__ void close_root(const Seg<R> &S, R aU, R bU, R rU, R 
 //   row_shr:n / row_shl:n  move within a row of 16 lanes; row_bcast15 / row_bcast31 hand lane 15 of
 //   each row to the next row / lane 31 to rows 2-3.  The tree only ever needs lane-d for a lane
 //   whose low bits are all ones, which these patterns cover for every stride (see fs_kernel.hpp).
-#ifndef FS_DPP
-#define FS_DPP 1
-#endif
-#ifndef FS_DPP_TIED
-#define FS_DPP_TIED 0   // 0: bound_ctrl moves without a tied destination (no register copy per move); 1: copy + in-place DPP
-#endif
 // lanes without a source read 0 (bound_ctrl): their value is unspecified for every caller below, and an
 // "old" operand that never shows through spares the register copy that keeps v alive next to its shifted copy
 template <int CTRL> __device__ __forceinline__ int dpp_mov(int v) {
-  return FS_DPP_TIED ? __builtin_amdgcn_update_dpp(v, v, CTRL, 0xF, 0xF, false) : __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true);
+  return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true);
 }
 template <int CTRL> __device__ __forceinline__ double dpp_mov(double v) {
   const int lo = dpp_mov<CTRL>(__double2loint(v)), hi = dpp_mov<CTRL>(__double2hiint(v));
@@ -942,27 +813,11 @@ template <int CTRL> __device__ __forceinline__ double dpp_mov(double v) {
 template <int CTRL> __device__ __forceinline__ float dpp_mov(float v) {
   return __int_as_float(dpp_mov<CTRL>(__float_as_int(v)));
 }
-// the same move into the lanes of the banks (groups of 4 lanes within a row of 16) in BANKS only; the others keep `old`
-template <int CTRL, int BANKS> __device__ __forceinline__ int dpp_mov_banks(int old, int v) {
-  return __builtin_amdgcn_update_dpp(old, v, CTRL, 0xF, BANKS, false);
-}
-template <int CTRL, int BANKS> __device__ __forceinline__ double dpp_mov_banks(double old, double v) {
-  const int lo = dpp_mov_banks<CTRL, BANKS>(__double2loint(old), __double2loint(v));
-  const int hi = dpp_mov_banks<CTRL, BANKS>(__double2hiint(old), __double2hiint(v));
-  return __hiloint2double(hi, lo);
-}
-template <int CTRL, int BANKS> __device__ __forceinline__ float dpp_mov_banks(float old, float v) {
-  return __int_as_float(dpp_mov_banks<CTRL, BANKS>(__float_as_int(old), __float_as_int(v)));
-}
 // value of lane - D for lanes whose low log2(2D) bits are all ones (others: unspecified)
 template <int D, typename R> __device__ __forceinline__ R tree_from_below(R v) {
-#if FS_DPP
   if (D < 16) return dpp_mov<0x110 + (D < 16 ? D : 1)>(v);      // row_shr:D
   if (D == 16) return dpp_mov<0x142>(v);                          // row_bcast15
   return dpp_mov<0x143>(v);                                       // row_bcast31
-#else
-  return __shfl_up(v, D, 64);
-#endif
 }
 template <int D, typename R> __device__ __forceinline__ Seg<R> seg_from_below(const Seg<R> &s) {
   Seg<R> o;
@@ -990,7 +845,6 @@ template <int CTRL, int ROWS, int BANKS> __device__ __forceinline__ float dpp_ze
 // sum over the 64 lanes, the same value in every lane (fixed order: prefix sums inside each row of 16,
 // then across rows; lane 63 holds the total and is broadcast through a scalar register)
 template <typename R> __device__ __forceinline__ R wave_sum(R v) {
-#if FS_DPP
   v += dpp_zero<0x111, 0xF, 0xF>(v);        // row_shr:1
   v += dpp_zero<0x112, 0xF, 0xF>(v);        // row_shr:2
   v += dpp_zero<0x114, 0xF, 0xF>(v);        // row_shr:4
@@ -1003,11 +857,6 @@ template <typename R> __device__ __forceinline__ R wave_sum(R v) {
   } else {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
   }
-#else
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-#endif
 }
 
 }  // namespace fs

@@ -27,128 +27,11 @@
 // 1 = RECT_UNIFORM with bc_is_light() kinds on both ends (closed-form rows, parameters in LDS), 2 + k = flow
 // hydrograph upstream and kind k downstream, known at compile time: the switch over the kinds folds away (rows the
 // reach never evaluates still cost registers and shape the code around them: flagship +1.5 %, C5 +2-3.5 %).
-// fs_abi.hip picks the most specific instantiation that matches the batch.
+// fs_dispatch.hpp picks the most specific instantiation that matches the batch.
 #pragma once
 #include <type_traits>
 #include "fs_device.hpp"
 #include "fs_poly.hpp"
-
-// build-time experiment switches (defaults = the configuration that measured fastest)
-#ifndef FS_CELL_FENCE
-#define FS_CELL_FENCE 1
-#endif
-#ifndef FS_WPE_W1
-#define FS_WPE_W1 1        // min waves/SIMD the one-wave-per-reach kernels are compiled for (2..4 measured: scratch spills, 0.25-0.8x)
-#endif
-#ifndef FS_SAVE_TERMS_MAXM_F64
-#define FS_SAVE_TERMS_MAXM_F64 2   // 4 and 8 cells per lane measured: trapezoid -13 % / -3 %, table +1 % (the LDS traffic of every fold outweighs one pass per level)
-#endif
-#ifndef FS_SAVE_TERMS
-#define FS_SAVE_TERMS 1
-#endif
-#ifndef FS_LONG_RECOMPUTE
-#define FS_LONG_RECOMPUTE 1   // multi-pass kernel, uniform sections: level constants recomputed per sweep instead of stored (fs_long.hpp)
-#endif
-#ifndef FS_LONG_PREFETCH
-#define FS_LONG_PREFETCH 0    // multi-pass kernel: the next pass's lines requested into L2 a pass ahead
-#endif
-#ifndef FS_LONG_COALESCE
-#define FS_LONG_COALESCE 1    // multi-pass kernel: state loads and stores with consecutive lanes on consecutive nodes, transposed through LDS
-#endif
-#ifndef FS_LONG_WPE
-#define FS_LONG_WPE 2
-#endif
-#ifndef FS_POLY_HINT_MAXM
-#define FS_POLY_HINT_MAXM 8
-#endif
-#ifndef FS_POLY_HINT
-#define FS_POLY_HINT 1     // polyline nodes start from the stage-table interval of their last evaluation (fs_poly.hpp)
-#endif
-#ifndef FS_SHARE_NODE
-#define FS_SHARE_NODE 1    // one-wave-per-reach kernels with general sections: a lane's last node is its right neighbour's first -
-#endif                     // take the neighbour's node terms (12 DPP moves) instead of evaluating the node a second time
-#ifndef FS_WPE_TRAP4
-#define FS_WPE_TRAP4 2          // trapezoid kernels with 4 cells per lane: 348 registers capped at 256 (+29 % at N = 200; the table kernel of that shape, 406 registers, loses 20 % when capped)
-#endif
-#ifndef FS_WPE_RECT8
-#define FS_WPE_RECT8 2          // rectangular fast-path kernels with <= 8 cells per lane: the ragged (8,1) one needs 310 registers, capped at 256 it runs two waves per SIMD (+21 % at N = 300)
-#endif
-#ifndef FS_WPE_LEAN_POLY
-#define FS_WPE_LEAN_POLY 2      // the same for the polyline kernels (332 registers capped at 256: +79 % on the polyline ensemble)
-#endif
-#ifndef FS_WPE_LEAN_SHORT
-#define FS_WPE_LEAN_SHORT 2     // fp64 table kernels of class 0 with <= 2 cells per lane: 314 registers capped at 256, two waves per SIMD (C4 +43 %)
-#endif
-#ifndef FS_WPE_PINNED_SHORT
-#define FS_WPE_PINNED_SHORT 2   // the same for kernels with the boundary kinds fixed at compile time
-#endif
-#ifndef FS_WPE_W1_F32_UNIFORM
-#define FS_WPE_W1_F32_UNIFORM 3   // fp32, uniform geometry, <= 8 cells per lane: 207 registers capped at 168, three waves per SIMD (C5 +14 %; four: -24 %)
-#endif
-#ifndef FS_WPE_W1_F32
-#define FS_WPE_W1_F32 2    // the same for fp32: two waves per SIMD fit (<= 256 registers) and hide the tree's latency (C5 fp32 +18 %)
-#endif
-#ifndef FS_LEVEL_FENCE
-#define FS_LEVEL_FENCE 0     // scheduling fence every k cells of the level-constant pass (0 = none)
-#endif
-#ifndef FS_PIN_SEG_F32
-#define FS_PIN_SEG_F32 1 // the same switch for the fp32 instantiations (C5 fp32: +5 % with the pin)
-#endif
-#ifndef FS_PIN_SEG
-#define FS_PIN_SEG 0     // pin the running rows at the end of each cell's scheduling region (round 1's block fold: +3 % at M >= 8; the
-#endif                   // scalar fold has 8 running numbers instead of 10 + a factor and schedules better without: +1.2 %)
-#ifndef FS_PHASE_FENCE
-#define FS_PHASE_FENCE 0   // bit 3: pin the back-substituted updates and fence them off from the acceptance block (round 1: +0.9 %; with the
-#endif                     // round-2 solve: fp64 flagship -2.3 %, C5 fp32 +4.5 %: see FS_PHASE_FENCE_F32); bits 0-1 (other phase boundaries): no gain
-#ifndef FS_PHASE_FENCE_F32
-#define FS_PHASE_FENCE_F32 8   // the same switch for the fp32 instantiations (three waves per SIMD at 168 registers: the fence keeps them there)
-#endif
-// table kernels with 2 rows per lane: the section parameters of the lane's three nodes are loaded once per launch instead of
-// at every node evaluation (46 vector loads per Newton iteration, their latency only half hidden by the second wave of the
-// SIMD): C4 +8.5 %, the general table kernel +11.6 %, still within the 256-register cap (20 spilled registers)
-#ifndef FS_REG_GEO
-#define FS_REG_GEO 1
-#endif
-#ifndef FS_FLAT_BC
-#define FS_FLAT_BC 1     // kernels compiled for a boundary pair evaluate the two rows in every lane, without a branch (below)
-#endif
-#ifndef FS_LAUNDER_BACK
-#define FS_LAUNDER_BACK 1
-#endif
-#ifndef FS_MONITOR_ALL
-#define FS_MONITOR_ALL 0   // 1: the conditioning monitor (below) also in the kernels compiled without diagnostics (DIAG = false); measured
-#endif                     // cost on the flagship: profiles/round3/README.md
-#ifndef FS_XLANES_MINW
-#define FS_XLANES_MINW 8 // waves per reach from which the cross-wave step runs as a second, small DPP tree (lane w of every wave carries
-#endif                   // the segment of wave w: 8 live numbers) instead of every thread folding all W segments in its own registers
-                         // (16 W live doubles).  Measured on 65 536 x 4 096 (profiles/round3/second_wave_per_simd.md): W = 8 (the (8, 8)
-                         // shape, two waves per SIMD) 7.9e6 -> 9.8e6 (the per-thread fold spills at 256 registers); W = 4 (the flagship
-                         // (16, 4) shape) 1.072e7 -> 1.058e7: with four segments the per-thread fold has the shorter dependent chain
-#ifndef FS_XWAVE_CONT
-#define FS_XWAVE_CONT 0      // 1: multi-wave kernels without the conditioning monitor (the no-diagnostics benchmark shapes) solve the W + 1
-#endif                       // unknowns of the cross-wave step (p of the first row, m of each wave's last row) as ONE small tridiagonal system by
-                             // forward and backward continuants - two independent chains of W + 1 fmas and one reciprocal - instead of folding the
-                             // W wave segments pairwise (two dependent merge levels, the root closure, two unfolding levels: four reciprocal
-                             // chains).  Built and measured in round 4 (profiles/round4/cross_wave_continuants.txt): the phase itself gets
-                             // shorter (1 330 -> 1 170 ticks of 15 500 in the stamped build), the shipped flagship does not get faster
-                             // (121.1 -> 122.2 ms; 121.0 with the top tree record no longer requested ahead of the barrier): off
-#ifndef FS_XWAVE_FENCE
-#define FS_XWAVE_FENCE 0     // scheduling fences around the cross-wave step (bit 0: before, bit 1: after)
-#endif
-#ifndef FS_TREE_REGS
-#define FS_TREE_REGS 0       // flagship shapes: the in-wave tree's records stay in registers (6 levels x 4 numbers, valid in the lane that survives
-#endif                       // its level) and come back on the way down by DPP broadcasts / readlanes instead of through LDS slots
-#ifndef FS_RC_EARLY
-#define FS_RC_EARLY 0        // flagship shapes: the continuity residuals the back-substitution needs are recomputed inside the cross-wave step
-#endif
-#ifndef FS_PREFETCH_DOWN
-#define FS_PREFETCH_DOWN 1   // multi-wave kernels without diagnostics: this many of the wave's top tree records (levels 5, 4, 3) are requested
-#endif                       // ahead of the cross-wave barrier instead of after the cross-wave step
-#ifndef FS_PRIME
-#define FS_PRIME 0      // 1: the level constants of a launch's first level come from the acceptance block of the loop (a priming pass
-#endif                   // through it) instead of from a second instance of that code ahead of the loop.  Not needed: with
-                         // -ffp-contract=on (Makefile) the two instances compile to the same arithmetic and chunked stepping equals
-                         // one launch bit for bit (tests/test_gpu_parity.py, test_gpu_dropin.py); flagship -5.5 %; kept as a switch
 
 namespace fs {
 
@@ -220,9 +103,9 @@ template <typename R> struct KernelArgs {
   int32_t passes;          // long reaches: passes of 64 W M rows a workgroup makes over its reach
   // ---- round 4: a reach longer than one lane grid as a TEAM of workgroups (kTeam below) ----
   int32_t team_size;             // G: workgroups per reach, member g owns rows [g C, (g + 1) C), C = 64 W M
-  R *team_mail;                  // [B][2][G W + 1][kTeamWords] mailboxes: one slot per (member, wave) + one for the upstream row, per iteration parity
-  unsigned long long *team_sync; // [1 + B]: [0] the ticket counter of the launch, [1 + reach] posts made for that reach so far (zeroed before every launch)
-  uint32_t team_epoch;           // tagged mailbox (FS_TEAM_TAGGED): the number of this launch among the handle's team launches (>= 1): the high half of every tag
+  R *team_mail;                  // [B][2][G W + 1][kTeamWords] mailboxes of 16-byte (value, tag) words: one slot per (member, wave) + one for the upstream row, per iteration parity
+  unsigned long long *team_sync; // [1]: the ticket counter of the launch (zeroed before every launch)
+  uint32_t team_epoch;           // the number of this launch among the handle's team launches (>= 1): the high half of every mailbox tag
 };
 constexpr int kTeamSlots = 64;   // (member, wave) segments of a team: the top tree is one wave wide
 // how long a member waits for its team before it gives the reach up (FS_TEAM_STALL): s_memtime ticks, 2.0e9 per second on gfx950 (tools/micro/rates.hip:
@@ -233,23 +116,14 @@ constexpr int kTeamWords = 12;   // per slot: the segment (8), the wave's residu
 
 template <typename R, int SEC> struct Geometry;
 
-// A team's mailbox (kTeam in the step kernel): every word is written and read with agent-scope atomic accesses - device-coherent
-// stores and loads (sc1), no cache involved that another XCD could not see - so that the exchange needs neither the write-back of
-// the L2 that an agent-scope release costs nor the invalidation of an acquire, both whole-cache operations and both on the critical
-// path of every Newton iteration of every team (measured: the exchange took 22 600 ticks of a 43 000-tick iteration with them).
-// Order is kept the plain way: the poster waits for its stores to be acknowledged (vmcnt) before the workgroup's barrier, thread 0
-// bumps the reach's counter after it; a reader polls the counter, passes a barrier, and only then issues its loads.
-template <typename T> __device__ __forceinline__ void team_put(T *p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void team_posted() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-// Tagged form (FS_TEAM_TAGGED): every mailbox word travels as ONE 16-byte device-coherent store of (value, tag), tag = (launch, exchange);
-// a reader polls the words themselves until every tag is the one it waits for.  No counter, no acknowledged stores, no barrier between
-// posting and counting: the exchange is one store flight and the reader's polls.  (A lane's aligned 16-byte access is one request.)
-#ifndef FS_TEAM_TAGGED
-#define FS_TEAM_TAGGED 1
-#endif
-#ifndef FS_TEAM_SLEEP
-#define FS_TEAM_SLEEP 1      // s_sleep between two polls of the mailbox (units of 64 cycles)
-#endif
+// A team's mailbox (kTeam in the step kernel): every word is written and read with device-coherent stores and loads (sc1), no
+// cache involved that another XCD could not see - so that the exchange needs neither the write-back of the L2 that an agent-scope
+// release costs nor the invalidation of an acquire, both whole-cache operations and both on the critical path of every Newton
+// iteration of every team (measured: the exchange took 22 600 ticks of a 43 000-tick iteration with them).
+// Every mailbox word travels as ONE 16-byte store of (value, tag), tag = (launch, exchange); a reader polls the words themselves
+// until every tag is the one it waits for.  No counter, no acknowledged stores, no barrier between posting and counting: the
+// exchange is one store flight and the reader's polls.  (A lane's aligned 16-byte access is one request.)
+constexpr int kTeamSleep = 1;        // s_sleep between two polls of the mailbox (units of 64 cycles)
 typedef unsigned int fs_u4 __attribute__((ext_vector_type(4)));
 constexpr int kTeamAuxSc1 = 16;      // cache-policy operand of the raw buffer intrinsics on gfx94x / gfx950: sc1 (device-coherent)
 __device__ __forceinline__ void team_put2(__amdgpu_buffer_rsrc_t r, unsigned off, unsigned long long bits, unsigned long long tag) {
@@ -387,9 +261,9 @@ template <typename R> struct Geometry<R, FS_SEC_TABLE> {
 };
 
 // TABLE plus polyline nodes (IrregularSection): per node either a row of the trapezoid table or a
-// polyline; both evaluations are inlined (FS_POLY_INLINE: out of line they spill the caller around every call).
+// polyline; both evaluations are inlined (out of line they spill the caller around every call).
 template <typename R>
-__device__ FS_POLY_ATTR NodeTerms<R> node_terms_general_call(const SecParams<R> s, R h, R Q) { return node_terms_general(s, h, Q); }
+__device__ __forceinline__ NodeTerms<R> node_terms_general_call(const SecParams<R> s, R h, R Q) { return node_terms_general(s, h, Q); }
 
 template <typename R> struct Geometry<R, FS_SEC_IRREGULAR> {
   static constexpr bool kConstT = false;
@@ -515,25 +389,25 @@ template <typename R> struct LocalElim { Parked<R> R1, R2, R3, qc; };
 // Minimum number of waves per SIMD a kernel is compiled for: caps its registers at 512 / n.  One wave per SIMD cannot
 // hide the latency of the in-wave tree, a second one is worth 20-80 % wherever the kernel fits 256 registers or nearly
 // does; forcing it on the larger kernels sends them to scratch (measured 0.25-0.8x).
-#ifndef FS_W1_LANES
-#define FS_W1_LANES 1      // one-wave fp64 kernels: the root segment and the upstream row meet through v_readlane instead of an LDS round trip (C5 fp64 +5.5 %, polyline ensemble +2.8 %, C4 +1.9 %; fp32: -0.5 %, left as it was)
-#endif
-#ifndef FS_TEAM_WPE
-#define FS_TEAM_WPE 2      // team kernels with <= 8 rows per lane: two workgroups per CU (one computes while the other waits for its team)
-#endif
 template <typename R, int SEC, int M, int W, int BCK, bool TEAM = false> constexpr int min_waves() {
-  if (TEAM && M <= 8 && sizeof(R) == 8) return FS_TEAM_WPE;
-#ifdef FS_WPE_TRAP42      // experiment: the (4, 2) trapezoid kernel (272 registers) capped at 256, two waves per SIMD
-  if (W == 2 && M == 4 && SEC == FS_SEC_TRAP_UNIFORM && sizeof(R) == 8) return FS_WPE_TRAP42;
-#endif
+  constexpr int kTeamWpe = 2;      // team kernels with <= 8 rows per lane: two workgroups per CU (one computes while the other waits for its team)
+  if (TEAM && M <= 8 && sizeof(R) == 8) return kTeamWpe;
   if (W > 1) return 1;          // multi-wave table kernels with 2 cells per lane at two waves per SIMD: no better than the 4- and 8-cell ones
-  if (sizeof(R) == 4) return (M <= 8 && (SEC == FS_SEC_RECT_UNIFORM || SEC == FS_SEC_TRAP_UNIFORM)) ? FS_WPE_W1_F32_UNIFORM : FS_WPE_W1_F32;
-  if (SEC == FS_SEC_RECT_UNIFORM && BCK >= 1 && M <= 8) return FS_WPE_RECT8;
-  if (BCK >= 2 && M <= 2) return FS_WPE_PINNED_SHORT;
-  if (BCK == 0 && M <= 2 && SEC == FS_SEC_TABLE) return FS_WPE_LEAN_SHORT;
-  if (BCK == 0 && M == 4 && SEC == FS_SEC_TRAP_UNIFORM) return FS_WPE_TRAP4;
-  if (BCK == 0 && M <= 2 && SEC == FS_SEC_IRREGULAR) return FS_WPE_LEAN_POLY;
-  return FS_WPE_W1;
+  constexpr int kWpeW1F32Uniform = 3; // fp32, uniform geometry, <= 8 cells per lane: 207 registers capped at 168, three waves per SIMD (C5 +14 %; four: -24 %)
+  constexpr int kWpeW1F32 = 2;        // the other fp32 kernels: two waves per SIMD fit (<= 256 registers) and hide the tree's latency (C5 fp32 +18 %)
+  if (sizeof(R) == 4) return (M <= 8 && (SEC == FS_SEC_RECT_UNIFORM || SEC == FS_SEC_TRAP_UNIFORM)) ? kWpeW1F32Uniform : kWpeW1F32;
+  constexpr int kWpeRect8 = 2;        // rectangular fast-path kernels with <= 8 cells per lane: the ragged (8,1) one needs 310 registers, capped at 256 it runs two waves per SIMD (+21 % at N = 300)
+  if (SEC == FS_SEC_RECT_UNIFORM && BCK >= 1 && M <= 8) return kWpeRect8;
+  constexpr int kWpePinnedShort = 2;  // kernels with the boundary kinds fixed at compile time and <= 2 cells per lane: as the table kernels below
+  if (BCK >= 2 && M <= 2) return kWpePinnedShort;
+  constexpr int kWpeLeanShort = 2;    // fp64 table kernels of class 0 with <= 2 cells per lane: 314 registers capped at 256, two waves per SIMD (C4 +43 %)
+  if (BCK == 0 && M <= 2 && SEC == FS_SEC_TABLE) return kWpeLeanShort;
+  constexpr int kWpeTrap4 = 2;        // trapezoid kernels with 4 cells per lane: 348 registers capped at 256 (+29 % at N = 200; the table kernel of that shape, 406 registers, loses 20 % when capped)
+  if (BCK == 0 && M == 4 && SEC == FS_SEC_TRAP_UNIFORM) return kWpeTrap4;
+  constexpr int kWpeLeanPoly = 2;     // the same for the polyline kernels (332 registers capped at 256: +79 % on the polyline ensemble)
+  if (BCK == 0 && M <= 2 && SEC == FS_SEC_IRREGULAR) return kWpeLeanPoly;
+  constexpr int kWpeW1 = 1;           // the other one-wave-per-reach kernels (2..4 measured: scratch spills, 0.25-0.8x)
+  return kWpeW1;
 }
 
 // Rows of the scalar system (fs_device.hpp): row k is the momentum row of cell k for k < N-1, the downstream boundary row
@@ -552,7 +426,7 @@ template <typename R, int SEC, int M, int W, int BCK, bool TEAM = false> constex
 // C = 64 W M rows of it on chip exactly as a short reach is held - unknowns in registers, level constants in LDS, HBM read once per
 // launch and written once - where the multi-pass kernel (fs_long.hpp) streams the Newton vector through memory twice per iteration.
 // What the W waves of one workgroup exchange through LDS (step 4) the G W waves of a team exchange through a mailbox in device
-// memory: every wave posts its segment, one release / acquire pair on a per-reach counter (agent scope) stands where the barrier
+// memory: every wave posts its segment as tagged words, polling for the tags of the exchange stands where the barrier
 // stood, wave 0 of every member reduces the G W segments with one more DPP tree (the multi-pass kernel's top tree: identity segments
 // pad the 64 lanes), closes the root with the upstream row and hands every wave its four numbers back through LDS.  All members
 // see the same numbers and take the same decisions (convergence, failure, monitor), so the time loop needs no other exchange.
@@ -572,9 +446,14 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
   // Short general-section kernels keep (A, Se, Q/A) of every node of the current fold in LDS: if the iterate is accepted they
   // are the node terms of level k, and the level constants of level k+1 come from them instead of from another pass over the
   // sections (1 of 6 section passes of the polyline ensemble, 1 of 11 of C4)
-  constexpr bool kRegGeo = FS_REG_GEO && SEC == FS_SEC_TABLE && W == 1 && M <= 2;
-  constexpr bool kFlatBC = FS_FLAT_BC && BCK >= 2 && sizeof(R) == 8 && SEC == FS_SEC_TRAP_UNIFORM;   // measured: C5 fp64 +1.5 %; flagship -1.5 %, C4 -7 %, polyline -1.3 %
-  constexpr bool kSaveTerms = FS_SAVE_TERMS && !Geometry<R, SEC>::kConstT && (M <= 2 || (sizeof(R) == 8 && M <= FS_SAVE_TERMS_MAXM_F64));
+  constexpr int kSaveTermsMaxMF64 = 2;       // 4 and 8 cells per lane measured: trapezoid -13 % / -3 %, table +1 % (the LDS traffic of every fold outweighs one pass per level)
+  constexpr bool kSaveTerms = !Geometry<R, SEC>::kConstT && (M <= 2 || (sizeof(R) == 8 && M <= kSaveTermsMaxMF64));
+  // table kernels with 2 rows per lane: the section parameters of the lane's three nodes are loaded once per launch instead of
+  // at every node evaluation (46 vector loads per Newton iteration, their latency only half hidden by the second wave of the
+  // SIMD): C4 +8.5 %, the general table kernel +11.6 %, still within the 256-register cap (20 spilled registers)
+  constexpr bool kRegGeo = SEC == FS_SEC_TABLE && W == 1 && M <= 2;
+  // kernels compiled for a boundary pair evaluate the two rows in every lane, without a branch (step 1 below)
+  constexpr bool kFlatBC = BCK >= 2 && sizeof(R) == 8 && SEC == FS_SEC_TRAP_UNIFORM;   // measured: C5 fp64 +1.5 %; flagship -1.5 %, C4 -7 %, polyline -1.3 %
   __shared__ Smem<R, M, W, kSaveTerms, kTeam> sm;
 
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -587,8 +466,7 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
   const int G = kTeam ? a.team_size : 1;
   const int reach = kTeam ? job / G : job, member = kTeam ? job - reach * G : 0;
   const int gt = member * T + t;                 // the lane's place in the reach's lane grid (t itself unless the reach is a team's)
-  constexpr bool kTagged = kTeam && FS_TEAM_TAGGED && sizeof(R) == 8;
-  // the reach's mailbox of one iteration parity as a raw buffer (tagged form: (G W + 1) slots of kTeamWords (value, tag) pairs)
+  // the reach's mailbox of one iteration parity as a raw buffer ((G W + 1) slots of kTeamWords (value, tag) pairs)
   auto mbox = [&](int par) __attribute__((always_inline)) {
     const size_t bytes = (size_t)(G * W + 1) * kTeamWords * 16;
     char *base = reinterpret_cast<char *>(a.team_mail) + ((size_t)reach * 2 + par) * bytes;
@@ -616,14 +494,15 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
 
   Geo geo;
   geo.init(a, reach, N);
-  // node terms of the lane's local node j (0..M); FS_REG_GEO: from section parameters loaded once per launch
+  // node terms of the lane's local node j (0..M); kRegGeo: from section parameters loaded once per launch
   SecParams<R> secs[kRegGeo ? M + 1 : 1];
   if constexpr (kRegGeo) {
 #pragma unroll
     for (int j = 0; j <= M; ++j) secs[j] = geo.section(min(s0 + j, N - 1));
   }
   // polyline nodes: the stage-table interval each of the lane's nodes was last evaluated in (Geometry::terms_hinted)
-  constexpr bool kHinted = SEC == FS_SEC_IRREGULAR && M <= FS_POLY_HINT_MAXM && FS_POLY_HINT;
+  constexpr int kPolyHintMaxM = 8;
+  constexpr bool kHinted = SEC == FS_SEC_IRREGULAR && M <= kPolyHintMaxM;
   int khint[kHinted ? M + 1 : 1];
   PolyBC<R> polybc[kHinted ? M + 1 : 1];      // (K, dK/dA, dA/dh) of the lane's nodes as last evaluated: the fused normal-depth row below
   if constexpr (kHinted) {
@@ -675,32 +554,31 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
   // clamped copy beyond the reach.  (Until round 3 lane 63 evaluated that node itself whenever the reach filled the wave - a
   // whole section evaluation per iteration, executed by 64 lanes for a result nobody read: a quarter of the polyline ensemble's
   // instructions.)
-  constexpr bool kShareNode = FS_SHARE_NODE && W == 1 && !Geo::kConstT;
-  auto last_node_terms = [&](const NodeTerms<R> &first, R hM, R QM) __attribute__((always_inline)) {
+  // So: one-wave-per-reach kernels with general sections take the neighbour's node terms (12 DPP moves) instead of evaluating
+  // the node a second time.
+  constexpr bool kShareNode = W == 1 && !Geo::kConstT;
+  auto last_node_terms = [&](const NodeTerms<R> &first) __attribute__((always_inline)) {
     auto rol = [](R v) { return dpp_mov<0x134>(v); };     // wave_rol:1
     NodeTerms<R> r;
     r.A = rol(first.A); r.T = rol(first.T); r.Se = rol(first.Se); r.eAT = rol(first.eAT); r.eQ = rol(first.eQ); r.v = rol(first.v);
     r.rT = rol(first.rT);
-    (void)hM; (void)QM;
     return r;
   };
   auto write_level_constants = [&](const R(&hh)[M + 1], const R(&QQ)[M + 1]) __attribute__((always_inline)) {
     NodeTerms<R> L = terms_at(0, hh[0], QQ[0]);
     NodeTerms<R> Rlast;
-    if (kShareNode) Rlast = last_node_terms(L, hh[M], QQ[M]);
+    if (kShareNode) Rlast = last_node_terms(L);
 #pragma unroll
     for (int c = 0; c < M; ++c) {
       const NodeTerms<R> Rn = (kShareNode && c == M - 1) ? Rlast : terms_at(c + 1, hh[c + 1], QQ[c + 1]);
       const R sumA = L.A + Rn.A;
-      // explicit fmas only (no a*b + c left to the compiler's choice: see FS_PRIME)
+      // explicit fmas only (no a*b + c left to the compiler's choice): this code has two instances, ahead of the time loop and at acceptance
+      // inside it, and chunked stepping / a restart gives the bits of one launch only if both compile to the same arithmetic (-ffp-contract=on, Makefile)
       sm.kc[0][c][t] = fma_(cqk, QQ[c + 1] - QQ[c], -(sumA * r2dt));
       sm.kc[1][c][t] = fma_(cqk, fma_(QQ[c + 1], Rn.v, -(QQ[c] * L.v)), -((QQ[c + 1] + QQ[c]) * r2dt));
       sm.kc[2][c][t] = ghthk * sumA;
       sm.kc[3][c][t] = fma_(cqk, geo.bed_step(s0 + c) + (hh[c + 1] - hh[c]), hthk * (L.Se + Rn.Se));
       L = Rn;
-#if FS_LEVEL_FENCE
-      if ((c % FS_LEVEL_FENCE) == FS_LEVEL_FENCE - 1) __builtin_amdgcn_sched_barrier(0);
-#endif
     }
   };
   auto save_terms = [&](int j, const NodeTerms<R> &nt) __attribute__((always_inline)) {
@@ -722,15 +600,10 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
     }
   };
 
-  // The launch starts with a priming pass: (h, Q) hold the accepted state of the entry level and run through the
-  // acceptance block of the loop below once (level constants of the first level to solve, flow[k] of the storage row),
-  // then they are replaced by the Newton start vector.  The level constants of every level - the first one of a launch
-  // included - thus come from ONE instance of the code, and chunked stepping / a restart gives the bits of one launch.
-  constexpr bool kPrime = FS_PRIME;
 #pragma unroll
   for (int j = 0; j <= M; ++j) {
     const int node = min(s0 + j, N - 1);
-    h[j] = kPrime ? a.hk[base + node] : a.hg[base + node];  Q[j] = kPrime ? a.Qk[base + node] : a.Qg[base + node];
+    h[j] = a.hg[base + node];  Q[j] = a.Qg[base + node];
   }
   // per-lane base pointers: every later access is base + immediate offset
   R *const hk_p = a.hk + base + s0, *const Qk_p = a.Qk + base + s0;
@@ -778,16 +651,15 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
   R Yprev = (ds_storage && gt == tD) ? a.Yprev[reach] : R(0);
   int status = a.status[reach];
   // FS_ILL_CONDITIONED is a warning that sticks to the reach, not a failure: the run goes on (and a later launch finds it here)
-  constexpr bool kMonitor = DIAG || FS_MONITOR_ALL;
+  constexpr bool kMonitor = DIAG;             // (what the monitor would cost the no-diagnostics flagship kernel: profiles/round3/README.md)
   bool warn = status == FS_ILL_CONDITIONED;
   if (warn) status = FS_OK;
-  bool primed = false;                        // (h, Q) hold the Newton vector (after the priming pass), not the entry state
   int parity = 0;
-  int exchanges = 0;                          // team form: exchanges made in this launch (the reach's counter stands at exchanges G after each)
+  int exchanges = 0;                          // team form: exchanges made in this launch (the low half of the mailbox tags)
   if (t == 0) { sm.xflag[0] = 0; sm.xflag[1] = 0; }
   __syncthreads();
 
-  if (!kPrime) {   // accepted state of the entry level -> 4 constants per cell in LDS (a second instance of that code)
+  {   // accepted state of the entry level -> 4 constants per cell in LDS (a second instance of the acceptance block's code)
     R hk[M + 1], Qk[M + 1];
 #pragma unroll
     for (int j = 0; j <= M; ++j) {
@@ -799,29 +671,21 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
       for (int j = RAGGED ? 0 : M - 1; j < M; ++j) if (j == jD) QoldD = Qk[j];
     }
     write_level_constants(hk, Qk);
-    primed = true;
   }
 #ifdef FS_STAMP
   unsigned long long stamp_[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long tprev_ = __builtin_amdgcn_s_memtime();
 #endif
-  for (int step = kPrime ? -1 : 0; step < a.n_steps && status == FS_OK; ++step) {
-    int prime = kPrime && step < 0;             // the priming pass (opaque to the optimiser: one loop body, not two)
-    if (kPrime) asm volatile("" : "+s"(prime));
+  for (int step = 0; step < a.n_steps && status == FS_OK; ++step) {
     const int level = a.level0 + step + 1;
-    if (!prime) {
-      if (usd.target) usd.tgt = usd.target[(size_t)level * a.B + reach];
-      if (dsd.target) dsd.tgt = dsd.target[(size_t)level * a.B + reach];
-    }
+    if (usd.target) usd.tgt = usd.target[(size_t)level * a.B + reach];
+    if (dsd.target) dsd.tgt = dsd.target[(size_t)level * a.B + reach];
     int it = kBudget ? it_entry : 0;
     int budget = (kBudget && a.iter_budget > 0) ? a.iter_budget : 0x7fffffff;
     bool converged = false;
     R Ynew = Yprev;
     while (!converged && status == FS_OK) {
       R dh[M + 1], dQ[M + 1];                   // the update, pending until the acceptance block is through
-      if (prime) {
-        converged = true;
-      } else {
       if (kBudget && budget-- <= 0) break;
       ++it;
       if constexpr (BCK <= 0) { if (it - 1 >= max_iter_of()) { status = FS_MAX_ITER; break; } }
@@ -845,15 +709,6 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
       int kco2 = kco + 2 * M * T;
       if constexpr (4 * M * T * sizeof(R) > 65536) asm volatile("" : "+v"(kco2));
       const R *kcb2 = &sm.kc[0][0][0] + kco2;
-#ifdef FS_DUMPKC
-      if (it == 1 && a.dbg && t == (reach & 63) && level < 12) {      // diagnostic builds: what the first iteration of a level starts from
-        unsigned long long *o = a.dbg + ((size_t)reach * 16 + 4 + level) * 12;
-        for (int i = 0; i < 4; ++i) o[i] = __double_as_longlong((double)sm.kc[i][0][t]);
-        for (int i = 0; i < 4; ++i) o[4 + i] = __double_as_longlong((double)sm.kc[i][M - 1][t]);
-        o[8] = __double_as_longlong((double)h[0]); o[9] = __double_as_longlong((double)Q[0]);
-        o[10] = __double_as_longlong((double)h[M]); o[11] = __double_as_longlong((double)Q[M]);
-      }
-#endif
 
       // ================= 1. boundary rows (boundary.py:56-242) =================
       // lane 0: the upstream row on (dh_0, dQ_0); the lane of node N-1: the downstream row, which is row N-1 of the
@@ -907,28 +762,25 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
       seg.u1 = R(0); seg.u3 = R(-1); seg.ru = R(0);
       R upU1 = R(0), upU3 = R(0), upRu = R(0);    // the lane's finished up row, kept for the way back
       R rcLast = R(0);                            // rc of the lane's last row (links node M: p_M = rc - m_{M-1})
-      constexpr bool kW1Lanes = FS_W1_LANES && W == 1 && !kTeam && sizeof(R) == 8;
+      // one-wave fp64 kernels: the root segment and the upstream row meet through v_readlane instead of an LDS round trip
+      // (C5 fp64 +5.5 %, polyline ensemble +2.8 %, C4 +1.9 %; fp32: -0.5 %, left as it was)
+      constexpr bool kW1Lanes = W == 1 && !kTeam && sizeof(R) == 8;
       R xb0 = R(0), xb1 = R(0), xb2 = R(0);      // kW1Lanes: the upstream row, valid in lane 0
       {
         NodeTerms<R> L = terms_at(0, h[0], Q[0]);
         NodeTerms<R> Rlast;
-        if (kShareNode) Rlast = last_node_terms(L, h[M], Q[M]);
+        if (kShareNode) Rlast = last_node_terms(L);
         save_terms(0, L);
         R i2tL = dt * L.rT;
         if (!Geo::kConstT) iTn[0] = i2tL;
         if (gt == 0) {                          // upstream row on (p_0, m_0): aU p_0 + bU m_0 = -res
           const R x = Urow.dh * i2tL, y = Urow.dq * i2c;
           if constexpr (kTeam) {                // (a team's: into the mailbox, next to the segments)
-            if constexpr (kTagged) {
-              const unsigned o = (unsigned)(G * W) * kTeamWords * 16u;
-              const unsigned long long tg = ((unsigned long long)a.team_epoch << 32) | (unsigned)(exchanges + 1);
-              const __amdgpu_buffer_rsrc_t mb = mbox(parity);
-              team_put2(mb, o, __double_as_longlong((double)(x + y)), tg); team_put2(mb, o + 16, __double_as_longlong((double)(x - y)), tg);
-              team_put2(mb, o + 32, __double_as_longlong((double)(-Urow.res)), tg);
-            } else {
-            R *q = a.team_mail + (((size_t)reach * 2 + parity) * (G * W + 1) + G * W) * kTeamWords;
-            team_put(q + 0, x + y); team_put(q + 1, x - y); team_put(q + 2, -Urow.res);
-            }
+            const unsigned o = (unsigned)(G * W) * kTeamWords * 16u;
+            const unsigned long long tg = ((unsigned long long)a.team_epoch << 32) | (unsigned)(exchanges + 1);
+            const __amdgpu_buffer_rsrc_t mb = mbox(parity);
+            team_put2(mb, o, __double_as_longlong((double)(x + y)), tg); team_put2(mb, o + 16, __double_as_longlong((double)(x - y)), tg);
+            team_put2(mb, o + 32, __double_as_longlong((double)(-Urow.res)), tg);
           } else if constexpr (kW1Lanes) {
             xb0 = x + y; xb1 = x - y; xb2 = -Urow.res;
           } else {
@@ -1007,13 +859,13 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
           }
           rcPrev = row.rc;
           // the running rows must exist here: keeps row c's elimination inside cell c's scheduling region
-          // (long chunks only: with M <= 4 the cells' node terms interleave profitably, measured on C4)
-          if constexpr (M >= 8 && (sizeof(R) == 4 ? FS_PIN_SEG_F32 : FS_PIN_SEG) != 0)
+          // (long chunks only: with M <= 4 the cells' node terms interleave profitably, measured on C4; fp32 only: C5 fp32 +5 % with
+          // the pin - round 1's block fold gained 3 % at M >= 8 in fp64 too, the scalar fold has 8 running numbers instead of
+          // 10 + a factor and schedules better without: +1.2 %)
+          if constexpr (M >= 8 && sizeof(R) == 4)
             asm volatile("" :: "v"(seg.u1), "v"(seg.u3), "v"(seg.ru), "v"(seg.d1), "v"(seg.d2), "v"(seg.d3), "v"(seg.rd), "v"(rcPrev));
           L = Rn; i2tL = i2tR;
-#if FS_CELL_FENCE
-          if ((c % FS_CELL_FENCE) == FS_CELL_FENCE - 1) __builtin_amdgcn_sched_barrier(0);
-#endif
+          __builtin_amdgcn_sched_barrier(0);        // one scheduling region per cell
         }
         seg.rc = rcPrev; rcLast = rcPrev;
         upU1 = seg.u1; upU3 = seg.u3; upRu = seg.ru;
@@ -1022,21 +874,15 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
       if constexpr (kMonitor) gi = hi_abs(seg.u3);
 
       FS_T(0);
-#if FS_PHASE_FENCE & 1
-      __builtin_amdgcn_sched_barrier(0);   // phases are not interleaved: it only costs registers (measured around the down-sweep: +5 %)
-#endif
       // ================= 3. in-wave tree (up-sweep) =================
-      constexpr bool kTreeRegs = FS_TREE_REGS && W > 1 && M >= 8 && !DIAG;
-      Elim<R> rec[kTreeRegs ? 6 : 1];
+      Elim<R> rec[1];      // (never used: the polyline kernels' machine code depends on this declaration, on rcE, pre4 and pre3 below - tools/isa_digest.py)
       auto up_level = [&](auto lc) __attribute__((always_inline)) {
         constexpr int l = decltype(lc)::value;
         constexpr int d = 1 << l;
         const Seg<R> left = seg_from_below<d>(seg);
         Seg<R> mg; Elim<R> e;
         merge(left, seg, mg, e);
-        if constexpr (kTreeRegs) {
-          rec[l] = e;
-        } else if ((lane & (2 * d - 1)) == (2 * d - 1)) {
+        if ((lane & (2 * d - 1)) == (2 * d - 1)) {
           const int slot = (64 - (64 >> l)) + (ln >> (l + 1));
           R *p = &sm.tree[wave][0][slot];
           p[0 * 64] = e.A1; p[1 * 64] = e.A2; p[2 * 64] = e.A3; p[3 * 64] = e.rc;
@@ -1047,30 +893,16 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
       up_level(std::integral_constant<int, 0>{}); up_level(std::integral_constant<int, 1>{});
       up_level(std::integral_constant<int, 2>{}); up_level(std::integral_constant<int, 3>{});
       up_level(std::integral_constant<int, 4>{}); up_level(std::integral_constant<int, 5>{});
-#if FS_PHASE_FENCE & 1
-      __builtin_amdgcn_sched_barrier(0);
-#endif
       nrm2 = wave_sum(nrm2);
       if constexpr (kTeam) {
         const int wflag = __builtin_amdgcn_ballot_w64(myflag != 0) != 0 ? (int)FS_STORAGE_RANGE : 0;      // raised by a lane of this wave
-        if constexpr (kTagged) {
-          if (lane == 63) {
-            const unsigned o = (unsigned)(member * W + wave) * kTeamWords * 16u;
-            const unsigned long long tg = ((unsigned long long)a.team_epoch << 32) | (unsigned)(exchanges + 1);
-            const __amdgpu_buffer_rsrc_t mb = mbox(parity);
-            auto put = [&](int i, R v) __attribute__((always_inline)) { team_put2(mb, o + 16u * i, __double_as_longlong((double)v), tg); };
-            put(0, seg.u1); put(1, seg.u3); put(2, seg.ru); put(3, seg.d1); put(4, seg.d2); put(5, seg.d3); put(6, seg.rd); put(7, seg.rc); put(8, nrm2);
-            team_put2(mb, o + 16u * 9, ((unsigned long long)(unsigned)wflag << 32) | (unsigned)gi, tg);
-          }
-        } else {
-        if (lane == 63) {                    // the wave's slot of the team's mailbox (device memory; published by the release below)
-          R *p = a.team_mail + (((size_t)reach * 2 + parity) * (G * W + 1) + (member * W + wave)) * kTeamWords;
-          team_put(p + 0, seg.u1); team_put(p + 1, seg.u3); team_put(p + 2, seg.ru); team_put(p + 3, seg.d1); team_put(p + 4, seg.d2);
-          team_put(p + 5, seg.d3); team_put(p + 6, seg.rd); team_put(p + 7, seg.rc); team_put(p + 8, nrm2);
-          int32_t *pi = reinterpret_cast<int32_t *>(p + 9);
-          team_put(pi, gi); team_put(pi + 1, wflag);
-        }
-        team_posted();
+        if (lane == 63) {                    // the wave's slot of the team's mailbox (device memory)
+          const unsigned o = (unsigned)(member * W + wave) * kTeamWords * 16u;
+          const unsigned long long tg = ((unsigned long long)a.team_epoch << 32) | (unsigned)(exchanges + 1);
+          const __amdgpu_buffer_rsrc_t mb = mbox(parity);
+          auto put = [&](int i, R v) __attribute__((always_inline)) { team_put2(mb, o + 16u * i, __double_as_longlong((double)v), tg); };
+          put(0, seg.u1); put(1, seg.u3); put(2, seg.ru); put(3, seg.d1); put(4, seg.d2); put(5, seg.d3); put(6, seg.rd); put(7, seg.rc); put(8, nrm2);
+          team_put2(mb, o + 16u * 9, ((unsigned long long)(unsigned)wflag << 32) | (unsigned)gi, tg);
         }
       } else if constexpr (kW1Lanes) {
         // nothing to post: the root segment is read from lane 63 below
@@ -1082,8 +914,8 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
         if constexpr (kMonitor) sm.xg[parity][wave] = gi;
       }
       FS_T(2);
-      // the wave's own top tree records for the way down (step 5), requested ahead of the barrier: their LDS latency passes
-      // during the cross-wave step instead of after it (FS_PREFETCH_DOWN levels; the wave wrote them itself, in order)
+      // the wave's own top tree record (level 5) for the way down (step 5), requested ahead of the barrier: its LDS latency passes
+      // during the cross-wave step instead of after it (multi-wave kernels without diagnostics; the wave wrote it itself, in order)
       auto load_rec_early = [&](auto lc) __attribute__((always_inline)) {
         constexpr int l = decltype(lc)::value;
         Elim<R> e;
@@ -1092,64 +924,36 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
         e.A1 = p[0 * 64]; e.A2 = p[1 * 64]; e.A3 = p[2 * 64]; e.rc = p[3 * 64];
         return e;
       };
-      constexpr int kPre = (W > 1 && M >= 8 && !DIAG && !kTreeRegs) ? FS_PREFETCH_DOWN : 0;
-      Elim<R> pre5, pre4, pre3;
-      if constexpr (kPre >= 1) pre5 = load_rec_early(std::integral_constant<int, 5>{});
-      if constexpr (kPre >= 2) pre4 = load_rec_early(std::integral_constant<int, 4>{});
-      if constexpr (kPre >= 3) pre3 = load_rec_early(std::integral_constant<int, 3>{});
-      // (the tagged team form could do without this barrier - wave 0 polls the mailbox for every wave's post, its own workgroup's included - and is
+      constexpr bool kPre = W > 1 && M >= 8 && !DIAG;
+      Elim<R> pre5, pre4, pre3;      // (pre4 and pre3 are never used: see rec above)
+      if constexpr (kPre) pre5 = load_rec_early(std::integral_constant<int, 5>{});
+      // (the team form could do without this barrier - wave 0 polls the mailbox for every wave's post, its own workgroup's included - and is
       // 6 % SLOWER without it: a wave 0 that starts polling while its neighbours still fold takes their issue slots and their memory path)
       // (one-wave reaches: no s_barrier is emitted for 64 threads, and dropping the workgroup fence with it changes nothing - measured, C4 / C5 / polylines +-0.3 %)
       __syncthreads();
       FS_T(3);
-      // rc of the lane's rows for the back-substitution (step 5) does not depend on the solve: computed here, its instructions
-      // fill the waits of the cross-wave step (a chain of dependent merges and reciprocals) instead of lengthening step 5
-      constexpr bool kRcEarly = FS_RC_EARLY && Geo::kConstT && FS_LAUNDER_BACK && W > 1 && M >= 8 && !DIAG && !RAGGED;
-      R rcE[kRcEarly ? M - 1 : 1];
-      if constexpr (kRcEarly) {
-        asm volatile("" : "+v"(kco));
-        kcb = &sm.kc[0][0][0] + kco;
-#pragma unroll
-        for (int j = 0; j <= M; ++j) asm volatile("" : "+v"(h[j]), "+v"(Q[j]));
-#pragma unroll
-        for (int j = 0; j + 1 < M; ++j)
-          rcE[j] = -(geo.terms_T() * (h[j] + h[j + 1]) * r2dt + cq * (Q[j + 1] - Q[j]) + kcb[(0 * M + j) * T]);
-      }
-
+      R rcE[1];            // (never used: see rec above)
       // ================= 4. across waves: fold, close with the upstream row, unfold =================
-#if FS_XWAVE_FENCE & 1
-      __builtin_amdgcn_sched_barrier(0);
-#endif
+      // Waves per reach from which the step runs as a second, small DPP tree (lane w of every wave carries the segment of wave w: 8 live
+      // numbers) instead of every thread folding all W segments in its own registers (16 W live doubles).  Measured on 65 536 x 4 096
+      // (profiles/round3/second_wave_per_simd.md): W = 8 (the (8, 8) shape, two waves per SIMD) 7.9e6 -> 9.8e6 (the per-thread fold spills
+      // at 256 registers); W = 4 (the flagship (16, 4) shape) 1.072e7 -> 1.058e7: with four segments the per-thread fold has the shorter
+      // dependent chain
+      constexpr int kXLanesMinW = 8;
       R tot = R(0);
       R pL, mR;                        // p of this wave's first row, m of its last one
       R mAw = R(0), mBw = R(0);        // m of this wave's first row / of the next wave's first row (shared nodes, below)
       if constexpr (kTeam) {
-        // ---- the team's exchange: where one workgroup has a barrier, G workgroups have a counter in device memory ----
-        // (every poster has seen its stores acknowledged before the __syncthreads above, thread 0 counts the workgroup in after it; the
-        // counter of a reach only grows: the e-th exchange of the launch is complete when it reaches e G)
+        // ---- the team's exchange: where one workgroup has a barrier, G workgroups have the tags of their mailbox in device memory ----
         ++exchanges;
-        if (!kTagged && t == 0) {
-          unsigned long long *cnt = a.team_sync + 1 + reach;
-          __hip_atomic_fetch_add(cnt, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          const unsigned long long want = (unsigned long long)exchanges * (unsigned long long)G;
-          const unsigned long long t_in = __builtin_amdgcn_s_memtime();
-          int stall = 0;
-          // (relaxed polls: an acquire per poll would invalidate the caches of the whole XCD on every turn; one acquire fence follows the wait)
-          while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
-            __builtin_amdgcn_s_sleep(1);
-            if (__builtin_amdgcn_s_memtime() - t_in > kTeamPatience) { stall = 1; break; }     // give the reach up, do not spin on
-          }
-          sm.xstall = stall;
-        }
         FS_T(11);
-        if constexpr (!kTagged) __syncthreads();
         if (wave == 0) {
           // the top tree over the S = G W posted segments, one per lane, identity segments beyond (the multi-pass kernel's, fs_long.hpp)
           const int S = G * W;
           Seg<R> xs;
           R nr, aU, bU, rU;
           int gx, fl;
-          if constexpr (kTagged) {
+          {
             // lane s polls the ten words of slot s, every lane the three of the upstream row, until all carry this exchange's tag
             const unsigned long long want = ((unsigned long long)a.team_epoch << 32) | (unsigned)exchanges;
             const __amdgpu_buffer_rsrc_t mb = mbox(parity);
@@ -1166,7 +970,7 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
 #pragma unroll
               for (int i = 0; i < 13; ++i) ok = ok && team_tag(w[i]) == want;
               if (__builtin_amdgcn_ballot_w64(!ok) == 0) break;
-              __builtin_amdgcn_s_sleep(FS_TEAM_SLEEP);
+              __builtin_amdgcn_s_sleep(kTeamSleep);
               if (__builtin_amdgcn_s_memtime() - t_in > kTeamPatience) { stall = 1; break; }     // give the reach up, do not spin on
             }
             if (lane == 0) sm.xstall = stall;
@@ -1175,18 +979,6 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
             nr = val(8);
             gx = (int)(unsigned)team_bits(w[9]); fl = (int)(unsigned)(team_bits(w[9]) >> 32);
             aU = val(10); bU = val(11); rU = val(12);
-          } else {
-          const R *mail = a.team_mail + ((size_t)reach * 2 + parity) * (S + 1) * kTeamWords;
-          const R *q = mail + (size_t)(lane < S ? lane : 0) * kTeamWords;
-          auto ld = [&](int i) { return __hip_atomic_load(q + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-          xs.u1 = ld(0); xs.u3 = ld(1); xs.ru = ld(2); xs.d1 = ld(3); xs.d2 = ld(4); xs.d3 = ld(5); xs.rd = ld(6); xs.rc = ld(7);
-          nr = ld(8);
-          const int32_t *qi = reinterpret_cast<const int32_t *>(q + 9);
-          gx = __hip_atomic_load(qi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          fl = __hip_atomic_load(qi + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          aU = __hip_atomic_load(mail + (size_t)S * kTeamWords + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          bU = __hip_atomic_load(mail + (size_t)S * kTeamWords + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          rU = __hip_atomic_load(mail + (size_t)S * kTeamWords + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
           if (lane >= S) { xs.u1 = R(0); xs.u3 = R(0); xs.ru = R(0); xs.d1 = R(0); xs.d2 = R(1); xs.d3 = R(0); xs.rd = R(0); xs.rc = R(0); nr = R(0); gx = 0; fl = 0; }
           const R u1o = xs.u1, u3o = xs.u3, ruo = xs.ru;
@@ -1258,7 +1050,7 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
         close_root(seg, aU, bU, rU, p0, m0, ml);
         pL = read_lane(p0, 63); mR = read_lane(ml, 63);
         if constexpr (kMonitor) { if (__builtin_amdgcn_readlane(gi, 63) > growth_limit_bits<R>()) grow = true; }
-      } else if constexpr (W > 1 && W >= FS_XLANES_MINW) {
+      } else if constexpr (W > 1 && W >= kXLanesMinW) {
         // A second, small tree over the W wave segments, one segment per LANE: lane w of every wave takes the segment of
         // wave w and the W - 1 merges run as log2 W DPP levels (row_shr:1/2/4) exactly like the in-wave tree - the same
         // merges in the same order as the per-thread fold below, so the bits do not change - with 8 live numbers per lane
@@ -1318,72 +1110,6 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
         mBw = read_lane(max_, (ws + 1) & (W - 1));
         if (ws == W - 1) mBw = R(0);
         if constexpr (kMonitor) { if (__builtin_amdgcn_readlane(gx, W - 1) > growth_limit_bits<R>()) grow = true; }
-      } else if constexpr (FS_XWAVE_CONT && !kMonitor && sizeof(R) == 8 && W > 1) {
-        // The W wave segments and the upstream row as ONE tridiagonal system.  With the links p_a(w) = rc_{w-1} - x_{w-1} and every
-        // wave's up row  m_a(w) = ru_w - u1_w p_a(w) - u3_w x_w  substituted into the down rows, the unknowns y = (p_0, x_0 .. x_{W-1}),
-        // x_w = m of wave w's last row, satisfy
-        //   row U  :                 (aU - bU u1_0) p_0 - bU u3_0 x_0                          = rU - bU ru_0
-        //   row k  : -d1_k x_{k-1} + (d2_k + d3_k u1_{k+1}) x_k - d3_k u3_{k+1} x_{k+1}        = rd_k - d1_k rc_{k-1} - d3_k (ru_{k+1} - u1_{k+1} rc_k)
-        //            (k = 0: + d1_0 p_0 and no rc_{-1} term; k = W-1: nothing to its right)
-        // Forward continuants th_i = B_i th_{i-1} - A_i C_{i-1} th_{i-2} with right-hand sides rho_i = th_{i-1} R_i - A_i rho_{i-1},
-        // backward ones ph_i, sg_i alike; det = th_W and  y_i = (ph_{i+1} rho_i - C_i th_{i-1} sg_{i+1}) / det : two independent chains
-        // of W + 1 steps and ONE reciprocal where the pairwise fold below has four dependent reciprocal chains (two merge levels, the
-        // two of the root closure).  The rows are diagonally dominant wherever the elimination itself is sound (fs_device.hpp); the
-        // kernels that watch the conditioning (kMonitor) keep the fold, whose merged segments the monitor reads.
-        Seg<R> sw[W];
-#pragma unroll
-        for (int w = 0; w < W; ++w) {
-          const R *p = sm.xseg[parity][w];
-          sw[w].u1 = p[0]; sw[w].u3 = p[1]; sw[w].ru = p[2]; sw[w].d1 = p[3]; sw[w].d2 = p[4]; sw[w].d3 = p[5];
-          sw[w].rd = p[6]; sw[w].rc = p[7];
-          tot += sm.xnorm[parity][w];
-        }
-        constexpr int n = W;                         // unknowns y_0 .. y_n
-        const R aU = sm.xbc[parity][0], bU = sm.xbc[parity][1], rU = sm.xbc[parity][2];
-        R Ac[n + 1], Bc[n + 1], Cc[n + 1], Rc[n + 1], AC[n + 1];     // AC[i] = A_i C_{i-1}
-        Ac[0] = R(0); Bc[0] = fma_(-bU, sw[0].u1, aU); Cc[0] = -(bU * sw[0].u3); Rc[0] = fma_(-bU, sw[0].ru, rU); AC[0] = R(0);
-#pragma unroll
-        for (int k = 0; k < W; ++k) {
-          const int i = k + 1;
-          Ac[i] = k == 0 ? sw[0].d1 : -sw[k].d1;
-          const R rdk = k == 0 ? sw[0].rd : fma_(-sw[k].d1, sw[k - 1].rc, sw[k].rd);
-          if (k + 1 < W) {
-            Bc[i] = fma_(sw[k].d3, sw[k + 1].u1, sw[k].d2); Cc[i] = -(sw[k].d3 * sw[k + 1].u3);
-            Rc[i] = fma_(-sw[k].d3, fma_(-sw[k + 1].u1, sw[k].rc, sw[k + 1].ru), rdk);
-          } else {
-            Bc[i] = sw[k].d2; Cc[i] = R(0); Rc[i] = rdk;
-          }
-          AC[i] = Ac[i] * Cc[i - 1];
-        }
-        R th[n + 1], rho[n + 1], ph[n + 2], sg[n + 2];
-        th[0] = Bc[0]; rho[0] = Rc[0];
-        th[1] = fma_(Bc[1], th[0], -AC[1]); rho[1] = fma_(th[0], Rc[1], -(Ac[1] * rho[0]));
-#pragma unroll
-        for (int i = 2; i <= n; ++i) { th[i] = fma_(Bc[i], th[i - 1], -(AC[i] * th[i - 2])); rho[i] = fma_(th[i - 1], Rc[i], -(Ac[i] * rho[i - 1])); }
-        ph[n + 1] = R(1); sg[n + 1] = R(0);
-        ph[n] = Bc[n]; sg[n] = Rc[n];
-        ph[n - 1] = fma_(Bc[n - 1], ph[n], -AC[n]); sg[n - 1] = fma_(ph[n], Rc[n - 1], -(Cc[n - 1] * sg[n]));
-#pragma unroll
-        for (int i = n - 2; i >= 1; --i) { ph[i] = fma_(Bc[i], ph[i + 1], -(AC[i + 1] * ph[i + 2])); sg[i] = fma_(ph[i + 1], Rc[i], -(Cc[i] * sg[i + 1])); }
-        const R rdet = frcp(th[n]);
-        R y[n + 1];
-        y[0] = fma_(ph[1], rho[0], -(Cc[0] * sg[1])) * rdet;
-#pragma unroll
-        for (int i = 1; i < n; ++i) y[i] = fma_(ph[i + 1], rho[i], -(Cc[i] * th[i - 1] * sg[i + 1])) * rdet;
-        y[n] = rho[n] * rdet;
-        R pw[W], ma[W + 1];
-        pw[0] = y[0];
-#pragma unroll
-        for (int w = 1; w < W; ++w) pw[w] = sw[w - 1].rc - y[w];
-        // m of every wave's first row from its own up row: the node there is shared with the wave before, and both
-        // copies must move by the same bits
-#pragma unroll
-        for (int w = 0; w < W; ++w) ma[w] = fma_(-sw[w].u1, pw[w], fma_(-sw[w].u3, y[w + 1], sw[w].ru));
-        ma[W] = R(0);
-        pL = pw[0]; mR = y[1]; mAw = ma[0]; mBw = ma[1];
-#pragma unroll
-        for (int w = 1; w < W; ++w)
-          if (wave == w) { pL = pw[w]; mR = y[w + 1]; mAw = ma[w]; mBw = ma[w + 1]; }
       } else {
       {
         // pairwise tree over the W wave segments (depth log2 W instead of a serial chain of W-1 merges;
@@ -1434,9 +1160,6 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
           if (wave == w) { pL = pw[w]; mR = mw[w]; mAw = ma[w]; mBw = ma[w + 1]; }
       }
       }
-#if FS_XWAVE_FENCE & 2
-      __builtin_amdgcn_sched_barrier(0);
-#endif
       FS_T(4);
       if (!kTeam && (BCK < 2 || ds_storage) && sm.xflag[parity] != 0) status = sm.xflag[parity];     // only the storage rows raise a flag (a team's: through the mailbox, above)
       // ||R|| = sqrt(tot) (utility.py:20-22) is NaN or beyond the blow-up bound (preissmann.py:135-137) exactly when tot is
@@ -1493,33 +1216,12 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
         using I3 = std::integral_constant<int, 3>; using I2 = std::integral_constant<int, 2>;
         using I1 = std::integral_constant<int, 1>; using I0 = std::integral_constant<int, 0>;
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (kTreeRegs) {
-          // the group's record from the group's last lane: readlane (the wave, its halves), row_newbcast (rows of 16, halves of a
-          // row through the bank mask), quad_perm (quads, pairs)
-          auto fetch = [&](auto lc2, R v) __attribute__((always_inline)) {
-            constexpr int l = decltype(lc2)::value;
-            if constexpr (l == 5) return read_lane(v, 63);
-            else if constexpr (l == 4) { const R lo = read_lane(v, 31), hi = read_lane(v, 63); return lane < 32 ? lo : hi; }
-            else if constexpr (l == 3) return dpp_mov<0x15F>(v);
-            else if constexpr (l == 2) return dpp_mov_banks<0x15F, 0xC>(dpp_mov_banks<0x157, 0x3>(R(0), v), v);
-            else if constexpr (l == 1) return dpp_mov<0xFF>(v);
-            else return dpp_mov<0xF5>(v);
-          };
-          auto rec_of = [&](auto lc2) __attribute__((always_inline)) {
-            constexpr int l = decltype(lc2)::value;
-            Elim<R> e;
-            e.A1 = fetch(lc2, rec[l].A1); e.A2 = fetch(lc2, rec[l].A2); e.A3 = fetch(lc2, rec[l].A3); e.rc = fetch(lc2, rec[l].rc);
-            return e;
-          };
-          down_level(I5{}, rec_of(I5{})); down_level(I4{}, rec_of(I4{})); down_level(I3{}, rec_of(I3{}));
-          down_level(I2{}, rec_of(I2{})); down_level(I1{}, rec_of(I1{})); down_level(I0{}, rec_of(I0{}));
-        } else {
-        Elim<R> r5, r4, r3;
-        if constexpr (kPre >= 1) r5 = pre5; else r5 = load_rec(I5{});
-        if constexpr (kPre >= 2) r4 = pre4; else r4 = load_rec(I4{});
+        Elim<R> r5, r4, r3;      // (declared ahead of their loads, not where they are loaded: the table and polyline kernels' machine code depends on it)
+        if constexpr (kPre) r5 = pre5; else r5 = load_rec(I5{});
+        r4 = load_rec(I4{});
         asm volatile("" ::: "memory");
         down_level(I5{}, r5);
-        if constexpr (kPre >= 3) r3 = pre3; else r3 = load_rec(I3{});
+        r3 = load_rec(I3{});
         asm volatile("" ::: "memory");
         down_level(I4{}, r4);
         const Elim<R> r2 = load_rec(I2{});
@@ -1532,7 +1234,6 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
         asm volatile("" ::: "memory");
         down_level(I1{}, r1);
         down_level(I0{}, r0);
-        }
         asm volatile("" : "+v"(pL), "+v"(mR));
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -1545,7 +1246,7 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
 
       // The update is kept pending in dh/dQ (they take the registers the elimination records free up):
       // the accepted iterate must still be intact for the level-constant pass below.
-      if (Geo::kConstT && FS_LAUNDER_BACK && !kRcEarly) {
+      if (Geo::kConstT) {
         // The continuity residuals are recomputed below on purpose (one value per node less to keep
         // across the solve).  Hide the operands so that common-subexpression elimination does not
         // resurrect the fold's copies of dQ / kc0 and keep 2 values per node alive instead.
@@ -1559,7 +1260,6 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
         auto i2t_of = [&](int j) { return Geo::kConstT ? i2tc : iTn[j]; };
         // rc of row j for the link p_{j+1} = rc_j - m_j: minus the continuity residual of cell j, 0 beyond the cells
         auto rc_of = [&](int j) __attribute__((always_inline)) {
-          if constexpr (kRcEarly) return rcE[j];
           if (Geo::kConstT) {
             const R v = -(geo.terms_T() * (h[j] + h[j + 1]) * r2dt + cq * (Q[j + 1] - Q[j]) + kcb[(0 * M + j) * T]);
             return (RAGGED && s0 + j >= NC) ? R(0) : v;
@@ -1587,38 +1287,34 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
         if constexpr (kTail) { dh[0] *= mle; dQ[0] *= mle; }
       }
       FS_T(6);
-      if constexpr (((sizeof(R) == 4 ? FS_PHASE_FENCE_F32 : FS_PHASE_FENCE) & 8) != 0) {
+      // fp32 only: pin the back-substituted updates and fence them off from the acceptance block (three waves per SIMD at 168 registers:
+      // the fence keeps them there, C5 fp32 +4.5 %; fp64: round 1 +0.9 %, with the round-2 solve flagship -2.3 %)
+      if constexpr (sizeof(R) == 4) {
 #pragma unroll
         for (int j = 1; j < M; ++j) asm volatile("" : "+v"(dh[j]), "+v"(dQ[j]));
         __builtin_amdgcn_sched_barrier(0);
       }
-#if FS_PHASE_FENCE & 1
-      __builtin_amdgcn_sched_barrier(0);
-#endif
-      }   // !prime
 
       // ================= 6. accepted iterate -> level k =================
       if (converged) {
-        if (!prime && gt == 0) {
+        if (gt == 0) {
           a.hydro[((size_t)level * 4 + 0) * a.B + reach] = h[0];
           a.hydro[((size_t)level * 4 + 1) * a.B + reach] = Q[0];
           a.iters[(size_t)level * a.B + reach] = it;
         }
-        if (!prime) {
-          // Level k+1 is rebuilt from registers, so the accepted state only has to reach HBM when
-          // somebody can look at it: at the last level of this launch (fs_batch_get_state, next launch)
-          // and, if a history is kept, at every level.  (A transposed, fully coalesced write-back
-          // through LDS was measured too: no gain, three extra barriers.)
-          const bool last = (step == a.n_steps - 1);
-          R *const hh_p = (DIAG && a.hist_h) ? a.hist_h + ((size_t)level * a.B + reach) * NS + s0 : nullptr;
-          R *const hQ_p = (DIAG && a.hist_h) ? a.hist_Q + ((size_t)level * a.B + reach) * NS + s0 : nullptr;
-          if (last || hh_p) {
+        // Level k+1 is rebuilt from registers, so the accepted state only has to reach HBM when
+        // somebody can look at it: at the last level of this launch (fs_batch_get_state, next launch)
+        // and, if a history is kept, at every level.  (A transposed, fully coalesced write-back
+        // through LDS was measured too: no gain, three extra barriers.)
+        const bool last = (step == a.n_steps - 1);
+        R *const hh_p = (DIAG && a.hist_h) ? a.hist_h + ((size_t)level * a.B + reach) * NS + s0 : nullptr;
+        R *const hQ_p = (DIAG && a.hist_h) ? a.hist_Q + ((size_t)level * a.B + reach) * NS + s0 : nullptr;
+        if (last || hh_p) {
 #pragma unroll
-            for (int j = 0; j < M; ++j) {
-              if (!RAGGED || s0 + j < N) {
-                if (last) { hk_p[j] = h[j]; Qk_p[j] = Q[j]; }
-                if (hh_p) { hh_p[j] = h[j]; hQ_p[j] = Q[j]; }
-              }
+          for (int j = 0; j < M; ++j) {
+            if (!RAGGED || s0 + j < N) {
+              if (last) { hk_p[j] = h[j]; Qk_p[j] = Q[j]; }
+              if (hh_p) { hh_p[j] = h[j]; hQ_p[j] = Q[j]; }
             }
           }
         }
@@ -1627,25 +1323,15 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
 #pragma unroll
           for (int j = RAGGED ? 0 : M - 1; j < M; ++j)
             if (j == jD) {
-              if (!prime) {
-                a.hydro[((size_t)level * 4 + 2) * a.B + reach] = h[j];
-                a.hydro[((size_t)level * 4 + 3) * a.B + reach] = Q[j];
-              }
+              a.hydro[((size_t)level * 4 + 2) * a.B + reach] = h[j];
+              a.hydro[((size_t)level * 4 + 3) * a.B + reach] = Q[j];
               QoldD = Q[j];                                             // flow[k] of the next level's storage row
             }
-          if (!prime) {
-            Yprev = Ynew;
-            if (ds_storage) a.stage_hist[(size_t)level * a.B + reach] = Ynew;
-          }
+          Yprev = Ynew;
+          if (ds_storage) a.stage_hist[(size_t)level * a.B + reach] = Ynew;
         }
         FS_T(9);
         if (kSaveTerms) {                                             // level constants of the next level
-          if (prime) {                           // no fold has run yet: the node terms of the entry state go where a fold leaves them
-            NodeTerms<R> L = terms_at(0, h[0], Q[0]);
-            save_terms(0, L);
-#pragma unroll
-            for (int c = 0; c < M; ++c) save_terms(c + 1, terms_at(c + 1, h[c + 1], Q[c + 1]));
-          }
           level_constants_from_saved(h, Q);
         } else {
           write_level_constants(h, Q);
@@ -1654,19 +1340,9 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
       }
 
       FS_T(5);
-      if (prime) {                               // Newton start vector of the first level to solve
 #pragma unroll
-        for (int j = 0; j <= M; ++j) {
-          const int node = min(s0 + j, N - 1);
-          h[j] = a.hg[base + node];  Q[j] = a.Qg[base + node];
-        }
-        primed = true;
-      } else {
-#pragma unroll
-        for (int j = 0; j <= M; ++j) { h[j] += dh[j]; Q[j] += dQ[j]; }     // preissmann.py:146-147
-      }
+      for (int j = 0; j <= M; ++j) { h[j] += dh[j]; Q[j] += dQ[j]; }     // preissmann.py:146-147
     }
-    if (prime) continue;
     if (status != FS_OK && gt == 0) a.iters[(size_t)level * a.B + reach] = it - (status == FS_MAX_ITER ? 1 : 0);
     if (kBudget && a.iter_budget > 0) {
       if (t == 0) a.it_done[reach] = (converged || status != FS_OK) ? -1 : it;
@@ -1675,11 +1351,9 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
   }
 
   // ---- Newton start vector of the next level + per-reach bookkeeping ----
-  if (primed) {                               // (a reach that came in failed keeps what it had)
 #pragma unroll
-    for (int j = 0; j < M; ++j)
-      if (!RAGGED || s0 + j < N) { hg_p[j] = h[j]; Qg_p[j] = Q[j]; }
-  }
+  for (int j = 0; j < M; ++j)
+    if (!RAGGED || s0 + j < N) { hg_p[j] = h[j]; Qg_p[j] = Q[j]; }
   if (gt == 0) a.status[reach] = (status == FS_OK && warn) ? (int)FS_ILL_CONDITIONED : status;
   if (ds_storage && gt == tD) a.Yprev[reach] = Yprev;
 #ifdef FS_STAMP

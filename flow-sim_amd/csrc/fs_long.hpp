@@ -34,7 +34,7 @@ template <typename R, int W, int M> struct SmemLong {
   // per-wave staging of the wave's 64 M (+ 1) nodes of a pass: global memory is read and written with consecutive lanes on
   // consecutive nodes, a lane takes its M + 1 consecutive nodes from here (one pad per 8 numbers: the lanes' chunks start in
   // different banks)
-  R stage[W][2][FS_LONG_COALESCE ? 64 * M + 8 * M + 8 : 1];
+  R stage[W][2][64 * M + 8 * M + 8];
   R tree[W][4][64];        // in-wave tree records of the pass being worked on
   R xtree[4][64];          // records of the top tree over the (pass, wave) segments (wave 0)
   R xseg[64][8];           // one segment per (pass, wave)
@@ -48,9 +48,10 @@ template <typename R, int W, int M> struct SmemLong {
 };
 
 // waves per SIMD the kernel is compiled for: without the level constants in flight the uniform-section kernels need 298 registers;
-// capped at 256 two workgroups share a CU and one covers the other's memory waits (FS_LONG_WPE)
+// capped at 256 two workgroups share a CU and one covers the other's memory waits
+constexpr int kLongWpe = 2;
 template <typename R, int SEC> constexpr int long_min_waves() {
-  return (FS_LONG_RECOMPUTE && (SEC == FS_SEC_RECT_UNIFORM || SEC == FS_SEC_TRAP_UNIFORM) && sizeof(R) == 8) ? FS_LONG_WPE : 1;
+  return ((SEC == FS_SEC_RECT_UNIFORM || SEC == FS_SEC_TRAP_UNIFORM) && sizeof(R) == 8) ? kLongWpe : 1;
 }
 
 template <typename R, int SEC, int M, int W, int BCK>
@@ -61,7 +62,7 @@ __global__ __launch_bounds__(64 * W, (long_min_waves<R, SEC>())) void preissmann
   // Uniform sections: the four level constants of a cell are recomputed in every sweep from the accepted state of level k (two node
   // evaluations of ~40 instructions) instead of being fetched from a scratch: 16 B instead of 32 B per node and sweep for a kernel
   // that is bound by HBM.  Same expressions as the stored ones, hence the same bits.
-  constexpr bool kRecompute = FS_LONG_RECOMPUTE && (SEC == FS_SEC_RECT_UNIFORM || SEC == FS_SEC_TRAP_UNIFORM);
+  constexpr bool kRecompute = SEC == FS_SEC_RECT_UNIFORM || SEC == FS_SEC_TRAP_UNIFORM;
   __shared__ SmemLong<R, W, M> sm;
 
   const int reach = blockIdx.x;
@@ -131,7 +132,6 @@ __global__ __launch_bounds__(64 * W, (long_min_waves<R, SEC>())) void preissmann
   // every load instruction of load_nodes touches 64 separate 64-byte segments, and the texture addresser was busy 82 % of the
   // kernel's time with them, profiles/round3/long_mem.txt), transposed through the wave's staging buffer.  LDS executes a wave's
   // instructions in order; the fences keep the compiler from moving the reads over the writes.
-  constexpr bool kCo = FS_LONG_COALESCE != 0;
   auto pad = [](int i) { return i + (i >> 3); };
   auto wave_sync = [] {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -140,23 +140,6 @@ __global__ __launch_bounds__(64 * W, (long_min_waves<R, SEC>())) void preissmann
   };
   auto load_nodes_co = [&](const R *hs, const R *Qs, int p, R(&h)[M + 1], R(&Q)[M + 1]) __attribute__((always_inline)) {
     const int wb = p * C + wave * (64 * M);                   // first node of this wave in this pass
-    auto one = [&](const R *src, R *st, R(&out)[M + 1]) __attribute__((always_inline)) {
-      R tv[M + 1];
-#pragma unroll
-      for (int k = 0; k < M; ++k) tv[k] = src[base + min(wb + lane + 64 * k, N - 1)];
-      if (lane == 0) tv[M] = src[base + min(wb + 64 * M, N - 1)];     // the node the wave shares with its right neighbour
-#pragma unroll
-      for (int k = 0; k < M; ++k) st[pad(lane + 64 * k)] = tv[k];
-      if (lane == 0) st[pad(64 * M)] = tv[M];
-      wave_sync();
-#pragma unroll
-      for (int j = 0; j <= M; ++j) out[j] = st[pad(lane * M + j)];
-    };
-    if constexpr (FS_LONG_COALESCE == 2) {      // one array after the other (half the numbers in flight)
-      one(hs, sm.stage[wave][0], h);
-      one(Qs, sm.stage[wave][1], Q);
-      wave_sync();
-    } else {
     R *const sh = sm.stage[wave][0], *const sq = sm.stage[wave][1];
     R th[M + 1], tq[M + 1];
 #pragma unroll
@@ -175,7 +158,6 @@ __global__ __launch_bounds__(64 * W, (long_min_waves<R, SEC>())) void preissmann
 #pragma unroll
     for (int j = 0; j <= M; ++j) { h[j] = sh[pad(lane * M + j)]; Q[j] = sq[pad(lane * M + j)]; }
     wave_sync();
-    }
   };
   // values of the lane's nodes g0 .. g0 + M - 1 to hd / Qd (nodes beyond the reach are not written)
   auto store_nodes_co = [&](R *hd, R *Qd, int p, const R *hv, const R *Qv) __attribute__((always_inline)) {
@@ -227,8 +209,6 @@ __global__ __launch_bounds__(64 * W, (long_min_waves<R, SEC>())) void preissmann
   }
   __syncthreads();
 
-  constexpr bool kPf = FS_LONG_PREFETCH != 0 && kCo;
-  int pf[4] = {0, 0, 0, 0};
   for (int step = 0; step < a.n_steps && status == FS_OK; ++step) {
     const int level = a.level0 + step + 1;
     if (usd.target) usd.tgt = usd.target[(size_t)level * a.B + reach];
@@ -254,22 +234,9 @@ __global__ __launch_bounds__(64 * W, (long_min_waves<R, SEC>())) void preissmann
             continue;
           }
           R h[M + 1], Q[M + 1];
-          if constexpr (kCo) load_nodes_co(a.hg, a.Qg, p, h, Q); else load_nodes(a.hg, a.Qg, g0, h, Q);
+          load_nodes_co(a.hg, a.Qg, p, h, Q);
           R hk_[kRecompute ? M + 1 : 1], Qk_[kRecompute ? M + 1 : 1];     // accepted state of level k at the lane's nodes
-          if constexpr (kRecompute) { if constexpr (kCo) load_nodes_co(a.hk, a.Qk, p, hk_, Qk_); else load_nodes(a.hk, a.Qk, g0, hk_, Qk_); }
-          if constexpr (kPf) {
-            // the lines of the next pass's state, requested a pass ahead (one dword per 64 bytes, results unused): when the
-            // pass gets there its loads find them in L2.  The four registers stay reserved until the loads have landed -
-            // the real loads above are younger than the last pass's requests and have been waited for.
-            asm volatile("" :: "v"(pf[0]), "v"(pf[1]), "v"(pf[2]), "v"(pf[3]));
-            int pn = p + 1;
-            if (pn >= P || pn * C > NC) pn = phase == 0 ? 0 : -1;
-            if (pn >= 0) {
-              const size_t o = base + min(pn * C + wave * (64 * M) + lane * 8, N - 1);
-              pf[0] = *reinterpret_cast<const volatile int *>(a.hg + o); pf[1] = *reinterpret_cast<const volatile int *>(a.Qg + o);
-              if constexpr (kRecompute) { pf[2] = *reinterpret_cast<const volatile int *>(a.hk + o); pf[3] = *reinterpret_cast<const volatile int *>(a.Qk + o); }
-            }
-          }
+          if constexpr (kRecompute) load_nodes_co(a.hk, a.Qk, p, hk_, Qk_);
           if (phase == 1) __syncthreads();          // every lane holds its nodes before any lane stores updated ones
 
           // ---- boundary rows (boundary.py:56-242) ----
@@ -447,11 +414,10 @@ __global__ __launch_bounds__(64 * W, (long_min_waves<R, SEC>())) void preissmann
             const bool last = step == a.n_steps - 1;
             R *const hh_p = a.hist_h ? a.hist_h + ((size_t)level * a.B + reach) * NS + g0 : nullptr;
             R *const hQ_p = a.hist_h ? a.hist_Q + ((size_t)level * a.B + reach) * NS + g0 : nullptr;
-            if constexpr (kCo) { if (last || kRecompute) store_nodes_co(a.hk, a.Qk, p, h, Q); }
+            if (last || kRecompute) store_nodes_co(a.hk, a.Qk, p, h, Q);
 #pragma unroll
             for (int j = 0; j < M; ++j) {
               if (g0 + j < N) {
-                if (!kCo && (last || kRecompute)) { a.hk[base + g0 + j] = h[j]; a.Qk[base + g0 + j] = Q[j]; }
                 if (hh_p) { hh_p[j] = h[j]; hQ_p[j] = Q[j]; }
               }
             }
@@ -468,15 +434,11 @@ __global__ __launch_bounds__(64 * W, (long_min_waves<R, SEC>())) void preissmann
             }
             if constexpr (!kRecompute) write_level_constants(p, g0, h, Q);
           }
-          if constexpr (kCo) {
+          {
             R hn[M], Qn[M];
 #pragma unroll
             for (int j = 0; j < M; ++j) { hn[j] = h[j] + dh[j]; Qn[j] = Q[j] + dQ[j]; }
             store_nodes_co(a.hg, a.Qg, p, hn, Qn);
-          } else {
-#pragma unroll
-          for (int j = 0; j < M; ++j)
-            if (g0 + j < N) { a.hg[base + g0 + j] = h[j] + dh[j]; a.Qg[base + g0 + j] = Q[j] + dQ[j]; }
           }
         }   // passes
 

@@ -19,19 +19,8 @@
 #include "fs_device.hpp"
 #include "fs_stage_table.hpp"
 
-#ifndef FS_POLY_INLINE
-#define FS_POLY_INLINE 1   // polyline walk inlined into the fold (+37 % on the polyline ensemble): a call inside the Newton loop spills its caller
-                           // (0 is an experiment switch: build it with -mllvm -enable-ipra=0, profiles/round3/polyline_calls.txt)
-#endif
-#if FS_POLY_INLINE
-#define FS_POLY_ATTR __forceinline__
-#else
-#define FS_POLY_ATTR __noinline__
-#endif
-
-#ifndef FS_POLY_PREFETCH
-#define FS_POLY_PREFETCH 1
-#endif
+// Every function here is in line, the polyline walk in the fold included (+37 % on the polyline ensemble: a call inside the
+// Newton loop spills its caller; out of line the build is rejected, tools/check_isa.py, profiles/round3/polyline_calls.txt).
 
 namespace fs {
 
@@ -118,7 +107,7 @@ template <typename R> __device__ __forceinline__ R strip_K(R A, R P, R n) {   //
 template <typename R> struct PolySums { R A0, P0, T0, A1, P1, A2, P2, Al, Pl, Am, Pm, Ar, Pr; };
 
 template <typename R>
-__device__ FS_POLY_ATTR PolySums<R> poly_sums_walk(const PolyNode<R> nd, const PolyView<R> v, R hw) {
+__device__ __forceinline__ PolySums<R> poly_sums_walk(const PolyNode<R> nd, const PolyView<R> v, R hw) {
   const R dh = R(1e-6);
   const int j0 = v.lo - (v.vl ? 1 : 0), j1 = v.hi + (v.vr ? 1 : 0);
   typedef const __attribute__((address_space(1))) R *GlobalR;          // (device memory: global loads, not flat ones)
@@ -129,17 +118,11 @@ __device__ FS_POLY_ATTR PolySums<R> poly_sums_walk(const PolyNode<R> nd, const P
   R A0 = 0, P0 = 0, T0 = 0, A1 = 0, P1 = 0, A2 = 0, P2 = 0, Td = 0;
   R Al = 0, Pl = 0, Am = 0, Pm = 0, Ar = 0, Pr = 0;
   R x0 = xa, z0 = Z(j0);
-#if FS_POLY_PREFETCH
   // the next vertex is requested one edge ahead: an edge is ~300 instructions, a vertex load an L2 round trip
   R xn = X(min(j0 + 1, j1)), zn = Z(min(j0 + 1, j1));
-#endif
   for (int j = j0; j < j1; ++j) {
-#if FS_POLY_PREFETCH
     const R x1 = xn, z1 = zn;
     xn = X(min(j + 2, j1)); zn = Z(min(j + 2, j1));
-#else
-    const R x1 = X(j + 1), z1 = Z(j + 1);
-#endif
     const R dx = x1 - x0, dz = z1 - z0;
     // full length: needed as soon as both ends are wet at the highest of the three stages
     const R len = (hw + dh > z0 && hw + dh > z1) ? fsqrt_len(dx * dx + dz * dz) : R(0);
@@ -185,7 +168,7 @@ __device__ __forceinline__ PolyEval<R> poly_finish(const PolyNode<R> &nd, const 
 }
 
 template <typename R>
-__device__ FS_POLY_ATTR PolyEval<R> poly_eval(const PolyNode<R> nd, const PolyView<R> v, R hw) {
+__device__ __forceinline__ PolyEval<R> poly_eval(const PolyNode<R> nd, const PolyView<R> v, R hw) {
   return poly_finish(nd, poly_sums_walk(nd, v, hw));
 }
 
@@ -240,7 +223,7 @@ __device__ __forceinline__ void poly_load_block(const R *tco, int cstride, int k
 
 // *kout (optional): the interval the stage was found in, -1 when the evaluation went back to the edge walk
 template <typename R>
-__device__ FS_POLY_ATTR PolyEval<R> poly_eval_whole(const PolyNode<R> nd, R hw, int *nsub, int *kout = nullptr) {
+__device__ __forceinline__ PolyEval<R> poly_eval_whole(const PolyNode<R> nd, R hw, int *nsub, int *kout = nullptr) {
   *nsub = -1;                                   // unknown: the caller counts the runs
   if (kout) *kout = -1;
   if (nd.tz == nullptr) return poly_eval_whole_walk(nd, hw);
@@ -297,7 +280,7 @@ __device__ __forceinline__ NodeTerms<R> poly_terms_tail(const PolyEval<R> &e, R 
 // *kout (optional): the table interval the evaluation used when a later one may start from it (one wetted run, no edge walk),
 // else -1
 template <typename R>
-__device__ FS_POLY_ATTR NodeTerms<R> node_terms_poly(const PolyNode<R> nd, R h, R Q, int *kout = nullptr, PolyBC<R> *bc = nullptr) {
+__device__ __forceinline__ NodeTerms<R> node_terms_poly(const PolyNode<R> nd, R h, R Q, int *kout = nullptr, PolyBC<R> *bc = nullptr) {
   const R hw = h + nd.zmin;
   int nsub = 0;
   const PolyEval<R> e = poly_eval_whole(nd, hw, &nsub, kout);
@@ -391,7 +374,7 @@ template <typename R> __device__ __forceinline__ BCRow<R> normal_depth_row_poly(
 }
 
 template <typename R>
-__device__ FS_POLY_ATTR BCRow<R> bc_normal_depth_poly(const PolyNode<R> nd, R S0, R bed, R h, R Q) {
+__device__ __forceinline__ BCRow<R> bc_normal_depth_poly(const PolyNode<R> nd, R S0, R bed, R h, R Q) {
   const R sg = S0 < R(0) ? R(-1) : R(1);
   const R rt = sqrt_(fabs_(S0));
   int ns_;

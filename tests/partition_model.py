@@ -84,7 +84,8 @@ def merge(X, Y):
 
 
 def continuant_close(seg, aU, bU, rU, dtype):
-    """The cross-wave step of the multi-wave kernels compiled without the conditioning monitor (fs_kernel.hpp, FS_XWAVE_CONT): the W
+    """The cross-wave step as the retired device experiment solved it ("Experiments built, measured and
+    retired"; profiles/round4/cross_wave_continuants.txt; the kernels fold the wave segments pairwise): the W
     remaining segments and the upstream row as ONE tridiagonal system in y = (p_0, x_0 .. x_{W-1}), x_w = m of segment w's last row,
     solved by forward and backward continuants with one reciprocal.  Returns (pL[W], mR[W]): the p of every segment's first row
     and the m of its last one - what the way down starts from."""

@@ -629,7 +629,7 @@ def test_fp64_near_singular_pivot_block_against_the_c_oracle():
 
 @pytest.mark.parametrize("N", [2, 64, 65, 66, 128, 129, 130, 257, 513])
 def test_trapezoid_reaches_that_fill_the_wave_exactly(N):
-    """General-section kernels take a lane's last node from its right neighbour (FS_SHARE_NODE); lane 63 has none
+    """General-section kernels take a lane's last node from its right neighbour (kShareNode, fs_kernel.hpp); lane 63 has none
     and evaluates the node itself when the reach fills the wave to the last cell (N - 1 = 64 M), one cell
     less leaves a padding cell there, one more moves to the next shape."""
     from fixture_batch import batch_from_problems

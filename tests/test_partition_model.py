@@ -36,9 +36,10 @@ def test_partition_solve_matches_superlu(name, m):
 @pytest.mark.parametrize("name", ["akbari", "gerd", "synthetic_rect_512", "c3_4096"])
 @pytest.mark.parametrize("W", [2, 4])
 def test_continuant_cross_wave_step_matches_superlu(name, W):
-    """The cross-wave step of the no-diagnostics multi-wave kernels (FS_XWAVE_CONT, fs_kernel.hpp): W wave segments + the upstream
-    row solved as one small tridiagonal system by continuants with one reciprocal, instead of the pairwise fold - same bar as the
-    fold above, on the same Jacobians and on the benchmark-size ones (c3_4096: 16 rows per lane, 4 waves: the flagship's layout)."""
+    """The cross-wave step as the retired device experiment solved it ("Experiments built, measured and
+    retired"; profiles/round4/cross_wave_continuants.txt): W wave segments + the upstream row as one small tridiagonal system by
+    continuants with one reciprocal, instead of the pairwise fold - the model's, same bar as the fold above, on the same Jacobians
+    and on the benchmark-size ones (c3_4096: 16 rows per lane, 4 waves: the flagship's layout)."""
     fx, meta = O.load_fixture(os.path.join(GOLDEN, name + ".npz"))
     p = O.problem_from_fixture(fx, meta, 0 if meta.get("B") else None)
     N = p.N
