@@ -17,11 +17,17 @@ def member_setup(n):
                  inflow_hyd_func=None, sim_duration=None)
 
 
-def rmse_curve(n_values):
-    solvers = [member_setup(float(n)) for n in n_values]          # host set-up per member (GVF profile depends on n)
-    lead, sections = solvers[0]
-    lead.channel.member_ics = np.stack([s.channel.initial_conditions for s, _ in solvers])
-    res = run_manning_ensemble(lead, n_values, tolerance=settings.tolerance)
+def rmse_curve(n_values, device_ic=False):
+    """device_ic=True: only the lead member is set up on the host (geometry, boundaries); every member's GVF profile - it depends
+    on n - is marched on the device."""
+    if device_ic:
+        lead, sections = member_setup(float(n_values[0]))
+        res = run_manning_ensemble(lead, n_values, tolerance=settings.tolerance, initial="gvf")
+    else:
+        solvers = [member_setup(float(n)) for n in n_values]          # host set-up per member (GVF profile depends on n)
+        lead, sections = solvers[0]
+        lead.channel.member_ics = np.stack([s.channel.initial_conditions for s, _ in solvers])
+        res = run_manning_ensemble(lead, n_values, tolerance=settings.tolerance)
     if np.any(res["status"] != 0):
         raise ValueError("ensemble member did not converge")
     z0 = sections[0].z_min

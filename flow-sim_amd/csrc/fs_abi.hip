@@ -24,6 +24,7 @@
 #include "fs_buffer.hpp"
 #include "fs_entries.hpp"
 #include "fs_host_pack.hpp"
+#include "fs_init_state.hpp"
 
 // ROCTx ranges around the phases a system trace should show (rocprofv3 --marker-trace): uploads, downloads, the step launch,
 // the post-processing launch.  Without a tool attached a push / pop is a few nanoseconds.
@@ -39,6 +40,13 @@ struct TraceRange {
 // the library: the kernels are instantiated in the fs_part_*.hip translation units (an FS_MINIMAL build instantiates its few where the
 // table below takes their address)
 FS_ACTIVE_LIST(FS_DECLARE)
+#else
+// an experiment build is this translation unit alone, with a few step kernels: it has no initial-condition kernels (fs_part_init.hip),
+// and fs_batch_init_state says so
+namespace fs {
+bool launch_init_state(int, const InitArgs<double> &, hipStream_t) { return false; }
+bool launch_init_state(int, const InitArgs<float> &, hipStream_t) { return false; }
+}  // namespace fs
 #endif
 
 namespace {
@@ -218,6 +226,8 @@ struct fs_batch : Timeline {
   fs::DeviceBuffer open_dev;            // int32: fs_batch_iterate's count of the reaches still iterating
   fs::PinnedBuffer open_pin;
   fs::DeviceBuffer derived[8];          // device results of the last derive call, kept and reused (grown, never shrunk)
+  fs::DeviceBuffer ic_in[4];            // fs_batch_init_state's inputs in the batch's type: flow, depth_us, depth_ds [B], bed_slope [N] or [B][N]
+  fs::DeviceBuffer ic_info;             // int32 [2][B]: what fs_batch_init_state reports per reach (allocated on first use)
   fs::DeviceBuffer dbg;
   Staging stage;                        // pinned chunks for large host <-> device transfers
   fs::DeviceBuffer kc_scratch;          // long reaches: level constants [B][4][passes * 64 W M]
@@ -335,6 +345,14 @@ __global__ void refresh_level0_downstream(const R *hk, const R *Qk, const int32_
   if (r >= B) return;
   const size_t last = (reach_nodes ? (size_t)reach_nodes[r] : N) - 1;
   hydro[2 * B + r] = hk[r * N + last]; hydro[3 * B + r] = Qk[r * N + last];
+}
+
+// ... and the upstream half, from node 0 (fs_batch_init_state: the state was computed on the device)
+template <typename R>
+__global__ void refresh_level0_upstream(const R *hk, const R *Qk, R *hydro, size_t B, size_t N) {
+  const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= B) return;
+  hydro[r] = hk[r * N]; hydro[B + r] = Qk[r * N];
 }
 
 // reaches whose open level still iterates (fs_batch_iterate): not yet accepted and not failed
@@ -485,6 +503,18 @@ int fill_side_kinds(fs_batch *b, int side, int kind) {
   const size_t B = b->d.n_reaches;
   const std::vector<int32_t> same(B, kind);
   HIP_TRY(hipMemcpy(b->reach_kinds.get<int32_t>() + (size_t)side * B, same.data(), B * 4, hipMemcpyHostToDevice));
+  return 0;
+}
+
+// the state in hk / Qk becomes the Newton start vector and, where a history is kept, its level 0 (solver.py:61-63)
+int spread_level0(fs_batch *b) {
+  const size_t bytes = (size_t)b->d.n_reaches * b->d.n_nodes * b->esz;
+  HIP_TRY(hipMemcpyAsync(b->hg.get(), b->hk.get(), bytes, hipMemcpyDeviceToDevice, b->stream));
+  HIP_TRY(hipMemcpyAsync(b->Qg.get(), b->Qk.get(), bytes, hipMemcpyDeviceToDevice, b->stream));
+  if (b->hist_h) {
+    HIP_TRY(hipMemcpyAsync(b->hist_h.get(), b->hk.get(), bytes, hipMemcpyDeviceToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(b->hist_Q.get(), b->Qk.get(), bytes, hipMemcpyDeviceToDevice, b->stream));
+  }
   return 0;
 }
 
@@ -820,12 +850,7 @@ int fs_batch_set_state(fs_batch *b, const double *h, const double *Q) {
   const size_t B = b->d.n_reaches, N = b->d.n_nodes;
   // each array crosses the bus once; the Newton start vector and level 0 of the history are device-to-device copies
   if (upload(b, b->hk, h, B * N) || upload(b, b->Qk, Q, B * N)) return -1;
-  HIP_TRY(hipMemcpyAsync(b->hg.get(), b->hk.get(), B * N * b->esz, hipMemcpyDeviceToDevice, b->stream));
-  HIP_TRY(hipMemcpyAsync(b->Qg.get(), b->Qk.get(), B * N * b->esz, hipMemcpyDeviceToDevice, b->stream));
-  if (b->hist_h) {   // level 0 of the history = initial conditions (solver.py:61-63)
-    HIP_TRY(hipMemcpyAsync(b->hist_h.get(), b->hk.get(), B * N * b->esz, hipMemcpyDeviceToDevice, b->stream));
-    HIP_TRY(hipMemcpyAsync(b->hist_Q.get(), b->Qk.get(), B * N * b->esz, hipMemcpyDeviceToDevice, b->stream));
-  }
+  if (spread_level0(b)) return -1;
   std::vector<double> row(4 * B);
   for (size_t r = 0; r < B; ++r) {
     const size_t last = (b->reach_nodes_host.empty() ? N : (size_t)b->reach_nodes_host[r]) - 1;     // the reach's own last node, not the caller's padding
@@ -850,6 +875,69 @@ int fs_batch_set_state_uniform(fs_batch *b, const double *h, const double *Q) {
   HIP_TRY(hipGetLastError());
   if (begin_at_level0(b)) return -1;
   HIP_TRY(hipStreamSynchronize(b->stream));      // (dh and dQ go when this returns)
+  return 0;
+}
+
+int fs_batch_init_state(fs_batch *b, int32_t method, const double *flow, const double *depth_us, const double *depth_ds,
+                        const double *bed_slope, int32_t bed_slope_per_reach, int32_t *info) {
+  if (!b || !flow) return fail("fs_batch_init_state: null argument");
+  if (method != FS_IC_LINEAR && method != FS_IC_GVF && method != FS_IC_STEADY)
+    return fail("fs_batch_init_state: method must be FS_IC_LINEAR, FS_IC_GVF or FS_IC_STEADY");
+  if (!b->have_scheme || !b->have_geo)
+    return fail(std::string("fs_batch_init_state: ") + (!b->have_scheme ? (!b->have_geo ? "the scheme (fs_batch_set_scheme: dx) and the geometry" : "the scheme (fs_batch_set_scheme: dx)") : "the geometry") +
+                " must be set first");
+  if (method != FS_IC_STEADY && !depth_ds) return fail("fs_batch_init_state: depth_ds is needed by FS_IC_LINEAR and FS_IC_GVF");
+  if (method == FS_IC_LINEAR && !depth_us) return fail("fs_batch_init_state: depth_us is needed by FS_IC_LINEAR");
+  const bool uniform = b->d.section_mode == FS_SEC_RECT_UNIFORM || b->d.section_mode == FS_SEC_TRAP_UNIFORM;
+  const size_t B = b->d.n_reaches, N = b->d.n_nodes;
+  if (method == FS_IC_STEADY) {
+    if (!bed_slope && !uniform) return fail("fs_batch_init_state: FS_IC_STEADY needs bed_slope in section modes FS_SEC_TABLE and FS_SEC_IRREGULAR");
+    if (bed_slope)        // the reference's None (channel.py:299-300), at a reach's own nodes
+      for (size_t r = 0; r < (bed_slope_per_reach ? B : 1); ++r) {
+        size_t n_r = N;
+        if (bed_slope_per_reach && !b->reach_nodes_host.empty()) n_r = (size_t)b->reach_nodes_host[r];
+        for (size_t i = 0; i < n_r; ++i)
+          if (std::isnan(bed_slope[r * N + i])) return fail("fs_batch_init_state: Bed slope must be defined.");
+      }
+  }
+  FS_ON_DEVICE(b);
+  // (the batch keeps the inputs: the kernels read them after this call has returned)
+  fs::DeviceBuffer &d_flow = b->ic_in[0], &d_us = b->ic_in[1], &d_ds = b->ic_in[2], &d_slope = b->ic_in[3];
+  HIP_TRY(hipStreamSynchronize(b->stream));      // an earlier call's kernels are through with them
+  if (method != FS_IC_LINEAR) d_us.reset();      // (what this method does not read must read as "not given")
+  if (method == FS_IC_STEADY) d_ds.reset();
+  if (method != FS_IC_STEADY || !bed_slope) d_slope.reset();
+  if (upload(b, d_flow, flow, B)) return -1;
+  if (method == FS_IC_LINEAR && upload(b, d_us, depth_us, B)) return -1;
+  if (method != FS_IC_STEADY && upload(b, d_ds, depth_ds, B)) return -1;
+  if (method == FS_IC_STEADY && bed_slope && upload(b, d_slope, bed_slope, bed_slope_per_reach ? B * N : N)) return -1;
+  HIP_TRY(b->ic_info.ensure(2 * B * sizeof(int32_t)));
+  HIP_TRY(hipMemsetAsync(b->ic_info.get(), 0, B * sizeof(int32_t), b->stream));
+  HIP_TRY(hipMemsetAsync(b->ic_info.get<int32_t>() + B, 0xff, B * sizeof(int32_t), b->stream));
+  {
+    TraceRange range_("flowsim:init_state");
+    const bool launched = with_real(b, [&](auto real) {
+      using R = decltype(real);
+      fs::InitArgs<R> p;
+      fill_args(b, 0, p.k);
+      p.method = method; p.flow = d_flow.get<const R>(); p.depth_us = d_us.get<const R>(); p.depth_ds = d_ds.get<const R>();
+      p.bed_slope = d_slope.get<const R>(); p.bed_slope_per_reach = bed_slope_per_reach; p.info = b->ic_info.get<int32_t>();
+      const bool ok = fs::launch_init_state(b->d.section_mode, p, b->stream);
+      if (ok) {      // the level-0 hydrograph row: node 0 and each reach's own last node
+        hipLaunchKernelGGL((refresh_level0_upstream<R>), grid_256(B), dim3(256), 0, b->stream, b->hk.get<const R>(), b->Qk.get<const R>(), b->hydro.get<R>(), B, N);
+        hipLaunchKernelGGL((refresh_level0_downstream<R>), grid_256(B), dim3(256), 0, b->stream, b->hk.get<const R>(), b->Qk.get<const R>(),
+                           b->reach_nodes.get<const int32_t>(), b->hydro.get<R>(), B, N);
+      }
+      return ok;
+    });
+    if (!launched) return fail("fs_batch_init_state: this build has no initial-condition kernel for this section mode and dtype");
+    HIP_TRY(hipGetLastError());
+  }
+  if (spread_level0(b) || begin_at_level0(b)) return -1;
+  if (info) {
+    HIP_TRY(hipMemcpyAsync(info, b->ic_info.get(), 2 * B * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+  }
   return 0;
 }
 

@@ -26,6 +26,8 @@ SC_NAMES = ("min_stage", "Y_min", "Y_max", "bed_level", "surface_area", "alpha",
 UPSTREAM, DOWNSTREAM = 0, 1
 OK, MAX_ITER, NAN, STORAGE_RANGE, ILL_CONDITIONED, TEAM_STALL = 0, 1, 2, 3, 4, 5
 FLAG_HISTORY, FLAG_TRACE, FLAG_MONITOR = 1, 2, 4
+IC_LINEAR, IC_GVF, IC_STEADY = 0, 1, 2
+IC_SUPERCRITICAL, IC_CLAMPED, IC_FLOORED, IC_NO_ROOT = 1, 2, 4, 8
 TRACE_CAP = 64
 DERIVE_ALL = 255
 ABI_VERSION = 3
@@ -62,6 +64,7 @@ SIGNATURES = {
     "fs_batch_set_bc_per_reach_wide": (C.c_int, [_P, C.c_int32, _I, _D, C.c_int32, _D]),
     "fs_batch_set_state": (C.c_int, [_P, _D, _D]),
     "fs_batch_set_state_uniform": (C.c_int, [_P, _D, _D]),
+    "fs_batch_init_state": (C.c_int, [_P, C.c_int32, _D, _D, _D, _D, C.c_int32, _I]),
     "fs_batch_step": (C.c_int, [_P, C.c_int32]),
     "fs_batch_sync": (C.c_int, [_P]),
     "fs_batch_iterate": (C.c_int, [_P, _I]),

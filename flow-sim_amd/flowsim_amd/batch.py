@@ -241,6 +241,37 @@ class PreissmannBatch:
         Q = np.ascontiguousarray(np.broadcast_to(np.asarray(Q, dtype=np.float64), (self.B,)))
         A.check(self._lib.fs_batch_set_state_uniform(self._h, _dptr(h), _dptr(Q)), "set_state_uniform")
 
+    IC_METHODS = {"linear": A.IC_LINEAR, "GVF_equation": A.IC_GVF, "steady-state": A.IC_STEADY}      # Channel's interpolation_method names
+
+    def init_state(self, method, flow, depth_ds=None, depth_us=None, bed_slope=None, strict=True):
+        """Channel.initialize_conditions (channel.py:107-138) on the device, for every reach at once, on the geometry the batch
+        holds: method 'linear' (depth_us, depth_ds), 'GVF_equation' (depth_ds: the backwater march) or 'steady-state' (normal depth;
+        bed_slope [N] or [B, N]: the nodes' interpolated CrossSection.bed_slope, None in the uniform modes).  flow, depth_*: scalar
+        or [B].  The batch is then where set_state(*state) would leave it.
+
+        Returns dict(flags[B], node[B]): the IC_* bits of each reach and the node of its first supercritical evaluation (-1).
+        strict=True raises the reference's RuntimeError for the first reach whose march met Fr > 1 (its depth is NaN upstream
+        of that node; the other reaches are complete)."""
+        per = lambda v: None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (self.B,)))
+        flow, depth_ds, depth_us = per(flow), per(depth_ds), per(depth_us)
+        per_reach = 0
+        if bed_slope is not None:
+            # (None entries are the reference's undefined slope: NaN, which the library refuses as the reference does)
+            bed_slope = np.ascontiguousarray(np.array(bed_slope, dtype=np.float64))
+            assert bed_slope.shape in ((self.N,), (self.B, self.N))
+            per_reach = int(bed_slope.ndim == 2)
+        info = np.empty((2, self.B), dtype=np.int32)
+        opt = lambda a: None if a is None else _dptr(a)
+        A.check(self._lib.fs_batch_init_state(self._h, self.IC_METHODS[method], _dptr(flow), opt(depth_us), opt(depth_ds), opt(bed_slope),
+                                              per_reach, info.ctypes.data_as(A._I)), "init_state")
+        out = dict(flags=info[0].copy(), node=info[1].copy())
+        bad = np.flatnonzero(out["flags"] & A.IC_SUPERCRITICAL)
+        if strict and len(bad):
+            r = int(bad[0])
+            raise RuntimeError(f"GVF Error: Flow became supercritical (Fr>1) at node {int(out['node'][r])} of reach {r}. "
+                               "Downstream boundary control is not valid for this Q.")
+        return out
+
     # -- the hot path ---------------------------------------------------------------------
     def step(self, n_steps: int = 1, sync: bool = True):
         A.check(self._lib.fs_batch_step(self._h, int(n_steps)), "step")

@@ -8,13 +8,18 @@ from .batch import PreissmannBatch
 from .hydromodel.preissmann import boundary_to_spec
 
 
-def run_manning_ensemble(solver, n_main_values, tolerance=1e-4, max_iter=100, dtype="f64", device=0, monitor=True):
+def run_manning_ensemble(solver, n_main_values, tolerance=1e-4, max_iter=100, dtype="f64", device=0, monitor=True, initial="host"):
     """`solver`: a set-up (not yet run) PreissmannSolver whose channel provides geometry, boundaries
     and initial conditions; the initial conditions are shared by all members (the reference's
     members start from the same downstream level and the same flow; their GVF profiles differ
     with n - pass `initial_conditions[B, N, 2]` through `solver.channel.member_ics` to override).
 
+    initial="gvf": every member starts from its own backwater profile instead, marched on the device from the channel's
+    downstream depth with the member's n (PreissmannBatch.init_state; channel.py:307-378) - no per-member set-up on the host.
+
     Returns dict(hydrographs[nt, 4, B], iterations[nt, B], status[B])."""
+    if initial not in ("host", "gvf"):
+        raise ValueError("initial must be 'host' or 'gvf'")
     ch = solver.channel
     n_vals = np.ascontiguousarray(n_main_values, dtype=np.float64)
     B, N, nt = len(n_vals), solver.number_of_nodes, solver.number_of_time_levels
@@ -24,7 +29,9 @@ def run_manning_ensemble(solver, n_main_values, tolerance=1e-4, max_iter=100, dt
         b.set_geometry_table(ch.node_geometry, n_main_override=n_vals)
         b.set_boundary(A.UPSTREAM, boundary_to_spec(ch.upstream_boundary, max(nt, 2), solver.time_step))
         b.set_boundary(A.DOWNSTREAM, boundary_to_spec(ch.downstream_boundary, max(nt, 2), solver.time_step))
-        if ics is None:
+        if initial == "gvf":
+            b.init_state("GVF_equation", ch.initial_flow_rate, depth_ds=ch.downstream_boundary.initial_depth)
+        elif ics is None:
             b.set_state(ch.initial_conditions[:, 0], ch.initial_conditions[:, 1])
         else:
             b.set_state(ics[:, :, 0], ics[:, :, 1])

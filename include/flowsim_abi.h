@@ -232,6 +232,25 @@ int fs_batch_set_state(fs_batch *b, const double *h, const double *Q);
  * the device (avoids staging B*N host values for large batches). */
 int fs_batch_set_state_uniform(fs_batch *b, const double *h, const double *Q);
 
+/* Channel.initialize_conditions (channel.py:107-138) on the device, on the geometry the batch holds: call it after the scheme, the
+ * geometry and, where used, fs_batch_set_reach_nodes / fs_batch_set_reach_scheme (a reach's spatial step is its own dx).  flow[B] is
+ * each reach's flow at every node.
+ *   FS_IC_LINEAR  depth_us[B], depth_ds[B]: h_i = h_us + (h_ds - h_us) x_i / L (channel.py:380-390)
+ *   FS_IC_GVF     depth_ds[B]: the backwater march from the downstream depth (channel.py:307-378)
+ *   FS_IC_STEADY  normal depth at every node (channel.py:296-305); bed_slope: the nodes' interpolated CrossSection.bed_slope, [N]
+ *                 shared or [B][N] (bed_slope_per_reach != 0); NULL in the two uniform modes: (z_us - z_ds) / ((n_r - 1) dx_r),
+ *                 channel.py:286.  A NaN entry is the reference's None: "Bed slope must be defined.", the call fails.
+ * The batch is then in the state fs_batch_set_state leaves when given the same values (nodes beyond a reach's own last one repeat
+ * it).  A reach whose march met Fr > 1 keeps NaN depth at the nodes it did not reach: a later step reports FS_NAN for it.
+ * info: NULL, or [2][B]: the FS_IC_* flag bits of each reach, then the node of its first supercritical evaluation (else -1).  The
+ * call synchronises only when info is given. */
+enum { FS_IC_LINEAR = 0, FS_IC_GVF = 1, FS_IC_STEADY = 2 };
+/* bits of info[0][r]: the march stopped at Fr > 1; 1 - Fr^2 was replaced by 0.01; a depth <= 0 was set to 0.01; brentq found no
+ * bracket (the result is one of the reference's fall-backs, cross_section.py:195-202) */
+enum { FS_IC_SUPERCRITICAL = 1, FS_IC_CLAMPED = 2, FS_IC_FLOORED = 4, FS_IC_NO_ROOT = 8 };
+int fs_batch_init_state(fs_batch *b, int32_t method, const double *flow, const double *depth_us, const double *depth_ds,
+                        const double *bed_slope, int32_t bed_slope_per_reach, int32_t *info);
+
 /* THE HOT PATH: advances every reach by n_steps time levels (preissmann.py:108-161).  Results
  * stay on the device: boundary hydrographs, Newton counts, status, (history).  Asynchronous. */
 int fs_batch_step(fs_batch *b, int32_t n_steps);
