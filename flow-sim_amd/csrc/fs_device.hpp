@@ -70,6 +70,24 @@ __device__ __forceinline__ float rcbrt_pos(float x) {
   return __builtin_fmaf(y * (1.0f / 3.0f), e, y);
 }
 
+// x^(-2/3) for x > 0, which is what the conveyance wants (K = A R^(2/3) / n): the same seed y, but the correction goes onto
+// s = y^2 directly - s (1 - e)^(-2/3) = s (1 + 2e/3 + 5 e^2/9 + O(e^3)) with the same e = 1 - x y^3, the neglected term
+// (40/81) e^3 < 2e-20 - instead of onto y, which the caller then squares: one instruction fewer per node
+__device__ __forceinline__ double rcbrt2_pos(double x) {
+  const float xf = (float)x;
+  const double y = (double)__builtin_amdgcn_exp2f(__builtin_amdgcn_logf(xf) * (-1.0f / 3.0f));
+  const double s = y * y;
+  const double e = __builtin_fma(-(x * s), y, 1.0);
+  const double p = __builtin_fma(e, 5.0 / 9.0, 2.0 / 3.0);
+  return __builtin_fma(s * e, p, s);
+}
+__device__ __forceinline__ float rcbrt2_pos(float x) {
+  float y = __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(x) * (-1.0f / 3.0f));
+  float s = y * y;
+  float e = __builtin_fmaf(-(x * s), y, 1.0f);
+  return __builtin_fmaf(s * (2.0f / 3.0f), e, s);
+}
+
 // A value written once per Newton iteration and read once much later (the per-node elimination records).  The register
 // allocator places it: forcing these into AGPRs (v_accvgpr_write / read through the "a" inline-asm register class) was measured
 // and lost against its choice.
@@ -148,7 +166,9 @@ template <typename R> struct NodeTerms {
   R Se;   // Sf + Sc                             (channel.py:53-69)
   R eAT;  // (dSe/dA in the reference's mixed convention) * dA/dh / T  (channel.py:71-87; the momentum row's dh entries are
           // used divided by the node's top width, below)
-  R eQ;   // dSe/dQ                              (channel.py:89-105)
+  R eQh;  // dSe/dQ / kEQScale of the section's Geometry (channel.py:89-105): the closed-form fast paths (node_terms_rect / _trap,
+          // kEQScale = 2) hand over HALF of it, |Q| / K^2, the general and polyline paths (kEQScale = 1) dSe/dQ itself; the only
+          // reader is the fold, whose constant hx carries kEQScale.  Anyone else who wants dSe/dQ multiplies by Geo::kEQScale
   R v;    // Q / A
   R rT;   // 1 / T: the continuity row's dh coefficient is T/(2dt) on both nodes (preissmann.py:431-447), its reciprocal scales
 };        // the node's momentum entries into the characteristic-like unknowns of the solve (below)
@@ -179,15 +199,15 @@ __device__ __forceinline__ NodeTerms<R> node_terms_rect(R b, R rb, R n, R h, R Q
   const R rP = r * h, rh = r * P;
   const R Rh = A * rP;                   // hydraulic radius
   const R rA = rh * rb;                  // 1/A
-  const R y = rcbrt_pos(Rh);             // R^(-1/3);  K = A R^(2/3)/n  ->  1/K^2 = (n y^2 / A)^2
-  const R nk = n * rA * (y * y);
+  const R y2 = rcbrt2_pos(Rh);           // R^(-2/3);  K = A R^(2/3)/n  ->  1/K^2 = (n R^(-2/3) / A)^2
+  const R nk = n * rA * y2;
   const R iK2 = nk * nk;
   const R aQ = fabs_(Q);
   t.A = A;
   t.T = b;
   const R w = aQ * iK2;
   t.Se = Q * w;                                                    // hydraulics.py:57
-  t.eQ = w + w;                                                    // hydraulics.py:92
+  t.eQh = w;                                                       // hydraulics.py:92, halved (NodeTerms)
   t.eAT = t.Se * fma_(R(-4.0 / 3.0) * b, rP, R(-2)) * rA;          // hydraulics.py:75 (times T, over T)
   t.v = Q * rA;
   t.rT = rb;
@@ -208,15 +228,15 @@ __device__ __forceinline__ NodeTerms<R> node_terms_trap(R b, R m, R sm2, R n, R 
   const R r3 = frcp(AP * T);
   const R rA = r3 * (P * T), rP = r3 * (A * T), rT = r3 * AP;
   const R Rh = A * rP;
-  const R y = rcbrt_pos(Rh);
-  const R nk = n * rA * (y * y);
+  const R y2 = rcbrt2_pos(Rh);
+  const R nk = n * rA * y2;
   const R iK2 = nk * nk;
   const R aQ = fabs_(Q);
   t.A = A;
   t.T = T;
   const R w = aQ * iK2;
   t.Se = Q * w;
-  t.eQ = w + w;
+  t.eQh = w;                                                       // halved (NodeTerms)
   const R f2 = fma_(R(-4.0 / 3.0), fma_(-(sm2 * A * rT), rP, R(1)), R(-2));      // -2 (1 + (2/3)(...))
   t.eAT = t.Se * f2 * rA;
   t.v = Q * rA;
@@ -369,7 +389,7 @@ __device__ __forceinline__ NodeTerms<R> node_terms_general(const SecParams<R> s,
   R dSeA = R(-2) * Sf * g.dKdA_K;        // per unit area
   R Se = Sf, eQ = R(2) * aQ * iK2;
   add_curvature(s.curv, g.A, g.rA, g.T, g.rT, g.T, g.neq, g.y13, g.dRdA, h, Q, Se, dSeA, eQ);
-  t.A = g.A; t.T = g.T; t.Se = Se; t.eAT = dSeA; t.eQ = eQ; t.v = Q * g.rA;    // (dSeA T) / T
+  t.A = g.A; t.T = g.T; t.Se = Se; t.eAT = dSeA; t.eQh = eQ; t.v = Q * g.rA;    // (dSeA T) / T
   t.rT = g.rT;
   return t;
 }

@@ -145,6 +145,7 @@ __device__ __forceinline__ BCDesc<R> pinned(const BCDesc<R> &bc) {
 
 template <typename R> struct Geometry<R, FS_SEC_RECT_UNIFORM> {
   static constexpr bool kConstT = true;      // dA/dh = b everywhere: no per-node top width to keep
+  static constexpr int kEQScale = 2;         // terms().eQh is half of dSe/dQ (node_terms_rect): the fold's hx carries the 2
   R b, rb, n, rn, z_us, z_ds, inv_nm1, dz;
   __device__ __forceinline__ void init(const KernelArgs<R> &a, int reach, int n_nodes) {
     b = a.geo_uniform[(size_t)FS_RU_WIDTH * a.B + reach];
@@ -184,6 +185,7 @@ template <typename R> struct Geometry<R, FS_SEC_RECT_UNIFORM> {
 
 template <typename R> struct Geometry<R, FS_SEC_TRAP_UNIFORM> {
   static constexpr bool kConstT = false;
+  static constexpr int kEQScale = 2;         // (node_terms_trap: as the rectangle)
   R b, m, sm2, n, rn, z_us, z_ds, inv_nm1, dz;
   __device__ __forceinline__ void init(const KernelArgs<R> &a, int reach, int n_nodes) {
     b = a.geo_uniform[(size_t)FS_RU_WIDTH * a.B + reach];
@@ -220,6 +222,7 @@ template <typename R> struct Geometry<R, FS_SEC_TRAP_UNIFORM> {
 
 template <typename R> struct Geometry<R, FS_SEC_TABLE> {
   static constexpr bool kConstT = false;
+  static constexpr int kEQScale = 1;         // node_terms_general hands over dSe/dQ itself in eQh (the curvature term is added to it)
   const R *tab;
   int N;
   R n_over, rn_over, k15_over;      // per-reach main-channel Manning n (ensembles), its reciprocal and its -1.5 power
@@ -267,6 +270,7 @@ __device__ __forceinline__ NodeTerms<R> node_terms_general_call(const SecParams<
 
 template <typename R> struct Geometry<R, FS_SEC_IRREGULAR> {
   static constexpr bool kConstT = false;
+  static constexpr int kEQScale = 1;
   Geometry<R, FS_SEC_TABLE> tb;
   const R *px, *pz, *plim, *ptz;
   const int32_t *pn;
@@ -536,7 +540,7 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
   R i2c = R(0.5) / cq;
   R kap = r2dt * i2c;
   R dtcq = dt * cq;
-  R hx = hth * i2c;                           // (theta/2) / (2cq)
+  R hx = R(Geo::kEQScale) * (hth * i2c);      // (theta/2) / (2cq), times the 2 that the fast paths' eQ leaves out
   R ghth = g * hth;                           // the level constant kc2 carries the factor g as well: g Abar in one fma
   const R ghthk = g * hthk;
   R ghdt = g * hth * dt;
@@ -547,7 +551,9 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
 
   // level-k constants of the 4-point stencil from the accepted state (h, Q) of level k:
   //   C = [sumA]/(2dt) + cq*dQ                 + kc0
-  //   M = [sumQ]/(2dt) + cq*d(Q^2/A)           + kc1 + (g*hth*sumA + kc2)*(cq*dY + hth*sumSe + kc3)     (kc2 carries g)
+  //   M = [sumQ]/(2dt) + cq*d(Q^2/A)           + kc1 + (g*hth*sumA + kc2)*(cq*dh + hth*sumSe + kc3)     (kc2 carries g)
+  // kc3 = cqk*(dz + dh_k) + hthk*sumSe_k + cq*dz: the bed step's share of the level-(k+1) water-surface slope cq*dY = cq*(dz + dh) is a constant of
+  // the cell and rides in kc3 (two instructions per cell and iteration fewer; the table kernels also lose the fold's two bed loads per cell)
   // Node s0 + M is lane + 1's node s0 (both lanes hold bitwise equal copies of its unknowns): with one wave per reach the
   // neighbour's terms arrive by a wave rotate.  Lane 63 receives lane 0's, which only a padding row or the downstream boundary
   // row ever looks at (and discards): the lane grid holds N rows, so lane 63's last row is never a cell, and its node M is a
@@ -560,7 +566,7 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
   auto last_node_terms = [&](const NodeTerms<R> &first) __attribute__((always_inline)) {
     auto rol = [](R v) { return dpp_mov<0x134>(v); };     // wave_rol:1
     NodeTerms<R> r;
-    r.A = rol(first.A); r.T = rol(first.T); r.Se = rol(first.Se); r.eAT = rol(first.eAT); r.eQ = rol(first.eQ); r.v = rol(first.v);
+    r.A = rol(first.A); r.T = rol(first.T); r.Se = rol(first.Se); r.eAT = rol(first.eAT); r.eQh = rol(first.eQh); r.v = rol(first.v);
     r.rT = rol(first.rT);
     return r;
   };
@@ -577,7 +583,8 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
       sm.kc[0][c][t] = fma_(cqk, QQ[c + 1] - QQ[c], -(sumA * r2dt));
       sm.kc[1][c][t] = fma_(cqk, fma_(QQ[c + 1], Rn.v, -(QQ[c] * L.v)), -((QQ[c + 1] + QQ[c]) * r2dt));
       sm.kc[2][c][t] = ghthk * sumA;
-      sm.kc[3][c][t] = fma_(cqk, geo.bed_step(s0 + c) + (hh[c + 1] - hh[c]), hthk * (L.Se + Rn.Se));
+      const R dzc = geo.bed_step(s0 + c);
+      sm.kc[3][c][t] = fma_(cqk, dzc + (hh[c + 1] - hh[c]), fma_(hthk, L.Se + Rn.Se, cq * dzc));
       L = Rn;
     }
   };
@@ -594,7 +601,8 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
         sm.kc[0][c][t] = fma_(cqk, QQ[c + 1] - QQ[c], -(sumA * r2dt));
         sm.kc[1][c][t] = fma_(cqk, fma_(QQ[c + 1], v1, -(QQ[c] * v0)), -((QQ[c + 1] + QQ[c]) * r2dt));
         sm.kc[2][c][t] = ghthk * sumA;
-        sm.kc[3][c][t] = fma_(cqk, geo.bed_step(s0 + c) + (hh[c + 1] - hh[c]), hthk * (Se0 + Se1));
+        const R dzc = geo.bed_step(s0 + c);
+        sm.kc[3][c][t] = fma_(cqk, dzc + (hh[c + 1] - hh[c]), fma_(hthk, Se0 + Se1, cq * dzc));
         A0 = A1; Se0 = Se1; v0 = v1;
       }
     }
@@ -800,19 +808,23 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
             const R sumA = L.A + Rn.A;
             const R Cres = sumA * r2dt + cq * (Q[c + 1] - Q[c]) + k0;                            // :220-249
             const R gA = fma_(ghth, sumA, k2);                                                    // g Abar
-            const R S = cq * (geo.bed_step(s0 + c) + (h[c + 1] - h[c])) + hth * (L.Se + Rn.Se) + k3;
+            const R S = fma_(cq, h[c + 1] - h[c], fma_(hth, L.Se + Rn.Se, k3));                  // (cq dz: in k3)
             const R Mres = (Q[c + 1] + Q[c]) * r2dt + cq * (Q[c + 1] * Rn.v - Q[c] * L.v) + k1 + gA * S;   // :251-301
             // momentum entries (preissmann.py:496-733) scaled by 1/(2t) of their node (dh) and 1/(2cq) (dQ):
             //   X0 = pm0 dt/T0, Y0 = pm1/(2cq), X1 = sm0 dt/T1, Y1 = sm1/(2cq)
             const R gAdt = gA * dt, gAx = gA * hx, sdt = ghdt * S;
             const R X0 = fma_(gAdt, fma_(hth, L.eAT, -(cq * L.rT)), fma_(dtcq, L.v * L.v, sdt));      // :558-612
             const R X1 = fma_(gAdt, fma_(hth, Rn.eAT, cq * Rn.rT), fma_(-dtcq, Rn.v * Rn.v, sdt));    // :496-550
-            const R Y0 = fma_(gAx, L.eQ, kap - L.v);                                                 // :677-733
-            const R Y1 = fma_(gAx, Rn.eQ, kap + Rn.v);                                               // :619-675
+            const R Y0 = fma_(gAx, L.eQh, kap - L.v);                                                 // :677-733
+            const R Y1 = fma_(gAx, Rn.eQh, kap + Rn.v);                                               // :619-675
             const R ga = X1 + Y1;
             row.al = X0 + Y0; row.D = (X0 - Y0) - ga; row.de = X1 - Y1;
             row.rho0 = fma_(ga, Cres, -Mres);             // qm - ga rc with qm = -Mres, rc = -Cres
             row.rc = -Cres;
+            // (Round 5 measured the norm as two fmas into the running sum where the row is a cell in every lane, and Mres as nested
+            // fmas: the 62 fp64 instructions they save per iteration came back as AGPR moves and copies - 3 196.3 issue slots with them,
+            // 3 188.3 without, 364 registers against 362 - and the flagship ran 0.3 % SLOWER with the two than without; DESIGN.md
+            // section 10, profiles/round5/fold_diet.txt.  Both stay as they were.)
             R r2 = fma_(Cres, Cres, Mres * Mres);
             if constexpr (kTail) {
               if (c == TAIL) {                 // the boundary row, in the one lane that owns node N - 1 (its residual was added in step 1)

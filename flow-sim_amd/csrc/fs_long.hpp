@@ -91,7 +91,7 @@ __global__ __launch_bounds__(64 * W, (long_min_waves<R, SEC>())) void preissmann
   const R tol_r = own_scheme ? a.reach_scheme[(size_t)3 * a.B + reach] : a.tol;       // the reach's own run(tolerance, max_iter)
   const int max_it = own_scheme ? (int)a.reach_scheme[(size_t)4 * a.B + reach] : a.max_iter;
   const R r2dt = R(1) / (R(2) * dt), cq = th / dx_, cqk = (R(1) - th) / dx_, hth = R(0.5) * th, hthk = R(0.5) * (R(1) - th);
-  const R g = R(kG), i2c = R(0.5) / cq, kap = r2dt * i2c, dtcq = dt * cq, hx = hth * i2c, ghth = g * hth, ghthk = g * hthk, ghdt = g * hth * dt;
+  const R g = R(kG), i2c = R(0.5) / cq, kap = r2dt * i2c, dtcq = dt * cq, hx = R(Geo::kEQScale) * (hth * i2c), ghth = g * hth, ghthk = g * hthk, ghdt = g * hth * dt;
 
   BCDesc<R> usd = a.us, dsd = a.ds;
   if (a.reach_kinds) { usd.kind = a.reach_kinds[reach]; dsd.kind = a.reach_kinds[(size_t)a.B + reach]; }
@@ -299,8 +299,8 @@ __global__ __launch_bounds__(64 * W, (long_min_waves<R, SEC>())) void preissmann
                 const R gAdt = gA * dt, gAx = gA * hx, sdt = ghdt * S;
                 const R X0 = fma_(gAdt, fma_(hth, L.eAT, -(cq * L.rT)), fma_(dtcq, L.v * L.v, sdt));
                 const R X1 = fma_(gAdt, fma_(hth, Rn.eAT, cq * Rn.rT), fma_(-dtcq, Rn.v * Rn.v, sdt));
-                const R Y0 = fma_(gAx, L.eQ, kap - L.v);
-                const R Y1 = fma_(gAx, Rn.eQ, kap + Rn.v);
+                const R Y0 = fma_(gAx, L.eQh, kap - L.v);
+                const R Y1 = fma_(gAx, Rn.eQh, kap + Rn.v);
                 const R ga = X1 + Y1;
                 row.al = X0 + Y0; row.D = (X0 - Y0) - ga; row.de = X1 - Y1;
                 row.rho0 = fma_(ga, Cres, -Mres);

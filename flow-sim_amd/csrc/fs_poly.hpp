@@ -272,7 +272,7 @@ __device__ __forceinline__ NodeTerms<R> poly_terms_tail(const PolyEval<R> &e, R 
   R dSeA = R(-2) * Sf * (dK * rK);
   R Se = Sf, eQ = R(2) * aQ * iK2;
   add_curvature(curv, e.A, frcp(e.A), e.T, frcp(e.T), e.dAdh, e.neq, e.y13, e.dRdA, h, Q, Se, dSeA, eQ);
-  t.A = e.A; t.T = e.dAdh; t.Se = Se; t.eAT = dSeA; t.eQ = eQ; t.v = Q * frcp(e.A);
+  t.A = e.A; t.T = e.dAdh; t.Se = Se; t.eAT = dSeA; t.eQh = eQ; t.v = Q * frcp(e.A);
   t.rT = frcp(e.dAdh);
   return t;
 }
