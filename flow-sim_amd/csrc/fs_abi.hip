@@ -231,6 +231,8 @@ struct fs_batch : Timeline {
   fs::DeviceBuffer dbg;
   Staging stage;                        // pinned chunks for large host <-> device transfers
   fs::DeviceBuffer kc_scratch;          // long reaches: level constants [B][4][passes * 64 W M]
+  fs::DeviceBuffer hk_entry, Qk_entry;  // long reaches of uniform sections: the state a launch of several levels began with (restore_failed_state)
+  fs::DeviceBuffer Yprev_entry;         // storage boundaries: the reservoir stages a launch of several levels began with (restore_failed_stage)
   int passes = 0;
   fs::DeviceBuffer team_mail;           // reaches stepped by teams of workgroups: mailboxes [B][2][G W + 1][kTeamWords]
   fs::DeviceBuffer team_sync;           // uint64 [1]: the ticket counter, zeroed before every launch
@@ -355,6 +357,28 @@ __global__ void refresh_level0_upstream(const R *hk, const R *Qk, R *hydro, size
   hydro[r] = hk[r * N]; hydro[B + r] = Qk[r * N];
 }
 
+// The multi-pass kernel of the uniform section modes reads the accepted state of level k from hk / Qk while it iterates on level
+// k + 1 (fs_long.hpp: its level constants are recomputed, not stored), so it writes every accepted level there - also those a reach
+// completes before it fails later in the same launch.  fs_batch_get_state promises the state at the end of the previous call for a
+// failed reach (include/flowsim_abi.h): the rows of such a reach go back to what the launch began with.
+template <typename R>
+__global__ void restore_failed_state(const int32_t *status, const R *hk0, const R *Qk0, R *hk, R *Qk, size_t B, size_t N) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * N) return;
+  const int32_t st = status[i / N];
+  if (st != FS_OK && st != FS_ILL_CONDITIONED) { hk[i] = hk0[i]; Qk[i] = Qk0[i]; }
+}
+
+// The same promise for the reservoir stage (fs_batch_get_storage_stage): every step kernel keeps the stage of the last level it
+// accepted and writes it back when it ends, also for a reach that failed on a later level of the same launch.
+template <typename R>
+__global__ void restore_failed_stage(const int32_t *status, const R *Y0, R *Y, size_t B) {
+  const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= B) return;
+  const int32_t st = status[r];
+  if (st != FS_OK && st != FS_ILL_CONDITIONED) Y[r] = Y0[r];
+}
+
 // reaches whose open level still iterates (fs_batch_iterate): not yet accepted and not failed
 __global__ void count_open_reaches(const int32_t *done, const int32_t *status, int32_t *out, size_t B) {
   const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -447,11 +471,35 @@ int launch_steps(fs_batch *b, int n_steps, int iter_budget) {
     HIP_TRY(b->team_sync.ensure(sizeof(unsigned long long)));
     HIP_TRY(hipMemsetAsync(b->team_sync.get(), 0, sizeof(unsigned long long), b->stream));
   }
+  // (a launch of one level writes the state of a reach only when that level is accepted: nothing to keep)
+  const bool keep_entry = k->key.longk && n_steps > 1 &&
+                          (b->d.section_mode == FS_SEC_RECT_UNIFORM || b->d.section_mode == FS_SEC_TRAP_UNIFORM);
+  const size_t state_bytes = (size_t)b->d.n_reaches * b->d.n_nodes * b->esz;
+  if (keep_entry) {
+    HIP_TRY(b->hk_entry.reserve(state_bytes));
+    HIP_TRY(b->Qk_entry.reserve(state_bytes));
+    HIP_TRY(hipMemcpyAsync(b->hk_entry.get(), b->hk.get(), state_bytes, hipMemcpyDeviceToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(b->Qk_entry.get(), b->Qk.get(), state_bytes, hipMemcpyDeviceToDevice, b->stream));
+  }
+  const bool keep_stage = n_steps > 1 && b->any_storage[FS_DOWNSTREAM];
+  if (keep_stage) {
+    HIP_TRY(b->Yprev_entry.reserve((size_t)b->d.n_reaches * b->esz));
+    HIP_TRY(hipMemcpyAsync(b->Yprev_entry.get(), b->Yprev.get(), (size_t)b->d.n_reaches * b->esz, hipMemcpyDeviceToDevice, b->stream));
+  }
   HIP_TRY(hipEventRecord(b->ev0, b->stream));
   with_real(b, [&](auto real) {
-    fs::KernelArgs<decltype(real)> a; fill_args(b, n_steps, a);
+    using R = decltype(real);
+    fs::KernelArgs<R> a; fill_args(b, n_steps, a);
     a.iter_budget = iter_budget;
     b->kern->fn(&a, b->d.n_reaches, b->stream);
+    if (keep_entry) {
+      const size_t B = b->d.n_reaches, N = b->d.n_nodes;
+      hipLaunchKernelGGL((restore_failed_state<R>), grid_256(B * N), dim3(256), 0, b->stream, b->status.get<const int32_t>(),
+                         b->hk_entry.get<const R>(), b->Qk_entry.get<const R>(), b->hk.get<R>(), b->Qk.get<R>(), B, N);
+    }
+    if (keep_stage)
+      hipLaunchKernelGGL((restore_failed_stage<R>), grid_256(b->d.n_reaches), dim3(256), 0, b->stream, b->status.get<const int32_t>(),
+                         b->Yprev_entry.get<const R>(), b->Yprev.get<R>(), (size_t)b->d.n_reaches);
   });
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(b->ev1, b->stream));

@@ -129,7 +129,11 @@ class PreissmannSolver(Solver):
                 raise ValueError("f(a) and f(b) must have different signs")      # what brentq raises in the reference
             if status == A.TEAM_STALL:
                 raise RuntimeError("device: a workgroup of this reach's team did not arrive (FS_TEAM_STALL, include/flowsim_abi.h)")
-            raise ValueError("NaN in system assembly")
+            # FS_NAN.  The reference looks for a NaN only with `diagnos` (preissmann.py:133-137); without it the norm test
+            # never passes (NaN < tolerance is False) and the level runs into the iteration cap (:124-126)
+            if diagnos:
+                raise ValueError("NaN in system assembly")
+            raise ValueError(f'Convergence within {max_iter} iterations couldn\'t be achieved.')
         self.time_level = nt - 1
         self.depth[:], self.flow[:] = h[:nt, 0], Q[:nt, 0]
         if self.ill_conditioned:

@@ -113,7 +113,25 @@ enum {
 #define FS_BC_MAX_PARAMS 10   /* of the fixed-size kinds 0..7 */
 enum { FS_UPSTREAM = 0, FS_DOWNSTREAM = 1 };
 
-/* per-reach status after stepping (preissmann.py:124-126 raises ValueError; :135-137 NaN check) */
+/* per-reach status after stepping (preissmann.py:124-126 raises ValueError; :135-137 NaN check)
+ *
+ * FS_MAX_ITER, FS_NAN and FS_STORAGE_RANGE are failures: the reach stops at the level it failed on (the FAILING LEVEL), the status
+ * sticks, and later fs_batch_step / fs_batch_iterate calls leave the reach alone until fs_batch_restart (or a new initial state)
+ * begins again from FS_OK.  The other reaches of the batch are not affected.  After a failure
+ *  - fs_batch_get_iterations holds, at the failing level, the number of Newton iterations that level began before it gave up:
+ *      FS_MAX_ITER        max_iter (the reference's "Convergence within N iterations couldn't be achieved"),
+ *      FS_NAN             the iteration whose residual norm was not finite,
+ *      FS_STORAGE_RANGE   the iteration whose reservoir row found no stage in [Y_min, Y_max] (brentq's ValueError in the reference);
+ *    the rows of later levels are 0, the rows of earlier levels the counts of those levels;
+ *  - the rows of fs_batch_get_hydrographs, fs_batch_get_history, fs_batch_get_storage_stages and fs_batch_get_residual_trace BEFORE
+ *    the failing level are complete and are what a run without the failure gives; the rows of the failing level and of later
+ *    levels are not written (hydrograph and storage-stage rows read 0 in a batch that has not held other results there, history
+ *    rows are undefined, and so is the trace row of the failing level);
+ *  - fs_batch_get_state and fs_batch_get_storage_stage are the state and the reservoir stage at the end of the previous call
+ *    (see there): a pair that belongs to one level, whatever levels the reach completed in the failing call before it failed;
+ *  - fs_batch_get_guess is the Newton vector of the failing level after its last update - it holds NaN after FS_NAN - and not a
+ *    start vector for anything: a caller that wants to go on from the last good level restarts from a (state, guess, stage)
+ *    triple it read before the failing call (fs_batch_restart), which is also how the level can be tried again with other inputs. */
 enum { FS_OK = 0, FS_MAX_ITER = 1, FS_NAN = 2, FS_STORAGE_RANGE = 3,
        /* A warning, not a failure (the reach keeps stepping and the status sticks): the linear systems of this reach are
         * ill-conditioned - in practice supercritical flow (v > c) over a long stretch, where one boundary condition per end
@@ -287,7 +305,8 @@ int fs_batch_restart(fs_batch *b, int32_t level, const double *h, const double *
  * every level into the history when FS_FLAG_HISTORY is set); for a reach whose status is not FS_OK
  * this is therefore the state at the end of the previous call. */
 int fs_batch_get_state(fs_batch *b, double *h, double *Q);
-/* the post-update Newton vector that seeds the next level (preissmann.py:146-147) */
+/* the post-update Newton vector that seeds the next level (preissmann.py:146-147); for a reach whose status is a failure: the
+ * vector the failing level ended with (see the status enum) */
 int fs_batch_get_guess(fs_batch *b, double *h, double *Q);
 /* out[n_levels][4][B] = depth[k,0], flow[k,0], depth[k,-1], flow[k,-1] for k = first..first+n-1
  * (what cases read from solver.depth / solver.flow, cases/gerd_roseires/model.py:107-111) */

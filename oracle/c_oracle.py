@@ -88,4 +88,6 @@ def run(p: O.Problem):
     stage = np.zeros(p.nt)
     st = lib().fso_run(C.byref(cp), depth.ctypes.data_as(_D), flow.ctypes.data_as(_D),
                        iters.ctypes.data_as(C.POINTER(C.c_int)), stage.ctypes.data_as(_D))
-    return dict(depth=depth, flow=flow, iters=iters, status=st, storage_stage=stage[1:])
+    # a failing run stops at the level whose count is the last one written (oracle/preissmann_oracle.py: fail_level)
+    fail_level = int(np.flatnonzero(iters)[-1]) if st else None
+    return dict(depth=depth, flow=flow, iters=iters, status=st, storage_stage=stage[1:], fail_level=fail_level)

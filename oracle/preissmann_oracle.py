@@ -350,8 +350,16 @@ def storage_mass_balance(st, dt, vol_in, Y_old):
     def f(Y_new):
         q_out = 0.5 * (storage_outflow(st, Y_old) + storage_outflow(st, Y_new)) if st.get("rc") is not None else 0.0
         return storage_net_vol(st, Y_old, Y_new) - (vol_in - q_out * dt)
-    Y = brentq(f, st["Y_min"], st["Y_max"])
+    try:
+        Y = brentq(f, st["Y_min"], st["Y_max"])
+    except ValueError as e:                                          # "f(a) and f(b) must have different signs"
+        raise StorageRange(str(e)) from None
     return st["min_stage"] if Y < st["min_stage"] else Y
+
+
+class StorageRange(ValueError):
+    """The reservoir's mass balance has no root in [Y_min, Y_max]: what brentq raises in the reference
+    (lumped_storage.py:24-35), status 3 of newton_run."""
 
 
 def boundary_eval(bc: BC, geo_node, h, Q, k, dt, Q_old=None, store=None):
@@ -389,8 +397,9 @@ def boundary_eval(bc: BC, geo_node, h, Q, k, dt, Q_old=None, store=None):
             Y_new = storage_mass_balance(st, dt, vol_in, Y_old)            # lumped_storage.py:24-35 (brentq)
         else:
             Y_new = Y_old + vol_in / st["area"]        # root of lumped_storage.py:25-28 with :170
+            store["Y_raw"] = Y_new                      # (before the range check and the floor: what a test measures margins on)
             if not (st["Y_min"] <= Y_new <= st["Y_max"]):
-                raise ValueError("f(a) and f(b) must have different signs")   # what brentq raises
+                raise StorageRange("f(a) and f(b) must have different signs")   # what brentq raises
             if Y_new < st["min_stage"]:
                 Y_new = st["min_stage"]
         store["Y_eval"] = Y_new
@@ -490,7 +499,10 @@ def csr_pattern(N):
 
 def newton_run(p: Problem, n_steps=None, trace=False, iterates=False):
     """Time loop x Newton loop, preissmann.py:101-163.  Returns dict(depth, flow [nt,N], iters[nt],
-    status, norms).  The row written for level k is the iterate whose residual norm passed the
+    status, norms).  status 1 / 2 / 3 (no convergence within max_iter, a residual norm that is not finite,
+    a reservoir stage without a root in [Y_min, Y_max]) end the run at "fail_level": depth / flow then stop
+    at that row (which holds the last iterate, not a result) and iters[fail_level] is the count
+    include/flowsim_abi.h defines.  trace=True also fills "stage_trace": (k, it, reservoir stage).  The row written for level k is the iterate whose residual norm passed the
     test, the updated vector seeds level k+1 (preissmann.py:128,146-154).  iterates=True adds
     "iterates": a list of (k, h_old, h) for every Newton iteration - the old-level state and the
     iterate whose node terms that iteration evaluated."""
@@ -507,7 +519,9 @@ def newton_run(p: Problem, n_steps=None, trace=False, iterates=False):
     norms = []
     store = {"Y_prev": None} if p.ds.storage is not None else None
     stages = []
+    stage_trace = []
     status = 0
+    fail_level = None
     old_terms = None
     its = []
     for k in range(1, nt):
@@ -520,7 +534,15 @@ def newton_run(p: Problem, n_steps=None, trace=False, iterates=False):
             depth[k], flow[k] = x[0::2], x[1::2]
             if iterates:
                 its.append((k, depth[k - 1].copy(), depth[k].copy()))
-            R, data, new = assemble(p, depth[k], flow[k], depth[k - 1], flow[k - 1], k, store, old_terms)
+            try:
+                R, data, new = assemble(p, depth[k], flow[k], depth[k - 1], flow[k - 1], k, store, old_terms)
+            except StorageRange:
+                status = 3
+                if trace and store is not None:
+                    stage_trace.append((k, it, store.get("Y_raw", np.nan)))
+                break
+            if trace and store is not None:
+                stage_trace.append((k, it, store.get("Y_raw", store["Y_eval"])))
             if J is None:
                 J = sp.coo_matrix((data, (rows, cols)), shape=(2 * N, 2 * N)).tocsr()
             else:
@@ -534,16 +556,19 @@ def newton_run(p: Problem, n_steps=None, trace=False, iterates=False):
                 break
             if err < p.tol:
                 break
-        iters[k] = it if status == 0 else it - 1
+        # the count of a failing level is the number of iterations whose residual was evaluated (include/flowsim_abi.h):
+        # max_iter for status 1, the iteration whose norm was not finite for 2, the one whose storage row had no root for 3
+        iters[k] = it - 1 if status == 1 else it
         if status:
+            fail_level = k
             depth, flow = depth[:k + 1], flow[:k + 1]
             break
         old_terms = new
         if store is not None:
             store["Y_prev"] = store["Y_eval"]
             stages.append(store["Y_eval"])
-    out = dict(depth=depth, flow=flow, iters=iters, status=status, norms=norms,
-               x_next=x, storage_stage=np.array(stages))
+    out = dict(depth=depth, flow=flow, iters=iters, status=status, norms=norms, fail_level=fail_level,
+               x_next=x, storage_stage=np.array(stages), stage_trace=stage_trace)
     if iterates:
         out["iterates"] = its
     return out

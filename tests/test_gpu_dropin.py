@@ -59,6 +59,16 @@ def test_non_convergence_raises_like_the_reference(capsys):
     with pytest.raises(ValueError, match="Convergence within 1 iterations couldn't be achieved."):
         solver.run(tolerance=1e-12, verbose=0, max_iter=1)
     assert "subcritical" in capsys.readouterr().out              # check_criticality ran first
+    # the message carries the count the oracle writes at the failing level (include/flowsim_abi.h: max_iter), also beyond 1
+    fx, meta = O.load_fixture(os.path.join(GOLDEN, "akbari.npz"))
+    p = O.problem_from_fixture(fx, meta)
+    p.tol, p.max_iter = 1e-12, 3
+    ref = O.newton_run(p)
+    assert ref["status"] == 1 and ref["iters"][ref["fail_level"]] == 3
+    solver, tol = CB.akbari()
+    with pytest.raises(ValueError, match=f"Convergence within {ref['iters'][ref['fail_level']]} iterations couldn't be achieved."):
+        solver.run(tolerance=1e-12, verbose=0, max_iter=3)
+    assert solver.time_level == ref["fail_level"] and solver.iterations[solver.time_level] == 3
 
 
 def test_manning_ensemble_batch_matches_sequential_reference_runs():
