@@ -130,7 +130,8 @@ enum { FS_UPSTREAM = 0, FS_DOWNSTREAM = 1 };
  *  - fs_batch_get_state and fs_batch_get_storage_stage are the state and the reservoir stage at the end of the previous call
  *    (see there): a pair that belongs to one level, whatever levels the reach completed in the failing call before it failed;
  *  - fs_batch_get_guess is the Newton vector of the failing level after its last update - it holds NaN after FS_NAN - and not a
- *    start vector for anything: a caller that wants to go on from the last good level restarts from a (state, guess, stage)
+ *    start vector for anything (after FS_MAX_ITER with max_iter = m it is the m-th Newton iterate of that level, which is what
+ *    tests/test_gpu_newton_iterates.py holds to the reference's iterates for every step kernel): a caller that wants to go on from the last good level restarts from a (state, guess, stage)
  *    triple it read before the failing call (fs_batch_restart), which is also how the level can be tried again with other inputs. */
 enum { FS_OK = 0, FS_MAX_ITER = 1, FS_NAN = 2, FS_STORAGE_RANGE = 3,
        /* A warning, not a failure (the reach keeps stepping and the status sticks): the linear systems of this reach are

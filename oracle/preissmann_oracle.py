@@ -497,7 +497,7 @@ def csr_pattern(N):
     return np.array(rows), np.array(cols)
 
 
-def newton_run(p: Problem, n_steps=None, trace=False, iterates=False):
+def newton_run(p: Problem, n_steps=None, trace=False, iterates=False, max_iter_at=None):
     """Time loop x Newton loop, preissmann.py:101-163.  Returns dict(depth, flow [nt,N], iters[nt],
     status, norms).  status 1 / 2 / 3 (no convergence within max_iter, a residual norm that is not finite,
     a reservoir stage without a root in [Y_min, Y_max]) end the run at "fail_level": depth / flow then stop
@@ -505,7 +505,9 @@ def newton_run(p: Problem, n_steps=None, trace=False, iterates=False):
     include/flowsim_abi.h defines.  trace=True also fills "stage_trace": (k, it, reservoir stage).  The row written for level k is the iterate whose residual norm passed the
     test, the updated vector seeds level k+1 (preissmann.py:128,146-154).  iterates=True adds
     "iterates": a list of (k, h_old, h) for every Newton iteration - the old-level state and the
-    iterate whose node terms that iteration evaluated."""
+    iterate whose node terms that iteration evaluated.  max_iter_at={level: m} caps that level alone (the
+    others keep p.max_iter): the run ends there with status 1 after m updates, and "x_next" is the m-th
+    Newton iterate of that level - what fs_batch_get_guess holds after FS_MAX_ITER."""
     N = p.N
     nt = p.nt if n_steps is None else min(p.nt, n_steps + 1)
     depth = np.empty((nt, N))
@@ -526,9 +528,10 @@ def newton_run(p: Problem, n_steps=None, trace=False, iterates=False):
     its = []
     for k in range(1, nt):
         it = 0
+        cap = p.max_iter if max_iter_at is None else max_iter_at.get(k, p.max_iter)
         while True:
             it += 1
-            if it - 1 >= p.max_iter:
+            if it - 1 >= cap:
                 status = 1
                 break
             depth[k], flow[k] = x[0::2], x[1::2]

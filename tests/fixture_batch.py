@@ -77,7 +77,7 @@ def is_rect_uniform(p: O.Problem):
             and flat(g["b_main"]) and flat(g["n_main"]))
 
 
-def batch_from_problems(problems, mode="auto", dtype="f64", history=True, n_main_override=None, monitor=None):
+def batch_from_problems(problems, mode="auto", dtype="f64", history=True, n_main_override=None, monitor=None, trace=False):
     """One batch from a list of oracle Problems that share N, nt and the scheme parameters.  monitor=None: as the history flag (a
     test that leaves the history out wants the step kernels compiled without diagnostics, the bench shapes)."""
     monitor = history if monitor is None else monitor
@@ -91,7 +91,7 @@ def batch_from_problems(problems, mode="auto", dtype="f64", history=True, n_main
         if mode != "rect_uniform" and B > 1:
             assert all(all(np.array_equal(p.geo[k], p0.geo[k]) for k in O.GEO_KEYS) for p in problems), \
                 "TABLE geometry is shared by the batch: reaches with their own channel need their own batch"
-    b = PreissmannBatch(B, p0.N, p0.nt, dtype=dtype, section_mode=mode, history=history, monitor=monitor)
+    b = PreissmannBatch(B, p0.N, p0.nt, dtype=dtype, section_mode=mode, history=history, monitor=monitor, trace=trace)
     b.set_scheme(p0.theta, p0.dt, p0.dx, p0.tol, p0.max_iter)
     if mode == "rect_uniform":
         b.set_geometry_uniform([p.geo["b_main"][0] for p in problems], [p.geo["n_main"][0] for p in problems],
