@@ -746,6 +746,9 @@ __device__ __forceinline__ BCRow<R> bc_eval_rect(const BCDesc<R> &bc, LdsParams<
   return r;
 }
 
+// parameters of the fixed-size boundary kinds (kind <= FS_BC_STORAGE): what the kernels copy to LDS ahead of the time loop
+__device__ __forceinline__ int bc_param_count(int kind) { static constexpr int kCount[] = {0, 1, 1, 2, 4, 5, 10, 5}; return kCount[kind]; }
+
 // ---------------------------------------------------------------------------------------------
 // The linear solve (reference: scipy.sparse.linalg.spsolve on the 2N x 2N banded Jacobian, preissmann.py:146).
 //
@@ -774,6 +777,27 @@ template <typename R> struct Seg { R u1, u3, ru, d1, d2, d3, rd, rc; };
 // what the way down needs to recover the separator m_{b-1} = -A1 p_a + A2 m_{c-1} + A3 of a merge and the p of the
 // right half's first row, p_b = rc - m_{b-1}
 template <typename R> struct Elim { R A1, A2, A3, rc; };
+
+// the eight numbers of a segment to / from consecutive words (LDS mailboxes), the four of a record to / from its slot of a
+// tree's record store R[4][64] (number-major: the 64 slots of one number are consecutive)
+template <typename R> __device__ __forceinline__ void put_seg(R *p, const Seg<R> &s) {
+  p[0] = s.u1; p[1] = s.u3; p[2] = s.ru; p[3] = s.d1; p[4] = s.d2; p[5] = s.d3; p[6] = s.rd; p[7] = s.rc;
+}
+template <typename R> __device__ __forceinline__ void get_seg(const R *p, Seg<R> &s) {
+  s.u1 = p[0]; s.u3 = p[1]; s.ru = p[2]; s.d1 = p[3]; s.d2 = p[4]; s.d3 = p[5]; s.rd = p[6]; s.rc = p[7];
+}
+template <typename R> __device__ __forceinline__ void put_elim(R *p, const Elim<R> &e) {
+  p[0 * 64] = e.A1; p[1 * 64] = e.A2; p[2 * 64] = e.A3; p[3 * 64] = e.rc;
+}
+template <typename R> __device__ __forceinline__ void get_elim(const R *p, Elim<R> &e) {
+  e.A1 = p[0 * 64]; e.A2 = p[1 * 64]; e.A3 = p[2 * 64]; e.rc = p[3 * 64];
+}
+// the segment of an identity row (m = 0): merged with anything it changes nothing - what pads a tree to its 64 lanes
+template <typename R> __device__ __forceinline__ void identity_seg(Seg<R> &s) {
+  s.u1 = R(0); s.u3 = R(0); s.ru = R(0); s.d1 = R(0); s.d2 = R(1); s.d3 = R(0); s.rd = R(0); s.rc = R(0);
+}
+// the 63 records of a tree over 64 lanes: level L's follow those of the levels below, one per group of 2^(L+1) lanes
+template <int L> __device__ __forceinline__ int tree_slot(int lane) { return (64 - (64 >> L)) + (lane >> (L + 1)); }
 
 __device__ __forceinline__ float abs_mod(float x) { return __builtin_fabsf(x); }     // source modifier, no instruction
 __device__ __forceinline__ double abs_mod(double x) { return __builtin_fabs(x); }
@@ -877,6 +901,45 @@ template <typename R> __device__ __forceinline__ R wave_sum(R v) {
   } else {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
   }
+}
+
+// LDS executes a wave's instructions in order: what a wave's lanes exchange through LDS among themselves needs no s_barrier, only
+// the fences that keep the compiler from moving the reads over the writes.  (A function object declared where it is used, as the
+// lambda it was: as a plain function it moves the multi-pass kernels' machine code - tools/isa_digest.py)
+struct WaveSync {
+  __device__ void operator()() const {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+};
+
+// ---- the tree over the 64 segments of a wave, one per lane (in-wave trees, top trees of a team or of the passes): records in rec[4][64] ----
+__device__ __forceinline__ int hi_abs(double v) { return __double2hiint(v) & 0x7fffffff; }      // (the conditioning monitor's word: fs_kernel.hpp)
+__device__ __forceinline__ int hi_abs(float v) { return __float_as_int(v) & 0x7fffffff; }
+__device__ __forceinline__ int max_(int a, int b) { return a > b ? a : b; }
+
+// Level L on the way up: every lane merges the segment of lane - 2^L into its own (a lane that does not survive the level is not read
+// again: no select, no branch around the merge), the group's last lane keeps the record (ln: the lane again, the step kernel's opaque copy).
+template <int L, typename R> __device__ __forceinline__ void up_level(Seg<R> &seg, R (&rec)[4][64], int lane, int ln) {
+  constexpr int d = 1 << L;
+  const Seg<R> left = seg_from_below<d>(seg);
+  Seg<R> mg; Elim<R> e;
+  merge(left, seg, mg, e);
+  if ((lane & (2 * d - 1)) == (2 * d - 1)) put_elim(&rec[0][tree_slot<L>(ln)], e);
+  seg = mg;
+}
+// the conditioning monitor's share of a level (fs_kernel.hpp): the largest |u3| of the segments merged so far, seg the level's result
+template <int L, typename R> __device__ __forceinline__ int monitor_level(int gi, const Seg<R> &seg) {
+  return max_(max_(tree_from_below<(1 << L)>(gi), gi), hi_abs(seg.u3));
+}
+// What a top tree hands back to the (member, wave) or (pass, wave) of lane s < S: px, mx of the way down, m of its first row from its
+// own up row (as posted) and m of the next one's first row (0 behind the last; shared nodes: both copies must move by the same bits).
+template <typename R> __device__ __forceinline__ void post_top_tree(R (*xres)[4], int lane, int S, R u1o, R u3o, R ruo, R px, R mx) {
+  const R ma = fma_(-u1o, px, fma_(-u3o, mx, ruo));
+  R mb = dpp_mov<0x134>(ma);                // wave_rol:1 : m of the next segment's first row
+  if (lane == 63) mb = R(0);
+  if (lane < S) { R *o = xres[lane]; o[0] = px; o[1] = mx; o[2] = ma; o[3] = (lane == S - 1) ? R(0) : mb; }
 }
 
 }  // namespace fs

@@ -8,6 +8,7 @@
 #include "fs_entry_list.hpp"
 #include "fs_dispatch.hpp"
 #include "fs_kernel.hpp"
+#include "fs_derive.hpp"
 
 typedef void (*FsLaunchFn)(const void *args, int B, hipStream_t st);
 

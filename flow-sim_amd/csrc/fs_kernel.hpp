@@ -61,10 +61,7 @@ template <typename R> __host__ __device__ constexpr R eps_of() { return sizeof(R
 // (the high word of the magnitude) carried along with the segment - and raises FS_ILL_CONDITIONED above 2^10 (calibration:
 // DESIGN.md section 4.1; every reference-generated near-critical fixture the kernel misses by more than 1e-8 lies above): the reference's
 // `diagnos` check (preissmann.py:139-144, rcond < 1e-12 -> ValueError "Jacobian is ill-conditioned") stands behind it.
-__device__ __forceinline__ int hi_abs(double v) { return __double2hiint(v) & 0x7fffffff; }
-__device__ __forceinline__ int hi_abs(float v) { return __float_as_int(v) & 0x7fffffff; }
 template <typename R> __host__ __device__ constexpr int growth_limit_bits() { return sizeof(R) == 8 ? ((1023 + 10) << 20) : ((127 + 10) << 23); }
-__device__ __forceinline__ int max_(int a, int b) { return a > b ? a : b; }
 
 template <typename R> struct KernelArgs {
   int32_t B, N, n_steps, level0, max_iter;
@@ -437,7 +434,7 @@ template <typename R, int SEC, int M, int W, int BCK, bool TEAM = false> constex
 // Membership is by TICKET, not by blockIdx: a workgroup takes the next (reach, member) job when it starts, so the members of the
 // oldest unfinished team are exactly the workgroups that started first - all resident, whatever order the dispatcher chose and
 // whatever else runs on the device; a team therefore never waits for a workgroup that cannot start (no co-residency assumption
-// beyond G <= CUs).  A wait that still exceeds ~2 s of s_memtime ends the reach with FS_TEAM_STALL instead of spinning on.
+// beyond G <= CUs).  A wait that still exceeds kTeamPatience (16e9 ticks of s_memtime) ends the reach with FS_TEAM_STALL instead of spinning on.
 template <typename R, int SEC, int M, int W, bool RAGGED = true, int BCK = 0, bool DIAG = true, int TAIL = -1, bool TEAM = false>
 __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) void preissmann_step_kernel(const KernelArgs<R> a) {
   static_assert(M >= 2, "a lane's segment needs two rows (its up and its down row)");
@@ -629,8 +626,7 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
     // kernel 1.2 % - seven more scalar loads inside its loops and 18 more AGPR moves - for code it never executes)
     const BCDesc<R> &src = side ? a.ds : a.us;
     const int skind = side ? dsd.kind : usd.kind;
-    static constexpr int kCount[] = {0, 1, 1, 2, 4, 5, 10, 5};
-    if (skind <= FS_BC_STORAGE && i < kCount[skind]) sm.bcp[side][i] = bc_param(src, i, reach, a.B);
+    if (skind <= FS_BC_STORAGE && i < bc_param_count(skind)) sm.bcp[side][i] = bc_param(src, i, reach, a.B);
     if (skind == FS_BC_NORMAL_DEPTH && i == 2) {        // derived: sign(S0) sqrt|S0| (hydraulics.py:4-13)
       const R S0 = bc_param(src, 0, reach, a.B);
       sm.bcp[side][2] = (S0 < R(0) ? R(-1) : R(1)) * sqrt_(fabs_(S0));
@@ -768,7 +764,6 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
       R iTn[Geo::kConstT ? 1 : M + 1];           // dt / T = 1/(2t) of the nodes, only when the top width varies
       Seg<R> seg;                                 // running rows of the lane's segment
       seg.u1 = R(0); seg.u3 = R(-1); seg.ru = R(0);
-      R upU1 = R(0), upU3 = R(0), upRu = R(0);    // the lane's finished up row, kept for the way back
       R rcLast = R(0);                            // rc of the lane's last row (links node M: p_M = rc - m_{M-1})
       // one-wave fp64 kernels: the root segment and the upstream row meet through v_readlane instead of an LDS round trip
       // (C5 fp64 +5.5 %, polyline ensemble +2.8 %, C4 +1.9 %; fp32: -0.5 %, left as it was)
@@ -880,8 +875,8 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
           __builtin_amdgcn_sched_barrier(0);        // one scheduling region per cell
         }
         seg.rc = rcPrev; rcLast = rcPrev;
-        upU1 = seg.u1; upU3 = seg.u3; upRu = seg.ru;
       }
+      const R upU1 = seg.u1, upU3 = seg.u3, upRu = seg.ru;    // the lane's finished up row, kept for the way back
       int gi = 0;                                  // conditioning monitor: largest |u3| of the segments this lane has seen
       if constexpr (kMonitor) gi = hi_abs(seg.u3);
 
@@ -890,17 +885,8 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
       Elim<R> rec[1];      // (never used: the polyline kernels' machine code depends on this declaration, on rcE, pre4 and pre3 below - tools/isa_digest.py)
       auto up_level = [&](auto lc) __attribute__((always_inline)) {
         constexpr int l = decltype(lc)::value;
-        constexpr int d = 1 << l;
-        const Seg<R> left = seg_from_below<d>(seg);
-        Seg<R> mg; Elim<R> e;
-        merge(left, seg, mg, e);
-        if ((lane & (2 * d - 1)) == (2 * d - 1)) {
-          const int slot = (64 - (64 >> l)) + (ln >> (l + 1));
-          R *p = &sm.tree[wave][0][slot];
-          p[0 * 64] = e.A1; p[1 * 64] = e.A2; p[2 * 64] = e.A3; p[3 * 64] = e.rc;
-        }
-        seg = mg;      // in every lane: a lane that does not survive this level is not read again (no select, no branch around the merge)
-        if constexpr (kMonitor) gi = max_(max_(tree_from_below<d>(gi), gi), hi_abs(mg.u3));
+        fs::up_level<l>(seg, sm.tree[wave], lane, ln);
+        if constexpr (kMonitor) gi = monitor_level<l>(gi, seg);
       };
       up_level(std::integral_constant<int, 0>{}); up_level(std::integral_constant<int, 1>{});
       up_level(std::integral_constant<int, 2>{}); up_level(std::integral_constant<int, 3>{});
@@ -920,25 +906,21 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
         // nothing to post: the root segment is read from lane 63 below
       } else
       if (lane == 63) {
-        R *p = sm.xseg[parity][wave];
-        p[0] = seg.u1; p[1] = seg.u3; p[2] = seg.ru; p[3] = seg.d1; p[4] = seg.d2; p[5] = seg.d3; p[6] = seg.rd; p[7] = seg.rc;
+        put_seg(sm.xseg[parity][wave], seg);
         sm.xnorm[parity][wave] = nrm2;
         if constexpr (kMonitor) sm.xg[parity][wave] = gi;
       }
       FS_T(2);
       // the wave's own top tree record (level 5) for the way down (step 5), requested ahead of the barrier: its LDS latency passes
       // during the cross-wave step instead of after it (multi-wave kernels without diagnostics; the wave wrote it itself, in order)
-      auto load_rec_early = [&](auto lc) __attribute__((always_inline)) {
-        constexpr int l = decltype(lc)::value;
+      auto load_rec = [&](auto lc) __attribute__((always_inline)) {
         Elim<R> e;
-        const int slot = (64 - (64 >> l)) + (ln >> (l + 1));
-        const R *p = &sm.tree[wave][0][slot];
-        e.A1 = p[0 * 64]; e.A2 = p[1 * 64]; e.A3 = p[2 * 64]; e.rc = p[3 * 64];
+        get_elim(&sm.tree[wave][0][tree_slot<decltype(lc)::value>(ln)], e);
         return e;
       };
       constexpr bool kPre = W > 1 && M >= 8 && !DIAG;
       Elim<R> pre5, pre4, pre3;      // (pre4 and pre3 are never used: see rec above)
-      if constexpr (kPre) pre5 = load_rec_early(std::integral_constant<int, 5>{});
+      if constexpr (kPre) pre5 = load_rec(std::integral_constant<int, 5>{});
       // (the team form could do without this barrier - wave 0 polls the mailbox for every wave's post, its own workgroup's included - and is
       // 6 % SLOWER without it: a wave 0 that starts polling while its neighbours still fold takes their issue slots and their memory path)
       // (one-wave reaches: no s_barrier is emitted for 64 threads, and dropping the workgroup fence with it changes nothing - measured, C4 / C5 / polylines +-0.3 %)
@@ -987,26 +969,19 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
             }
             if (lane == 0) sm.xstall = stall;
             auto val = [&](int i) { return (R)__longlong_as_double((long long)team_bits(w[i])); };
-            xs.u1 = val(0); xs.u3 = val(1); xs.ru = val(2); xs.d1 = val(3); xs.d2 = val(4); xs.d3 = val(5); xs.rd = val(6); xs.rc = val(7);
+            const R posted[8] = {val(0), val(1), val(2), val(3), val(4), val(5), val(6), val(7)};
+            get_seg(posted, xs);
             nr = val(8);
             gx = (int)(unsigned)team_bits(w[9]); fl = (int)(unsigned)(team_bits(w[9]) >> 32);
             aU = val(10); bU = val(11); rU = val(12);
           }
-          if (lane >= S) { xs.u1 = R(0); xs.u3 = R(0); xs.ru = R(0); xs.d1 = R(0); xs.d2 = R(1); xs.d3 = R(0); xs.rd = R(0); xs.rc = R(0); nr = R(0); gx = 0; fl = 0; }
+          if (lane >= S) { identity_seg(xs); nr = R(0); gx = 0; fl = 0; }
           const R u1o = xs.u1, u3o = xs.u3, ruo = xs.ru;
           auto xup = [&](auto lc) __attribute__((always_inline)) {
             constexpr int l = decltype(lc)::value;
-            constexpr int d = 1 << l;
-            const Seg<R> left = seg_from_below<d>(xs);
-            Seg<R> mg; Elim<R> e;
-            merge(left, xs, mg, e);
-            if ((lane & (2 * d - 1)) == (2 * d - 1)) {
-              R *w = &sm.xtree[0][(64 - (64 >> l)) + (lane >> (l + 1))];
-              w[0 * 64] = e.A1; w[1 * 64] = e.A2; w[2 * 64] = e.A3; w[3 * 64] = e.rc;
-            }
-            xs = mg;
-            gx = max_(max_(tree_from_below<d>(gx), gx), hi_abs(mg.u3));
-            fl = max_(tree_from_below<d>(fl), fl);
+            fs::up_level<l>(xs, sm.xtree, lane, lane);
+            gx = monitor_level<l>(gx, xs);
+            fl = max_(tree_from_below<(1 << l)>(fl), fl);
           };
           // (levels that would only merge identity segments are skipped: S <= 2^nl lanes carry something; the root then sits in lane 2^nl - 1)
           const int nl = S <= 8 ? 3 : (S <= 16 ? 4 : (S <= 32 ? 5 : 6));
@@ -1014,18 +989,15 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
           if (nl > 3) xup(std::integral_constant<int, 3>{});
           if (nl > 4) xup(std::integral_constant<int, 4>{});
           if (nl > 5) xup(std::integral_constant<int, 5>{});
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+          WaveSync{}();
           R p0, m0, ml;
           close_root(xs, aU, bU, rU, p0, m0, ml);            // valid in the root's lane
           const int rl = (1 << nl) - 1;
           R px = read_lane(p0, rl), mx = read_lane(ml, rl);
           auto xdown = [&](auto lc) __attribute__((always_inline)) {
             constexpr int l = decltype(lc)::value;
-            const R *w = &sm.xtree[0][(64 - (64 >> l)) + (lane >> (l + 1))];
             Elim<R> e;
-            e.A1 = w[0 * 64]; e.A2 = w[1 * 64]; e.A3 = w[2 * 64]; e.rc = w[3 * 64];
+            get_elim(&sm.xtree[0][tree_slot<l>(lane)], e);
             const R sep = separator(e, px, mx);
             const bool upper = ((lane >> l) & 1) != 0;
             px = upper ? e.rc - sep : px;
@@ -1035,10 +1007,7 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
           if (nl > 4) xdown(std::integral_constant<int, 4>{});
           if (nl > 3) xdown(std::integral_constant<int, 3>{});
           xdown(std::integral_constant<int, 2>{}); xdown(std::integral_constant<int, 1>{}); xdown(std::integral_constant<int, 0>{});
-          const R ma = fma_(-u1o, px, fma_(-u3o, mx, ruo));
-          R mb = dpp_mov<0x134>(ma);                // wave_rol:1 : m of the next segment's first row
-          if (lane == 63) mb = R(0);
-          if (lane < S) { R *o = sm.xres[lane]; o[0] = px; o[1] = mx; o[2] = ma; o[3] = (lane == S - 1) ? R(0) : mb; }
+          post_top_tree(sm.xres, lane, S, u1o, u3o, ruo, px, mx);
           const R tsum = wave_sum(nr);               // (a fixed order: the same total in every member)
           // (cross-lane reads in uniform control flow, fs_long.hpp)
           const int gtop = __builtin_amdgcn_readlane(gx, rl), ftop = __builtin_amdgcn_readlane(fl, rl);
@@ -1072,7 +1041,7 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
         const int wl = ln & (W - 1);
         const R *ps = sm.xseg[parity][wl];
         Seg<R> xs;
-        xs.u1 = ps[0]; xs.u3 = ps[1]; xs.ru = ps[2]; xs.d1 = ps[3]; xs.d2 = ps[4]; xs.d3 = ps[5]; xs.rd = ps[6]; xs.rc = ps[7];
+        get_seg(ps, xs);
         const R u1o = xs.u1, u3o = xs.u3, ruo = xs.ru;       // the wave's own up row (m of its first row, below)
 #pragma unroll
         for (int w = 0; w < W; ++w) tot += sm.xnorm[parity][w];
@@ -1131,8 +1100,7 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
 #pragma unroll
         for (int w = 0; w < W; ++w) {
           const R *p = sm.xseg[parity][w];
-          sw[w].u1 = p[0]; sw[w].u3 = p[1]; sw[w].ru = p[2]; sw[w].d1 = p[3]; sw[w].d2 = p[4]; sw[w].d3 = p[5];
-          sw[w].rd = p[6]; sw[w].rc = p[7];
+          get_seg(p, sw[w]);
           sw0[w] = sw[w];
           tot += sm.xnorm[parity][w];
         }
@@ -1207,14 +1175,6 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
       // group's first row and the m of its last one.  The group's record is one LDS slot that all its lanes read (a
       // broadcast read); each lane recovers the separator itself and keeps it as its new right number (lower half) or
       // turns it into its new left one (upper half): no cross-lane traffic, two dependent fp64 operations per level.
-      auto load_rec = [&](auto lc) __attribute__((always_inline)) {
-        constexpr int l = decltype(lc)::value;
-        Elim<R> e;
-        const int slot = (64 - (64 >> l)) + (ln >> (l + 1));
-        const R *p = &sm.tree[wave][0][slot];
-        e.A1 = p[0 * 64]; e.A2 = p[1 * 64]; e.A3 = p[2 * 64]; e.rc = p[3 * 64];
-        return e;
-      };
       auto down_level = [&](auto lc, const Elim<R> &e) __attribute__((always_inline)) {
         constexpr int l = decltype(lc)::value;
         const R sep = separator(e, pL, mR);
@@ -1372,131 +1332,6 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
   if (a.dbg && lane == 0)
     for (int i = 0; i < 12; ++i) a.dbg[((size_t)reach * 16 + (member * W + wave) % 16) * 12 + i] = stamp_[i];
 #endif
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// Post-processing (reference: Solver.prepare_results, solver.py:65-127).  One thread per V consecutive
-// (reach, node) elements walks the stored levels: 16-byte loads / stores (V = 2 doubles, 4 floats), consecutive
-// threads on consecutive elements, 16 B in and up to 56 B out per element - a plain HBM-bound stream.
-// ---------------------------------------------------------------------------------------------
-template <typename R> struct DeriveArgs {
-  int32_t B, N, first, n, section_mode;
-  const R *hist_h, *hist_Q;       // [levels][B][N]
-  const R *geo_uniform, *geo_table;
-  const R *poly_x, *poly_z;       // IRREGULAR (see KernelArgs)
-  const int32_t *poly_n;
-  int64_t geo_reach_stride, poly_reach_stride;      // per-reach tables (see KernelArgs), 0: shared
-  R *level, *area, *top, *froude, *vel, *cel, *amp, *peak;   // [n][B][N] (peak: [B][N]) or nullptr
-  const int32_t *reach_nodes;     // [B] or nullptr: nodes of each reach of a ragged batch (fs_batch_set_reach_nodes); entries beyond come out 0
-};
-
-template <typename R, int V> struct Pack { typedef R type __attribute__((ext_vector_type(V))); };
-
-// V elements from / to p: one 16-byte access when the thread's elements all exist and the row is aligned (whole)
-template <typename R, int V> __device__ __forceinline__ void load_pack(const R *__restrict__ p, bool whole, int cnt, R (&out)[V]) {
-  if (whole) {
-    const typename Pack<R, V>::type q = *reinterpret_cast<const typename Pack<R, V>::type *>(p);
-#pragma unroll
-    for (int e = 0; e < V; ++e) out[e] = q[e];
-  } else {
-#pragma unroll
-    for (int e = 0; e < V; ++e) out[e] = e < cnt ? p[e] : R(1);
-  }
-}
-template <typename R, int V> __device__ __forceinline__ void store_pack(R *__restrict__ p, bool whole, int cnt, const R (&in)[V]) {
-  if (whole) {
-    typename Pack<R, V>::type q;
-#pragma unroll
-    for (int e = 0; e < V; ++e) q[e] = in[e];
-    __builtin_nontemporal_store(q, reinterpret_cast<typename Pack<R, V>::type *>(p));     // written once, read by nobody on the device
-  } else {
-#pragma unroll
-    for (int e = 0; e < V; ++e) if (e < cnt) p[e] = in[e];
-  }
-}
-
-template <typename R, int V> __global__ __launch_bounds__(256) void derive_fields_kernel(const DeriveArgs<R> a) {
-  const size_t BN = (size_t)a.B * a.N;
-  const size_t i0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
-  if (i0 >= BN) return;
-  const int cnt = (int)(BN - i0 < (size_t)V ? BN - i0 : (size_t)V);
-  const bool whole = cnt == V && BN % V == 0;        // every level's row of this thread starts on a 16-byte boundary
-  SecParams<R> s[V];
-  PolyNode<R> pnode[V];
-  bool beyond[V];                            // ragged batches: a slot past the reach's own node count (no history there: results 0)
-#pragma unroll
-  for (int e = 0; e < V; ++e) {
-    const size_t i = i0 + (e < cnt ? e : 0);
-    const int reach = (int)(i / a.N), node = (int)(i - (size_t)reach * a.N);
-    const int nodes_r = a.reach_nodes ? a.reach_nodes[reach] : a.N;        // the step kernels' Geometry::init(a, reach, n_nodes)
-    beyond[e] = node >= nodes_r;
-    pnode[e].n = 0;
-    if (a.section_mode == FS_SEC_TABLE || a.section_mode == FS_SEC_IRREGULAR) {
-      auto g = [&](int row) { return a.geo_table[(size_t)reach * a.geo_reach_stride + (size_t)row * a.N + node]; };
-      s[e].z = g(FS_GEO_Z_BED); s[e].b = g(FS_GEO_B_MAIN); s[e].m = g(FS_GEO_M_MAIN);
-      s[e].compound = g(FS_GEO_IS_COMPOUND) > R(0.5);
-      s[e].hbf = g(FS_GEO_H_BANKFULL); s[e].bl = g(FS_GEO_B_FP_LEFT); s[e].br = g(FS_GEO_B_FP_RIGHT); s[e].mfp = g(FS_GEO_M_FP);
-      if (a.section_mode == FS_SEC_IRREGULAR) {
-        const size_t po = (size_t)reach * a.poly_reach_stride, no = a.poly_reach_stride ? (size_t)reach * a.N : 0;
-        if (a.poly_n[no + node] > 0) {
-          pnode[e].x = a.poly_x + po + node; pnode[e].z = a.poly_z + po + node; pnode[e].stride = a.N; pnode[e].n = a.poly_n[no + node];
-          pnode[e].tz = nullptr; pnode[e].K = 0; pnode[e].KP = 0;
-        }
-      }
-    } else {
-      const R z_us = a.geo_uniform[(size_t)FS_RU_Z_US * a.B + reach], z_ds = a.geo_uniform[(size_t)FS_RU_Z_DS * a.B + reach];
-      const R w2 = R(node) * (R(1) / R(nodes_r - 1));       // the reach's own node count, as Geometry<R, *_UNIFORM>::bed
-      s[e].z = z_us * (R(1) - w2) + z_ds * w2;
-      s[e].b = a.geo_uniform[(size_t)FS_RU_WIDTH * a.B + reach];
-      s[e].m = a.section_mode == FS_SEC_TRAP_UNIFORM ? a.geo_uniform[(size_t)FS_TU_SIDE_SLOPE * a.B + reach] : R(0);
-      s[e].compound = false; s[e].hbf = s[e].bl = s[e].br = s[e].mfp = R(0);
-    }
-  }
-  R h0[V], peak[V];                          // depth[0] (amplitude reference, solver.py:96-97)
-  load_pack<R, V>(a.hist_h + i0, whole, cnt, h0);
-#pragma unroll
-  for (int e = 0; e < V; ++e) peak[e] = R(-3.0e38);
-  for (int k = 0; k < a.n; ++k) {
-    const size_t src = (size_t)(a.first + k) * BN + i0, dst = (size_t)k * BN + i0;
-    R h[V], Q[V], lev[V], A[V], T[V], Fr[V], vel[V], cel[V], am[V];
-    load_pack<R, V>(a.hist_h + src, whole, cnt, h);
-    load_pack<R, V>(a.hist_Q + src, whole, cnt, Q);
-#pragma unroll
-    for (int e = 0; e < V; ++e) {
-      if (beyond[e]) { h[e] = R(1); Q[e] = R(0); }        // (never written by the step kernel)
-      // area and top width: cross_section.py:623-679 (incl. the over-bank convention)
-      const SecParams<R> &se = s[e];
-      const R d = fmax_(R(0), h[e]);
-      R Te = se.b + R(2) * se.m * d;
-      R Ae = (se.b + Te) / R(2) * d;
-      if (se.compound && d > se.hbf) {
-        const R dfp = d - se.hbf, Tb = se.b + R(2) * se.m * se.hbf;
-        Ae = (se.b + Tb) / R(2) * se.hbf + (se.bl + R(0.5) * se.mfp * dfp) * dfp + (se.br + R(0.5) * se.mfp * dfp) * dfp;
-        Te = (se.bl + Tb + se.br) + R(2) * se.mfp * dfp;
-      }
-      if (d <= R(0)) { Ae = R(0); Te = R(0); }
-      if (pnode[e].n > 0) poly_area_top(pnode[e], h[e] + se.z, Ae, Te);     // cross_section.py:248-328
-      const R Ve = Q[e] / Ae;
-      lev[e] = h[e] + se.z; A[e] = Ae; T[e] = Te; vel[e] = Ve;
-      {                                        // hydraulics.py:155-168 with its clamps
-        const R Vc = Q[e] / fmax_(Ae, R(1e-6)), D = Ae / fmax_(Te, R(1e-6));
-        Fr[e] = Vc / sqrt_(R(kG) * fmax_(D, R(1e-6)));
-      }
-      cel[e] = Ve + sqrt_(R(kG) * Ae / Te);
-      am[e] = h[e] - h0[e];
-      peak[e] = fmax_(peak[e], am[e]);
-      if (beyond[e]) { lev[e] = A[e] = T[e] = Fr[e] = vel[e] = cel[e] = am[e] = R(0); peak[e] = R(0); }
-    }
-    if (a.level) store_pack<R, V>(a.level + dst, whole, cnt, lev);
-    if (a.area) store_pack<R, V>(a.area + dst, whole, cnt, A);
-    if (a.top) store_pack<R, V>(a.top + dst, whole, cnt, T);
-    if (a.froude) store_pack<R, V>(a.froude + dst, whole, cnt, Fr);
-    if (a.vel) store_pack<R, V>(a.vel + dst, whole, cnt, vel);
-    if (a.cel) store_pack<R, V>(a.cel + dst, whole, cnt, cel);
-    if (a.amp) store_pack<R, V>(a.amp + dst, whole, cnt, am);
-  }
-  if (a.peak) store_pack<R, V>(a.peak + i0, whole, cnt, peak);
 }
 
 }  // namespace fs

@@ -99,8 +99,7 @@ __global__ __launch_bounds__(64 * W, (long_min_waves<R, SEC>())) void preissmann
     const int side = t / FS_BC_MAX_PARAMS, i = t - side * FS_BC_MAX_PARAMS;
     BCDesc<R> src = side ? a.ds : a.us;
     src.kind = side ? dsd.kind : usd.kind;
-    static constexpr int kCount[] = {0, 1, 1, 2, 4, 5, 10, 5};
-    if (src.kind <= FS_BC_STORAGE && i < kCount[src.kind]) sm.bcp[side][i] = bc_param(src, i, reach, a.B);
+    if (src.kind <= FS_BC_STORAGE && i < bc_param_count(src.kind)) sm.bcp[side][i] = bc_param(src, i, reach, a.B);
     if (src.kind == FS_BC_NORMAL_DEPTH && i == 2) {
       const R S0 = bc_param(src, 0, reach, a.B);
       sm.bcp[side][2] = (S0 < R(0) ? R(-1) : R(1)) * sqrt_(fabs_(S0));
@@ -133,11 +132,7 @@ __global__ __launch_bounds__(64 * W, (long_min_waves<R, SEC>())) void preissmann
   // kernel's time with them, profiles/round3/long_mem.txt), transposed through the wave's staging buffer.  LDS executes a wave's
   // instructions in order; the fences keep the compiler from moving the reads over the writes.
   auto pad = [](int i) { return i + (i >> 3); };
-  auto wave_sync = [] {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  };
+  const WaveSync wave_sync;
   auto load_nodes_co = [&](const R *hs, const R *Qs, int p, R(&h)[M + 1], R(&Q)[M + 1]) __attribute__((always_inline)) {
     const int wb = p * C + wave * (64 * M);                   // first node of this wave in this pass
     R *const sh = sm.stage[wave][0], *const sq = sm.stage[wave][1];
@@ -227,8 +222,8 @@ __global__ __launch_bounds__(64 * W, (long_min_waves<R, SEC>())) void preissmann
           const int g0 = p * C + t * M;                                  // first row / node of this lane in this pass
           if (p * C > NC) {                                              // nothing but padding: identity segments
             if (phase == 0 && lane == 63) {
-              R *q = sm.xseg[p * W + wave];
-              q[0] = R(0); q[1] = R(0); q[2] = R(0); q[3] = R(0); q[4] = R(1); q[5] = R(0); q[6] = R(0); q[7] = R(0);
+              Seg<R> idn; identity_seg(idn);
+              put_seg(sm.xseg[p * W + wave], idn);
               sm.xg[p * W + wave] = 0;
             }
             continue;
@@ -339,16 +334,8 @@ __global__ __launch_bounds__(64 * W, (long_min_waves<R, SEC>())) void preissmann
           // ---- in-wave tree, up ----
           auto up_level = [&](auto lc) __attribute__((always_inline)) {
             constexpr int l = decltype(lc)::value;
-            constexpr int d = 1 << l;
-            const Seg<R> left = seg_from_below<d>(seg);
-            Seg<R> mg; Elim<R> e;
-            merge(left, seg, mg, e);
-            if ((lane & (2 * d - 1)) == (2 * d - 1)) {
-              R *q = &sm.tree[wave][0][(64 - (64 >> l)) + (lane >> (l + 1))];
-              q[0 * 64] = e.A1; q[1 * 64] = e.A2; q[2 * 64] = e.A3; q[3 * 64] = e.rc;
-            }
-            seg = mg;
-            gi = max_(max_(tree_from_below<d>(gi), gi), hi_abs(mg.u3));
+            fs::up_level<l>(seg, sm.tree[wave], lane, lane);
+            gi = monitor_level<l>(gi, seg);
           };
           up_level(std::integral_constant<int, 0>{}); up_level(std::integral_constant<int, 1>{});
           up_level(std::integral_constant<int, 2>{}); up_level(std::integral_constant<int, 3>{});
@@ -356,8 +343,7 @@ __global__ __launch_bounds__(64 * W, (long_min_waves<R, SEC>())) void preissmann
 
           if (phase == 0) {
             if (lane == 63) {
-              R *q = sm.xseg[p * W + wave];
-              q[0] = seg.u1; q[1] = seg.u3; q[2] = seg.ru; q[3] = seg.d1; q[4] = seg.d2; q[5] = seg.d3; q[6] = seg.rd; q[7] = seg.rc;
+              put_seg(sm.xseg[p * W + wave], seg);
               sm.xg[p * W + wave] = gi;
             }
             continue;
@@ -366,16 +352,13 @@ __global__ __launch_bounds__(64 * W, (long_min_waves<R, SEC>())) void preissmann
           // ---- sweep 1: way down, back-substitution, acceptance, update ----
           // the records of this pass's tree were written by this wave's own lanes just above: LDS executes a wave's
           // instructions in order, the fence keeps the compiler from hoisting the reads over the predicated stores
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+          wave_sync();
           const R *xr = sm.xres[p * W + wave];
           R pL = xr[0], mR = xr[1];
           auto down_level = [&](auto lc) __attribute__((always_inline)) {
             constexpr int l = decltype(lc)::value;
-            const R *q = &sm.tree[wave][0][(64 - (64 >> l)) + (lane >> (l + 1))];
             Elim<R> e;
-            e.A1 = q[0 * 64]; e.A2 = q[1 * 64]; e.A3 = q[2 * 64]; e.rc = q[3 * 64];
+            get_elim(&sm.tree[wave][0][tree_slot<l>(lane)], e);
             const R sep = separator(e, pL, mR);
             const bool upper = ((lane >> l) & 1) != 0;
             pL = upper ? e.rc - sep : pL;
@@ -450,38 +433,26 @@ __global__ __launch_bounds__(64 * W, (long_min_waves<R, SEC>())) void preissmann
           if (wave == 0) {
             const int S = P * W;
             const int sl = lane < S ? lane : 0;
-            const R *q = sm.xseg[sl];
             Seg<R> xs;
-            xs.u1 = q[0]; xs.u3 = q[1]; xs.ru = q[2]; xs.d1 = q[3]; xs.d2 = q[4]; xs.d3 = q[5]; xs.rd = q[6]; xs.rc = q[7];
+            get_seg(sm.xseg[sl], xs);
             int gx = sm.xg[sl];
-            if (lane >= S) { xs.u1 = R(0); xs.u3 = R(0); xs.ru = R(0); xs.d1 = R(0); xs.d2 = R(1); xs.d3 = R(0); xs.rd = R(0); xs.rc = R(0); gx = 0; }
+            if (lane >= S) { identity_seg(xs); gx = 0; }
             const R u1o = xs.u1, u3o = xs.u3, ruo = xs.ru;
             auto xup = [&](auto lc) __attribute__((always_inline)) {
               constexpr int l = decltype(lc)::value;
-              constexpr int d = 1 << l;
-              const Seg<R> left = seg_from_below<d>(xs);
-              Seg<R> mg; Elim<R> e;
-              merge(left, xs, mg, e);
-              if ((lane & (2 * d - 1)) == (2 * d - 1)) {
-                R *w = &sm.xtree[0][(64 - (64 >> l)) + (lane >> (l + 1))];
-                w[0 * 64] = e.A1; w[1 * 64] = e.A2; w[2 * 64] = e.A3; w[3 * 64] = e.rc;
-              }
-              xs = mg;
-              gx = max_(max_(tree_from_below<d>(gx), gx), hi_abs(mg.u3));
+              up_level<l>(xs, sm.xtree, lane, lane);
+              gx = monitor_level<l>(gx, xs);
             };
             xup(std::integral_constant<int, 0>{}); xup(std::integral_constant<int, 1>{}); xup(std::integral_constant<int, 2>{});
             xup(std::integral_constant<int, 3>{}); xup(std::integral_constant<int, 4>{}); xup(std::integral_constant<int, 5>{});
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
             R p0, m0, ml;
             close_root(xs, sm.xbc[0], sm.xbc[1], sm.xbc[2], p0, m0, ml);        // valid in lane 63
             R px = read_lane(p0, 63), mx = read_lane(ml, 63);
             auto xdown = [&](auto lc) __attribute__((always_inline)) {
               constexpr int l = decltype(lc)::value;
-              const R *w = &sm.xtree[0][(64 - (64 >> l)) + (lane >> (l + 1))];
               Elim<R> e;
-              e.A1 = w[0 * 64]; e.A2 = w[1 * 64]; e.A3 = w[2 * 64]; e.rc = w[3 * 64];
+              get_elim(&sm.xtree[0][tree_slot<l>(lane)], e);
               const R sep = separator(e, px, mx);
               const bool upper = ((lane >> l) & 1) != 0;
               px = upper ? e.rc - sep : px;
@@ -489,10 +460,7 @@ __global__ __launch_bounds__(64 * W, (long_min_waves<R, SEC>())) void preissmann
             };
             xdown(std::integral_constant<int, 5>{}); xdown(std::integral_constant<int, 4>{}); xdown(std::integral_constant<int, 3>{});
             xdown(std::integral_constant<int, 2>{}); xdown(std::integral_constant<int, 1>{}); xdown(std::integral_constant<int, 0>{});
-            const R ma = fma_(-u1o, px, fma_(-u3o, mx, ruo));
-            R mb = dpp_mov<0x134>(ma);              // wave_rol:1 : m of the next segment's first row
-            if (lane == 63) mb = R(0);
-            if (lane < S) { R *o = sm.xres[lane]; o[0] = px; o[1] = mx; o[2] = ma; o[3] = (lane == S - 1) ? R(0) : mb; }
+            post_top_tree(sm.xres, lane, S, u1o, u3o, ruo, px, mx);
             R tot = R(0);
 #pragma unroll
             for (int w = 0; w < W; ++w) tot += sm.xnorm[w];
