@@ -527,6 +527,7 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
   auto tol_of = [&]() __attribute__((always_inline)) -> R { if constexpr (BCK <= 0) { if (own_scheme) return a.reach_scheme[(size_t)3 * a.B + reach]; } return a.tol; };
   auto max_iter_of = [&]() __attribute__((always_inline)) -> int { if constexpr (BCK <= 0) { if (own_scheme) return (int)a.reach_scheme[(size_t)4 * a.B + reach]; } return a.max_iter; };
   R r2dt = R(1) / (R(2) * dt);
+  const R Tr2dt = geo.terms_T() * r2dt;        // constant top width: T/(2dt), the weight of h_j + h_{j+1} in the continuity residual (rc_of below)
   R cq = th / dx_;                            // theta/dx
   const R cqk = (R(1) - th) / dx_;            // (1-theta)/dx
   R hth = R(0.5) * th;
@@ -689,7 +690,9 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
     bool converged = false;
     R Ynew = Yprev;
     while (!converged && status == FS_OK) {
-      R dh[M + 1], dQ[M + 1];                   // the update, pending until the acceptance block is through
+      // the update, pending until the acceptance block is through, as the two sums it is made of: dh = p + m and
+      // dQ = p - m of the node; the scalings 1/(2t) and 1/(2cq) are applied with the addition, one fma per unknown
+      R dh[M + 1], dQ[M + 1];
       if (kBudget && budget-- <= 0) break;
       ++it;
       if constexpr (BCK <= 0) { if (it - 1 >= max_iter_of()) { status = FS_MAX_ITER; break; } }
@@ -1216,7 +1219,7 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
       R mB = dpp_mov<0x134>(mA);                // wave_rol:1 - m of the next lane's first row = this lane's node M
       if (lane == 63) mB = mBw;
 
-      // The update is kept pending in dh/dQ (they take the registers the elimination records free up):
+      // The update is kept pending in dh/dQ as p + m and p - m (they take the registers the elimination records free up):
       // the accepted iterate must still be intact for the level-constant pass below.
       if (Geo::kConstT) {
         // The continuity residuals are recomputed below on purpose (one value per node less to keep
@@ -1227,13 +1230,13 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
 #pragma unroll
         for (int j = 0; j <= M; ++j) asm volatile("" : "+v"(h[j]), "+v"(Q[j]));
       }
+      const R i2tc = dt * geo.rT_const();
+      auto i2t_of = [&](int j) { return Geo::kConstT ? i2tc : iTn[j]; };
       {
-        const R i2tc = dt * geo.rT_const();
-        auto i2t_of = [&](int j) { return Geo::kConstT ? i2tc : iTn[j]; };
         // rc of row j for the link p_{j+1} = rc_j - m_j: minus the continuity residual of cell j, 0 beyond the cells
         auto rc_of = [&](int j) __attribute__((always_inline)) {
           if (Geo::kConstT) {
-            const R v = -(geo.terms_T() * (h[j] + h[j + 1]) * r2dt + cq * (Q[j + 1] - Q[j]) + kcb[(0 * M + j) * T]);
+            const R v = -(fma_(h[j] + h[j + 1], Tr2dt, cq * (Q[j + 1] - Q[j])) + kcb[(0 * M + j) * T]);
             return (RAGGED && s0 + j >= NC) ? R(0) : v;
           }
           return j + 1 < M ? el[j].qc.get() : rcLast;
@@ -1243,23 +1246,20 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
           // node M: p from this lane's last row, m from the next lane.  rcLast, not a recomputed residual: the next lane's
           // p of its first row is (this rc) - (this m), and both copies of the shared node must move by the same bits
           const R pM = rcLast - mR;
-          dh[M] = (pM + mB) * i2t_of(M); dQ[M] = (pM - mB) * i2c;
-          if constexpr (kTail) { dh[M] *= mlt; dQ[M] *= mlt; }       // (node M > TAIL always: a phantom node from the owner lane on)
+          dh[M] = pM + mB; dQ[M] = pM - mB;
         }
 #pragma unroll
         for (int j = M - 1; j >= 1; --j) {
           // m_{j-1} = R3 - R1 p_a - R2 m_j ; row 0's m comes from the up row (mA)
           const R mprev = j == 1 ? mA : fma_(-el[j - 1].R2.get(), mj, fma_(-el[j - 1].R1.get(), pL, el[j - 1].R3.get()));
           const R pj = rc_of(j - 1) - mprev;
-          dh[j] = (pj + mj) * i2t_of(j); dQ[j] = (pj - mj) * i2c;
-          if constexpr (kTail) { dh[j] *= (j <= TAIL ? mle : mlt); dQ[j] *= (j <= TAIL ? mle : mlt); }     // phantom nodes stay where they are
+          dh[j] = pj + mj; dQ[j] = pj - mj;
           mj = mprev;
         }
-        dh[0] = (pL + mA) * i2t_of(0); dQ[0] = (pL - mA) * i2c;
-        if constexpr (kTail) { dh[0] *= mle; dQ[0] *= mle; }
+        dh[0] = pL + mA; dQ[0] = pL - mA;
       }
       FS_T(6);
-      // fp32 only: pin the back-substituted updates and fence them off from the acceptance block (three waves per SIMD at 168 registers:
+      // fp32 only: pin the back-substituted (pending) sums and fence them off from the acceptance block (three waves per SIMD at 168 registers:
       // the fence keeps them there, C5 fp32 +4.5 %; fp64: round 1 +0.9 %, with the round-2 solve flagship -2.3 %)
       if constexpr (sizeof(R) == 4) {
 #pragma unroll
@@ -1313,7 +1313,12 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
 
       FS_T(5);
 #pragma unroll
-      for (int j = 0; j <= M; ++j) { h[j] += dh[j]; Q[j] += dQ[j]; }     // preissmann.py:146-147
+      for (int j = 0; j <= M; ++j) {                                       // preissmann.py:146-147
+        // tail-only form: the masks ride in the factor - phantom nodes (j > TAIL from the owner lane on, every j behind it) stay where they are
+        const R mk = kTail ? (j <= TAIL ? mle : mlt) : R(1);
+        h[j] = fma_(dh[j], kTail ? i2t_of(j) * mk : i2t_of(j), h[j]);
+        Q[j] = fma_(dQ[j], kTail ? i2c * mk : i2c, Q[j]);
+      }
     }
     if (status != FS_OK && gt == 0) a.iters[(size_t)level * a.B + reach] = it - (status == FS_MAX_ITER ? 1 : 0);
     if (kBudget && a.iter_budget > 0) {
