@@ -25,6 +25,7 @@
 #include "fs_entries.hpp"
 #include "fs_host_pack.hpp"
 #include "fs_init_state.hpp"
+#include "fs_reduce.hpp"
 
 // ROCTx ranges around the phases a system trace should show (rocprofv3 --marker-trace): uploads, downloads, the step launch,
 // the post-processing launch.  Without a tool attached a push / pop is a few nanoseconds.
@@ -41,11 +42,17 @@ struct TraceRange {
 // table below takes their address)
 FS_ACTIVE_LIST(FS_DECLARE)
 #else
-// an experiment build is this translation unit alone, with a few step kernels: it has no initial-condition kernels (fs_part_init.hip),
-// and fs_batch_init_state says so
+// an experiment build is this translation unit alone, with a few step kernels: it has no initial-condition kernels (fs_part_init.hip)
+// and no post-processing kernels (fs_part_reduce.hip), and fs_batch_init_state, fs_batch_summarize, ... say so
 namespace fs {
 bool launch_init_state(int, const InitArgs<double> &, hipStream_t) { return false; }
 bool launch_init_state(int, const InitArgs<float> &, hipStream_t) { return false; }
+bool launch_summarize(const ReduceArgs<double> &, double *, hipStream_t) { return false; }
+bool launch_summarize(const ReduceArgs<float> &, double *, hipStream_t) { return false; }
+bool launch_lookup(const ReduceArgs<double> &, const LookupArgs &, hipStream_t) { return false; }
+bool launch_lookup(const ReduceArgs<float> &, const LookupArgs &, hipStream_t) { return false; }
+bool launch_bands(const ReduceArgs<double> &, const BandArgs &, hipStream_t) { return false; }
+bool launch_bands(const ReduceArgs<float> &, const BandArgs &, hipStream_t) { return false; }
 }  // namespace fs
 #endif
 
@@ -228,6 +235,8 @@ struct fs_batch : Timeline {
   fs::DeviceBuffer derived[8];          // device results of the last derive call, kept and reused (grown, never shrunk)
   fs::DeviceBuffer ic_in[4];            // fs_batch_init_state's inputs in the batch's type: flow, depth_us, depth_ds [B], bed_slope [N] or [B][N]
   fs::DeviceBuffer ic_info;             // int32 [2][B]: what fs_batch_init_state reports per reach (allocated on first use)
+  fs::DeviceBuffer red_in[3];           // double: what the caller handed to the last fs_batch_lookup / fs_batch_bands (offsets, abscissae or levels, targets)
+  fs::DeviceBuffer red_out[3];          // results of the last fs_batch_summarize / lookup / bands, kept and reused (grown, never shrunk)
   fs::DeviceBuffer dbg;
   Staging stage;                        // pinned chunks for large host <-> device transfers
   fs::DeviceBuffer kc_scratch;          // long reaches: level constants [B][4][passes * 64 W M]
@@ -606,6 +615,39 @@ int init_batch(fs_batch *b) {
   if (B * N * esz >= kStageMin) (void)b->stage.init();        // large batch: the pinned chunks exist before the first transfer is timed
   return 0;
 }
+
+
+// ---- ensemble post-processing (fs_reduce.hpp): what the three entry points share ----
+
+// the range [first, first + n) must hold computed rows only
+int check_reduce_range(const fs_batch *b, const char *entry, int32_t first, int32_t n) {
+  if (!b->have_state) return fail(std::string(entry) + ": no state yet");
+  if (first < 0 || n < 1 || (int64_t)first + n > (int64_t)b->level + 1)
+    return fail(std::string(entry) + ": levels [" + std::to_string(first) + ", " + std::to_string((int64_t)first + n) + ") are not inside 0 .. " +
+                std::to_string(b->level) + ", the levels this batch has computed");
+  if (b->restart_level > 0 && first < b->restart_level)
+    return fail(std::string(entry) + ": this batch was restarted at level " + std::to_string(b->restart_level) + "; the hydrograph rows before it were not restored");
+  return 0;
+}
+
+template <typename R> fs::ReduceArgs<R> reduce_args(const fs_batch *b, int32_t first, int32_t n) {
+  return fs::ReduceArgs<R>{b->hydro.get<const R>(), b->status.get<const int32_t>(), b->iters.get<const int32_t>(), b->d.n_reaches, b->level, first, n};
+}
+
+// n doubles of the caller's into a double buffer of the handle (the batch's dtype does not apply to these)
+int upload_f64(fs::DeviceBuffer &dst, const double *src, size_t n) {
+  HIP_TRY(dst.reserve(n * sizeof(double)));
+  HIP_TRY(hipMemcpy(dst.get(), src, n * sizeof(double), hipMemcpyHostToDevice));
+  return 0;
+}
+
+int fetch(fs_batch *b, void *dst, const void *dev, size_t bytes) {
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  HIP_TRY(hipMemcpy(dst, dev, bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+const char kNoReduceKernels[] = ": this build has no post-processing kernels";
 
 }  // namespace
 
@@ -1230,6 +1272,94 @@ int fs_batch_derive(fs_batch *b, int32_t first, int32_t n, double *level, double
   const size_t BN = (size_t)b->d.n_reaches * b->d.n_nodes;
   for (int f = 0; f < 8; ++f)
     if (host[f] && download(b, host[f], b->derived[f], 0, f == 7 ? BN : BN * n)) return -1;
+  return 0;
+}
+
+int fs_batch_summarize(fs_batch *b, int32_t first, int32_t n, double *out) {
+  if (!b) return fail("fs_batch_summarize: null handle");
+  if (!out) return fail("fs_batch_summarize: null output");
+  if (check_reduce_range(b, "fs_batch_summarize", first, n)) return -1;
+  FS_ON_DEVICE(b);
+  TraceRange range_("flowsim:reduce");
+  const size_t B = b->d.n_reaches, bytes = (size_t)FS_SUM_NROWS * B * sizeof(double);
+  HIP_TRY(b->red_out[0].reserve(bytes));
+  const bool launched = with_real(b, [&](auto real) {
+    using R = decltype(real);
+    return fs::launch_summarize(reduce_args<R>(b, first, n), b->red_out[0].get<double>(), b->stream);
+  });
+  if (!launched) return fail(std::string("fs_batch_summarize") + kNoReduceKernels);
+  HIP_TRY(hipGetLastError());
+  return fetch(b, out, b->red_out[0].get(), bytes);
+}
+
+int fs_batch_lookup(fs_batch *b, int32_t first, int32_t n, int32_t x_row, int32_t y_row, const double *y_offset,
+                    const double *xq, int32_t n_q, const double *target, double *values, double *rmse, int32_t *info) {
+  if (!b) return fail("fs_batch_lookup: null handle");
+  if (!values && !rmse && !info) return fail("fs_batch_lookup: no output requested (values, rmse and info are all NULL)");
+  if (x_row < 0 || x_row > 3 || y_row < 0 || y_row > 3) return fail("fs_batch_lookup: x_row and y_row are 0..3 (h[0], Q[0], h[N-1], Q[N-1])");
+  if (n_q < 1 || n_q > 65535) return fail("fs_batch_lookup: n_q must be 1 .. 65535");
+  if (!xq) return fail("fs_batch_lookup: null query abscissae");
+  if (rmse && !target) return fail("fs_batch_lookup: rmse needs a target");
+  if (check_reduce_range(b, "fs_batch_lookup", first, n)) return -1;
+  FS_ON_DEVICE(b);
+  TraceRange range_("flowsim:reduce");
+  const size_t B = b->d.n_reaches;
+  HIP_TRY(hipStreamSynchronize(b->stream));      // an earlier call's kernels are through with the inputs
+  if (y_offset && upload_f64(b->red_in[0], y_offset, B)) return -1;
+  if (upload_f64(b->red_in[1], xq, (size_t)n_q)) return -1;
+  if (rmse && upload_f64(b->red_in[2], target, (size_t)n_q)) return -1;
+  // values [n_q][B], then rmse [B], then info [B]
+  const size_t n_val = (size_t)n_q * B;
+  HIP_TRY(b->red_out[1].reserve((n_val + B) * sizeof(double) + B * sizeof(int32_t)));
+  double *d_val = b->red_out[1].get<double>();
+  fs::LookupArgs l;
+  l.x_row = x_row; l.y_row = y_row; l.n_q = n_q;
+  l.y_offset = y_offset ? b->red_in[0].get<const double>() : nullptr;
+  l.xq = b->red_in[1].get<const double>(); l.target = rmse ? b->red_in[2].get<const double>() : nullptr;
+  l.values = d_val; l.rmse = rmse ? d_val + n_val : nullptr; l.info = info ? (int32_t *)(d_val + n_val + B) : nullptr;
+  const bool launched = with_real(b, [&](auto real) {
+    using R = decltype(real);
+    return fs::launch_lookup(reduce_args<R>(b, first, n), l, b->stream);
+  });
+  if (!launched) return fail(std::string("fs_batch_lookup") + kNoReduceKernels);
+  HIP_TRY(hipGetLastError());
+  if (values && fetch(b, values, l.values, n_val * sizeof(double))) return -1;
+  if (rmse && fetch(b, rmse, l.rmse, B * sizeof(double))) return -1;
+  if (info && fetch(b, info, l.info, B * sizeof(int32_t))) return -1;
+  return 0;
+}
+
+int fs_batch_bands(fs_batch *b, int32_t first, int32_t n, const double *q, int32_t n_q, double *moments, double *quantiles,
+                   int32_t *n_members) {
+  if (!b) return fail("fs_batch_bands: null handle");
+  if (!moments && !quantiles && !n_members) return fail("fs_batch_bands: no output requested (moments, quantiles and n_members are all NULL)");
+  if (n_q < 0 || n_q > fs::kBandMaxQ) return fail("fs_batch_bands: n_q must be 0 .. " + std::to_string(fs::kBandMaxQ));
+  if (n_q > 0 && !q) return fail("fs_batch_bands: null quantile levels");
+  for (int i = 0; i < n_q; ++i)
+    if (!(q[i] >= 0.0 && q[i] <= 1.0)) return fail("fs_batch_bands: quantile levels must be in [0, 1]");
+  if (check_reduce_range(b, "fs_batch_bands", first, n)) return -1;
+  FS_ON_DEVICE(b);
+  TraceRange range_("flowsim:reduce");
+  const bool want_q = quantiles && n_q > 0;
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  if (want_q && upload_f64(b->red_in[1], q, (size_t)n_q)) return -1;
+  // moments [n][4][4], then quantiles [n][4][n_q], then n_members [n]
+  const size_t n_mom = (size_t)n * 16, n_qu = want_q ? (size_t)n * 4 * n_q : 0;
+  HIP_TRY(b->red_out[2].reserve((n_mom + n_qu) * sizeof(double) + (size_t)n * sizeof(int32_t)));
+  double *d_mom = b->red_out[2].get<double>();
+  fs::BandArgs p;
+  p.q = want_q ? b->red_in[1].get<const double>() : nullptr; p.n_q = want_q ? n_q : 0;
+  p.moments = moments ? d_mom : nullptr; p.quantiles = want_q ? d_mom + n_mom : nullptr;
+  p.n_members = n_members ? (int32_t *)(d_mom + n_mom + n_qu) : nullptr;
+  const bool launched = with_real(b, [&](auto real) {
+    using R = decltype(real);
+    return fs::launch_bands(reduce_args<R>(b, first, n), p, b->stream);
+  });
+  if (!launched) return fail(std::string("fs_batch_bands") + kNoReduceKernels);
+  HIP_TRY(hipGetLastError());
+  if (moments && fetch(b, moments, p.moments, n_mom * sizeof(double))) return -1;
+  if (want_q && fetch(b, quantiles, p.quantiles, n_qu * sizeof(double))) return -1;
+  if (n_members && fetch(b, n_members, p.n_members, (size_t)n * sizeof(int32_t))) return -1;
   return 0;
 }
 

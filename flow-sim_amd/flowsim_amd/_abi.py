@@ -30,6 +30,11 @@ IC_LINEAR, IC_GVF, IC_STEADY = 0, 1, 2
 IC_SUPERCRITICAL, IC_CLAMPED, IC_FLOORED, IC_NO_ROOT = 1, 2, 4, 8
 TRACE_CAP = 64
 DERIVE_ALL = 255
+# rows of fs_batch_summarize (FS_SUM_* of the header)
+SUM_ROWS = ("levels", "q_in", "q_out", "q_net", "peak_q_in", "peak_q_in_level", "peak_q_out", "peak_q_out_level",
+            "peak_h_in", "peak_h_in_level", "peak_h_out", "peak_h_out_level", "median_in_level", "median_out_level")
+ROW_H_IN, ROW_Q_IN, ROW_H_OUT, ROW_Q_OUT = 0, 1, 2, 3      # x_row / y_row of fs_batch_lookup: h[0], Q[0], h[N-1], Q[N-1]
+BANDS_MAX_Q = 16
 ABI_VERSION = 3
 
 
@@ -84,6 +89,9 @@ SIGNATURES = {
     "fs_batch_derive": (C.c_int, [_P, C.c_int32, C.c_int32, _D, _D, _D, _D, _D, _D, _D, _D]),
     "fs_batch_derive_device": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32]),
     "fs_batch_derived_device_ptr": (_P, [_P, C.c_int32]),
+    "fs_batch_summarize": (C.c_int, [_P, C.c_int32, C.c_int32, _D]),
+    "fs_batch_lookup": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D, _D, C.c_int32, _D, _D, _D, _I]),
+    "fs_batch_bands": (C.c_int, [_P, C.c_int32, C.c_int32, _D, C.c_int32, _D, _D, _I]),
     "fs_batch_hydrograph_device_ptr": (_P, [_P]),
     "fs_batch_stream": (_P, [_P]),
     "fs_batch_last_step_ms": (C.c_double, [_P]),

@@ -387,6 +387,45 @@ class PreissmannBatch:
                 "derive")
         return out
 
+    # -- ensemble post-processing on the device (the hydrograph block is reduced where it is) ----
+    def summaries(self, first=0, n=None):
+        """The numbers of the reference's result summary (solver.py:203-229) for every reach over the levels [first, first + n):
+        dict name -> [B] with the names of _abi.SUM_ROWS.  Level indices are relative to `first` (multiply by the reach's dt); a
+        failed reach is summarised over the rows before its failing level, `levels` says how many."""
+        n = self.level + 1 - first if n is None else n
+        out = np.empty((len(A.SUM_ROWS), self.B))
+        A.check(self._lib.fs_batch_summarize(self._h, int(first), int(n), _dptr(out)), "summarize")
+        return {k: out[i] for i, k in enumerate(A.SUM_ROWS)}
+
+    def lookup(self, x_row, y_row, xq, y_offset=None, target=None, first=0, n=None):
+        """np.interp(xq, x_series, y_series + y_offset) for every reach (rows: _abi.ROW_*), dict(values [n_q, B], rmse [B] against
+        `target` or None, monotone [B]: False where x descends somewhere in the range - np.interp is not defined there, and the
+        values of that reach are those of a plain bisection)."""
+        n = self.level + 1 - first if n is None else n
+        xq = np.ascontiguousarray(xq, dtype=np.float64).reshape(-1)
+        off = None if y_offset is None else np.ascontiguousarray(np.broadcast_to(np.asarray(y_offset, dtype=np.float64), (self.B,)))
+        tgt = None if target is None else np.ascontiguousarray(target, dtype=np.float64).reshape(-1)
+        assert tgt is None or tgt.shape == xq.shape
+        values = np.empty((len(xq), self.B))
+        rmse = None if tgt is None else np.empty(self.B)
+        info = np.empty(self.B, dtype=np.int32)
+        opt = lambda a: None if a is None else _dptr(a)
+        A.check(self._lib.fs_batch_lookup(self._h, int(first), int(n), int(x_row), int(y_row), opt(off), _dptr(xq), len(xq), opt(tgt),
+                                          _dptr(values), opt(rmse), info.ctypes.data_as(A._I)), "lookup")
+        return dict(values=values, rmse=rmse, monotone=(info & 1) == 0)
+
+    def bands(self, quantiles=(0.05, 0.5, 0.95), first=0, n=None):
+        """Across the members, per level and signal: dict(min, max, mean, std [n, 4], quantiles [n, 4, n_q]: exact order
+        statistics, numpy's default method; n_members [n]).  Failed members are left out."""
+        n = self.level + 1 - first if n is None else n
+        q = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
+        mom = np.empty((n, 4, 4))
+        qu = np.empty((n, 4, len(q)))
+        cnt = np.empty(n, dtype=np.int32)
+        A.check(self._lib.fs_batch_bands(self._h, int(first), int(n), _dptr(q) if len(q) else None, len(q), _dptr(mom),
+                                         _dptr(qu) if len(q) else None, cnt.ctypes.data_as(A._I)), "bands")
+        return dict(min=mom[:, :, 0], max=mom[:, :, 1], mean=mom[:, :, 2], std=mom[:, :, 3], quantiles=qu, n_members=cnt)
+
     def last_step_ms(self):
         return self._lib.fs_batch_last_step_ms(self._h)
 

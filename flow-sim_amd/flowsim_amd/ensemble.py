@@ -8,7 +8,8 @@ from .batch import PreissmannBatch
 from .hydromodel.preissmann import boundary_to_spec
 
 
-def run_manning_ensemble(solver, n_main_values, tolerance=1e-4, max_iter=100, dtype="f64", device=0, monitor=True, initial="host"):
+def run_manning_ensemble(solver, n_main_values, tolerance=1e-4, max_iter=100, dtype="f64", device=0, monitor=True, initial="host",
+                         summaries=False, score=None, bands=None, hydrographs=True):
     """`solver`: a set-up (not yet run) PreissmannSolver whose channel provides geometry, boundaries
     and initial conditions; the initial conditions are shared by all members (the reference's
     members start from the same downstream level and the same flow; their GVF profiles differ
@@ -17,7 +18,14 @@ def run_manning_ensemble(solver, n_main_values, tolerance=1e-4, max_iter=100, dt
     initial="gvf": every member starts from its own backwater profile instead, marched on the device from the channel's
     downstream depth with the member's n (PreissmannBatch.init_state; channel.py:307-378) - no per-member set-up on the host.
 
-    Returns dict(hydrographs[nt, 4, B], iterations[nt, B], status[B])."""
+    Post-processing on the device, on the hydrograph block where it is (PreissmannBatch.summaries / lookup / bands):
+    summaries=True adds 'summaries' (dict of [B]: the numbers of the reference's result summary, see summary_text);
+    score=dict(xq, target=None, y_offset=None) adds 'score' (dict(values[n_q, B], rmse[B],
+    monotone[B]): the members' upstream level at the flows xq and its RMSE against the target, n_calibrate.py:55-67);
+    bands=(q, ...) adds 'bands' (min, max, mean, std [nt, 4], quantiles [nt, 4, n_q], n_members [nt] across the members);
+    hydrographs=False leaves the block on the device - at 32 768 members and 385 levels it is 400 MB.
+
+    Returns dict(hydrographs[nt, 4, B], iterations[nt, B], status[B]) and what the keywords above add."""
     if initial not in ("host", "gvf"):
         raise ValueError("initial must be 'host' or 'gvf'")
     ch = solver.channel
@@ -36,7 +44,26 @@ def run_manning_ensemble(solver, n_main_values, tolerance=1e-4, max_iter=100, dt
         else:
             b.set_state(ics[:, :, 0], ics[:, :, 1])
         b.step(nt - 1)
-        return dict(hydrographs=b.hydrographs(0, nt), iterations=b.iterations(0, nt), status=b.status())
+        out = dict(iterations=b.iterations(0, nt), status=b.status())
+        if hydrographs:
+            out = dict(hydrographs=b.hydrographs(0, nt), **out)
+        if summaries:
+            out["summaries"] = b.summaries(0, nt)
+        if score is not None:
+            out["score"] = b.lookup(A.ROW_Q_IN, A.ROW_H_IN, score["xq"],
+                                    y_offset=score.get("y_offset"), target=score.get("target"), first=0, n=nt)
+        if bands is not None:
+            out["bands"] = b.bands(bands, 0, nt)
+        return out
+
+
+def summary_text(summaries, r, time_step, spatial_step, duration):
+    """Member r's result summary in the reference's words (solver.py:188-233; Solver.summary writes the same block from a
+    single-channel run) from the numbers PreissmannBatch.summaries computed on the device."""
+    from .hydromodel.solver import summary_block
+    s = summaries
+    return summary_block(spatial_step, time_step, duration, s["q_net"][r], s["q_in"][r], s["peak_q_in"][r], s["peak_q_out"][r],
+                         s["median_in_level"][r], s["median_out_level"][r])
 
 
 def gvf_profiles(channel, n_main_values):

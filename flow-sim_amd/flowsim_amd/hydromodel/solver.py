@@ -12,6 +12,25 @@ from . import hydraulics
 from .channel import Channel
 
 
+def summary_block(spatial_step, time_step, duration, net_sum, inflow_sum, peak_in, peak_out, median_in_level, median_out_level) -> str:
+    """The text block of the reference's results file (solver.py:188-233) from its numbers: np.sum(Q_in - Q_out), np.sum(Q_in),
+    the two peaks and the median-volume levels.  Solver.summary computes them on the host, flowsim_amd.ensemble.summary_text takes
+    them from the device (PreissmannBatch.summaries)."""
+    from .utility import seconds_to_hms
+    imbalance = net_sum * time_step
+    pct = float(imbalance / time_step / inflow_sum) * 100
+    t_in, t_out = int(median_in_level) * time_step, int(median_out_level) * time_step
+    lines = [f'Spatial step = {spatial_step} m', f'Time step = {time_step} s',
+             f'Simulation duration = {seconds_to_hms(duration)}',
+             f'Mass imbalance (total inflow - total outflow) = {imbalance:.2f} m^3 = {pct:.4f}% of inflow.',
+             f'Peak inflow = {peak_in:.2f} m^3/s', f'Peak outflow = {peak_out:.2f} m^3/s',
+             f'Attenuation = {(peak_in - peak_out) / peak_in * 100:.2f}%',
+             f'Median volume entry time = {seconds_to_hms(t_in)}',
+             f'Median volume arrival time = {seconds_to_hms(t_out)}',
+             f'Median volume travel time = {seconds_to_hms(t_out - t_in)}']
+    return "\n".join(lines) + "\n"
+
+
 class Solver(ABC):
     def __init__(self, channel: Channel, time_step, spatial_step, simulation_time, regularization: bool = False,
                  fit_spatial_step: bool = True):
@@ -190,25 +209,13 @@ class Solver(ABC):
     def summary(self) -> str:
         """The text block of the reference's results file (solver.py:188-233): steps, duration, mass
         imbalance, peak attenuation and median-volume travel time."""
-        from .utility import seconds_to_hms
         q_in, q_out = np.asarray(self.flow)[:, 0], np.asarray(self.flow)[:, -1]
-        imbalance = np.sum(q_in - q_out) * self.time_step
-        pct = float(imbalance / self.time_step / np.sum(q_in)) * 100
-        peak_in, peak_out = np.max(q_in), np.max(q_out)
 
-        def median_time(q):
+        def median_level(q):
             cum = np.concatenate([[0.0], np.cumsum(q)[:-1]])          # sum(q[:i]) for i = 0..n-1
-            return int(np.argmax(cum >= 0.5 * cum[-1])) * self.time_step
-        t_in, t_out = median_time(q_in), median_time(q_out)
-        lines = [f'Spatial step = {self.spatial_step} m', f'Time step = {self.time_step} s',
-                 f'Simulation duration = {seconds_to_hms(self.total_sim_duration)}',
-                 f'Mass imbalance (total inflow - total outflow) = {imbalance:.2f} m^3 = {pct:.4f}% of inflow.',
-                 f'Peak inflow = {peak_in:.2f} m^3/s', f'Peak outflow = {peak_out:.2f} m^3/s',
-                 f'Attenuation = {(peak_in - peak_out) / peak_in * 100:.2f}%',
-                 f'Median volume entry time = {seconds_to_hms(t_in)}',
-                 f'Median volume arrival time = {seconds_to_hms(t_out)}',
-                 f'Median volume travel time = {seconds_to_hms(t_out - t_in)}']
-        return "\n".join(lines) + "\n"
+            return int(np.argmax(cum >= 0.5 * cum[-1]))
+        return summary_block(self.spatial_step, self.time_step, self.total_sim_duration, np.sum(q_in - q_out), np.sum(q_in),
+                             np.max(q_in), np.max(q_out), median_level(q_in), median_level(q_out))
 
     def _finalize(self, verbose):
         self._solved = True

@@ -342,6 +342,45 @@ enum { FS_DERIVE_LEVEL = 1, FS_DERIVE_AREA = 2, FS_DERIVE_TOP_WIDTH = 4, FS_DERI
 int fs_batch_derive_device(fs_batch *b, int32_t first_level, int32_t n_levels, int32_t fields);
 void *fs_batch_derived_device_ptr(fs_batch *b, int32_t field_index);
 
+/* ---- Ensemble post-processing on the device ----
+ * Three reductions of the boundary hydrograph block (what fs_batch_get_hydrographs downloads) over the levels [first, first + n),
+ * which must lie inside 0 .. fs_batch_level() (after fs_batch_restart: from the restart level on).  They read the block where it is,
+ * accumulate in fp64 whatever the batch dtype, copy only their results to the caller's host arrays, and synchronise.  A reach whose
+ * status is a failure (FS_MAX_ITER, FS_NAN, FS_STORAGE_RANGE, FS_TEAM_STALL; see the status enum) enters the per-reach reductions with
+ * the rows BEFORE its failing level only - the rows the status enum documents as complete - and is left out of the cross-member one;
+ * FS_ILL_CONDITIONED is a warning and changes nothing.
+ *
+ * fs_batch_summarize: the numbers of the reference's result summary (solver.py:203-229) for every reach, out[FS_SUM_NROWS][B].  Level
+ * indices are relative to `first`, as doubles; the caller multiplies by the reach's own dt.  The median-volume level is the reference's
+ * loop as written (solver.py:219-229): with cum_i = sum(Q[:i]), i = 0 .. m-1, the first i with cum_i >= 0.5 cum_{m-1}.  A reach that
+ * completed no row of the range reports FS_SUM_LEVELS 0, sums 0, peaks NaN and levels -1. */
+enum { FS_SUM_LEVELS = 0,            /* rows of the range this reach completed */
+       FS_SUM_Q_IN, FS_SUM_Q_OUT,    /* np.sum(Q_in), np.sum(Q_out) (solver.py:207) */
+       FS_SUM_Q_NET,                 /* np.sum(Q_in - Q_out), accumulated as the difference (solver.py:206) */
+       FS_SUM_PEAK_Q_IN,  FS_SUM_PEAK_Q_IN_LEVEL,      /* np.max / np.argmax (solver.py:211-212) */
+       FS_SUM_PEAK_Q_OUT, FS_SUM_PEAK_Q_OUT_LEVEL,
+       FS_SUM_PEAK_H_IN,  FS_SUM_PEAK_H_IN_LEVEL,
+       FS_SUM_PEAK_H_OUT, FS_SUM_PEAK_H_OUT_LEVEL,     /* depth, first index of the maximum */
+       FS_SUM_MEDIAN_IN_LEVEL, FS_SUM_MEDIAN_OUT_LEVEL,
+       FS_SUM_NROWS };
+int fs_batch_summarize(fs_batch *b, int32_t first, int32_t n, double *out);
+/* np.interp(x=xq, xp=x_series, fp=y_series + y_offset) for every reach, as cases/gerd_roseires/n_calibrate.py:55-67 and the Q= branch
+ * of model.run (model.py:105-113) call it: outside the range the end values, inside it the largest j with xp[j] <= x and
+ * fp[j] + (x - xp[j]) (fp[j+1] - fp[j]) / (xp[j+1] - xp[j]).  x_row, y_row: 0..3 = h[0], Q[0], h[N-1], Q[N-1].  y_offset: [B] or NULL
+ * (bed level -> stage).  xq[n_q], 1 <= n_q <= 65535, shared by the batch.  values: [n_q][B] or NULL.  rmse: [B] or NULL,
+ * sqrt(mean((values - target)^2)), needs target[n_q].  info: [B] or NULL, bit 0 = x descends somewhere in the range: np.interp is
+ * defined for nondecreasing xp only, the values of such a reach are those of a plain bisection and promise nothing against numpy.  A
+ * reach that completed no row of the range reports NaN.  At least one of values, rmse, info must be given. */
+int fs_batch_lookup(fs_batch *b, int32_t first, int32_t n, int32_t x_row, int32_t y_row, const double *y_offset,
+                    const double *xq, int32_t n_q, const double *target, double *values, double *rmse, int32_t *info);
+/* Across the members, per level and signal (np.min / max / mean / std / quantile over the members of fs_batch_get_hydrographs' rows):
+ * moments[n][4][4] = min, max, mean, std (ddof = 0; two passes) or NULL; quantiles[n][4][n_q] or NULL: the exact order statistics at
+ * the levels q[n_q] in [0, 1], 0 <= n_q <= 16, with numpy's default method "linear" (virtual index (m - 1) q, interpolated between its
+ * two neighbours); n_members[n] or NULL: the members that entered each level.  Failed members are left out of every level; a level of
+ * which no member remains reports 0 members and NaN.  At least one output must be given. */
+int fs_batch_bands(fs_batch *b, int32_t first, int32_t n, const double *q, int32_t n_q, double *moments, double *quantiles,
+                   int32_t *n_members);
+
 /* zero-copy access for device-side consumers (RCCL gather of hydrographs): device pointer to the
  * [max_levels][4][B] hydrograph block in the batch dtype, and the handle's hipStream_t */
 void *fs_batch_hydrograph_device_ptr(fs_batch *b);
