@@ -2,6 +2,7 @@
 
 `flowsim_amd._abi`   ctypes binding of the C ABI (include/flowsim_abi.h, libflowsim_hip.so)
 `flowsim_amd.batch`  PreissmannBatch: many independent reaches stepped on one GPU
+`flowsim_amd._pack`  the argument layouts of the C ABI as plain functions (numpy only, no library)
 `flowsim_amd.hydromodel`  the reference's Channel / Boundary / ... / PreissmannSolver interface
 """
 from . import _abi  # noqa: F401

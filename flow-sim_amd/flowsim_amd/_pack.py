@@ -1,0 +1,171 @@
+"""Python values -> the flat arrays the C ABI receives (include/flowsim_abi.h), without the library: numpy and the constants of _abi
+only, no arithmetic.  Every function returns C-contiguous arrays of the dtype and shape the call takes; batch.py passes them on.
+tests/test_batch_pack.py holds them on the CPU to the arrays the setters built before these functions existed, and to what
+fs::check_bc / fs::check_bc_per_reach accept."""
+import numpy as np
+
+from . import _abi as A
+
+_KIND_PARAMS = {
+    A.BC_FLOW_HYDROGRAPH: (), A.BC_STAGE_HYDROGRAPH: ("bed_level",), A.BC_FIXED_DEPTH: ("initial_depth",),
+    A.BC_NORMAL_DEPTH: ("bed_slope", "bed_level"), A.BC_RATING_POWER: ("a", "b", "stage_shift", "bed_level"),
+    A.BC_RATING_POLY: ("a", "b", "c", "stage_shift", "bed_level"),
+    A.BC_RATING_BLEND: ("stage0", "buffer", "lo0", "lo1", "lo2", "hi0", "hi1", "hi2", "dY", "bed_level"),
+    A.BC_STORAGE: ("surface_area", "min_stage", "Y_min", "Y_max", "bed_level"),
+}
+
+
+# -- scalar or array -> one value per reach / per node --------------------------------------------
+def per_reach(v, B, dtype=np.float64):
+    """scalar or [B] -> [B]"""
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dtype), (B,)))
+
+
+def opt_per_reach(v, B, dtype=np.float64):
+    return None if v is None else per_reach(v, B, dtype)
+
+
+def per_node(v, B, N):
+    """scalar, [N] or [B, N] -> [B, N]"""
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (B, N)))
+
+
+def bed_slope(v, B, N):
+    """(None | [N] | [B, N], per_reach) of init_state; None entries are the reference's undefined slope: NaN, which the library
+    refuses as the reference does"""
+    if v is None:
+        return None, 0
+    v = np.ascontiguousarray(np.array(v, dtype=np.float64))
+    assert v.shape in ((N,), (B, N))
+    return v, int(v.ndim == 2)
+
+
+# -- geometry -------------------------------------------------------------------------------------
+def n_override(v, B):
+    if v is None:
+        return None
+    v = np.ascontiguousarray(v, dtype=np.float64)
+    assert v.shape == (B,)
+    return v
+
+
+def uniform_params(trap, B, width, manning, z_us, z_ds, side_slope=None):
+    """[RU_NPARAM | TU_NPARAM, B]"""
+    p = np.empty((A.TU_NPARAM if trap else A.RU_NPARAM, B), dtype=np.float64)
+    p[A.RU_WIDTH], p[A.RU_MANNING], p[A.RU_Z_US], p[A.RU_Z_DS] = width, manning, z_us, z_ds
+    if trap:
+        p[A.TU_SIDE_SLOPE] = 0.0 if side_slope is None else side_slope
+    return p
+
+
+def geometry_table(geo, B, N, per_reach):
+    """[GEO_NPARAM, N], or with per_reach [B, GEO_NPARAM, N] (rows given as [N] are shared by the reaches)"""
+    tab = np.empty(((B,) if per_reach else ()) + (A.GEO_NPARAM, N), dtype=np.float64)
+    for i, k in enumerate(A.GEO_ROWS):
+        tab[..., i, :] = np.asarray(geo[k], dtype=np.float64)
+    return tab
+
+
+def irregular_arrays(geo, B, N):
+    """(table, n_pts int32, x, z, limits, per_reach); one channel per reach where irr_npts is [B, N]"""
+    per_reach = np.ndim(geo["irr_npts"]) == 2
+    lead = (B,) if per_reach else ()
+    cnt = np.ascontiguousarray(geo["irr_npts"], dtype=np.int32)
+    x = np.ascontiguousarray(geo["irr_x"], dtype=np.float64)
+    z = np.ascontiguousarray(geo["irr_z"], dtype=np.float64)
+    lim = np.ascontiguousarray(geo["irr_limits"], dtype=np.float64)
+    assert cnt.shape == lead + (N,) and x.shape == z.shape and x.shape[:-1] == lead + (N,) and lim.shape == lead + (N, 2)
+    return geometry_table(geo, B, N, per_reach), cnt, x, z, lim, per_reach
+
+
+# -- boundaries -----------------------------------------------------------------------------------
+def storage_curve_rows(out, params, stages, areas):
+    """FS_BC_STORAGE_CURVE into out [rows] (one reservoir) or [rows, B]: the FS_SC_* scalars (alpha 1 when absent, the others 0 when
+    absent or None, n_curve from the curve), then stages [n_curve(, B)], then areas; rows beyond those are left as they are"""
+    nf, nc = len(A.SC_NAMES), len(stages)
+    sc = {"alpha": 1.0, **params, "n_curve": float(nc)}
+    for i, k in enumerate(A.SC_NAMES):
+        v = sc.get(k)
+        out[i] = 0.0 if v is None else v
+    out[nf:nf + nc] = stages
+    out[nf + nc:nf + 2 * nc] = areas
+
+
+def _curve(params):
+    return np.asarray(params.get("curve", np.empty((0, 2))), dtype=np.float64)
+
+
+def bc_params(spec, B):
+    """(params | None, n_params, per_reach) of fs_batch_set_bc; KeyError for a kind without a device form"""
+    if spec.kind == A.BC_HOST_ROW:          # evaluated by the caller before every Newton iteration (set_host_rows / iterate)
+        return None, 3, 1
+    if spec.kind == A.BC_STORAGE_CURVE:
+        # one reservoir per reach where a scalar is [B] or the curve [B, n_curve, 2] (the others shared), else one for the batch
+        curve = _curve(spec.params)
+        per = curve.ndim == 3 or any(np.ndim(v) > 0 for k, v in spec.params.items() if k != "curve")
+        if per:
+            curve = np.broadcast_to(curve.reshape((-1,) + curve.shape[-2:]) if curve.size else np.empty((1, 0, 2)), (B,) + curve.shape[-2:])
+        else:
+            curve = curve.reshape(-1, 2)
+        p = np.empty((len(A.SC_NAMES) + 2 * curve.shape[-2],) + ((B,) if per else ()), dtype=np.float64)
+        storage_curve_rows(p, spec.params, curve[..., 0].T, curve[..., 1].T)
+        return p, p.shape[0], int(per)
+    names = _KIND_PARAMS[spec.kind]
+    vals = [np.asarray(spec.params[n], dtype=np.float64) for n in names]
+    per = any(v.ndim > 0 for v in vals)
+    p = np.empty((len(names),) + ((B,) if per else ()), dtype=np.float64)
+    for i, v in enumerate(vals):
+        p[i] = v
+    return (p if names else None), len(names), int(per)
+
+
+def bc_params_per_reach(specs, B):
+    """(kinds int32 [B], params [rows, B], rows) of fs_batch_set_bc_per_reach_wide; a kind without a device form gets zeros (the
+    library refuses it)"""
+    assert len(specs) == B
+    kinds = np.array([s.kind for s in specs], dtype=np.int32)
+    curves = {r: _curve(s.params).reshape(-1, 2) for r, s in enumerate(specs) if s.kind == A.BC_STORAGE_CURVE}
+    rows = max([A.BC_MAX_PARAMS] + [len(A.SC_NAMES) + 2 * len(c) for c in curves.values()])
+    p = np.zeros((rows, B), dtype=np.float64)
+    for r, s in enumerate(specs):
+        if r in curves:
+            storage_curve_rows(p[:, r], s.params, curves[r][:, 0], curves[r][:, 1])
+        else:
+            for i, name in enumerate(_KIND_PARAMS.get(s.kind, ())):
+                p[i, r] = float(s.params[name])
+    return kinds, p, rows
+
+
+def _pad_levels(out, t):
+    """the first min(L, n) rows of t [n, ...] into out [L, ...], the last of them repeated below"""
+    n = min(len(out), len(t))
+    out[:n] = t[:n]
+    out[n:] = t[n - 1]
+
+
+def bc_target(target, L, B):
+    """[n] (shared) or [n, B] -> [L, B]; None stays None"""
+    if target is None:
+        return None
+    t = np.asarray(target, dtype=np.float64)
+    tgt = np.empty((L, B), dtype=np.float64)
+    _pad_levels(tgt, t[:, None] if t.ndim == 1 else t)
+    return tgt
+
+
+def bc_target_per_reach(targets, L, B):
+    """one optional [n_r] per reach -> [L, B] (zeros for a reach without one); None where no reach has one"""
+    if all(t is None for t in targets):
+        return None
+    tgt = np.zeros((L, B), dtype=np.float64)
+    for r, t in enumerate(targets):
+        if t is not None:
+            _pad_levels(tgt[:, r], np.asarray(t, dtype=np.float64).reshape(-1))
+    return tgt
+
+
+def host_rows(dh, dq, res, B):
+    """[3, B]: d/dh, d/dQ, residual"""
+    rows = np.empty((3, B), dtype=np.float64)
+    rows[0], rows[1], rows[2] = dh, dq, res
+    return rows

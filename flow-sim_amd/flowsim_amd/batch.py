@@ -14,14 +14,8 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _abi as A
-
-_KIND_PARAMS = {
-    A.BC_FLOW_HYDROGRAPH: (), A.BC_STAGE_HYDROGRAPH: ("bed_level",), A.BC_FIXED_DEPTH: ("initial_depth",),
-    A.BC_NORMAL_DEPTH: ("bed_slope", "bed_level"), A.BC_RATING_POWER: ("a", "b", "stage_shift", "bed_level"),
-    A.BC_RATING_POLY: ("a", "b", "c", "stage_shift", "bed_level"),
-    A.BC_RATING_BLEND: ("stage0", "buffer", "lo0", "lo1", "lo2", "hi0", "hi1", "hi2", "dY", "bed_level"),
-    A.BC_STORAGE: ("surface_area", "min_stage", "Y_min", "Y_max", "bed_level"),
-}
+from . import _pack as P
+from ._pack import _KIND_PARAMS  # noqa: F401  (the parameter names per boundary kind)
 
 
 @dataclass
@@ -37,7 +31,16 @@ class BoundarySpec:
 
 
 def _dptr(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
+    return a.ctypes.data_as(A._D)
+
+
+def _iptr(a):
+    return a.ctypes.data_as(A._I)
+
+
+def _opt(a):
+    """an optional array argument: NULL where the caller gave none"""
+    return None if a is None else _dptr(a)
 
 
 class PreissmannBatch:
@@ -83,48 +86,33 @@ class PreissmannBatch:
                                               int(max_iter)), "set_scheme")
 
     def set_geometry_uniform(self, width, manning, z_us, z_ds, side_slope=None):
-        trap = self.mode == A.SEC_TRAP_UNIFORM
-        p = np.empty((A.TU_NPARAM if trap else A.RU_NPARAM, self.B), dtype=np.float64)
-        p[A.RU_WIDTH], p[A.RU_MANNING], p[A.RU_Z_US], p[A.RU_Z_DS] = width, manning, z_us, z_ds
-        if trap:
-            p[A.TU_SIDE_SLOPE] = 0.0 if side_slope is None else side_slope
+        p = P.uniform_params(self.mode == A.SEC_TRAP_UNIFORM, self.B, width, manning, z_us, z_ds, side_slope)
         A.check(self._lib.fs_batch_set_geometry_uniform(self._h, _dptr(p)), "set_geometry_uniform")
 
     def set_geometry_table(self, geo: dict, n_main_override: Optional[Sequence[float]] = None):
         """geo[k]: [N] (one channel shared by the batch) or [B, N] (one channel per reach: geometry ensembles, different
         rivers; rows of a shorter reach padded by repeating its last node, see set_reach_nodes)"""
         per_reach = any(np.ndim(geo[k]) == 2 for k in A.GEO_ROWS)
-        tab = np.empty((self.B, A.GEO_NPARAM, self.N) if per_reach else (A.GEO_NPARAM, self.N), dtype=np.float64)
-        for i, k in enumerate(A.GEO_ROWS):
-            if per_reach:
-                tab[:, i, :] = np.broadcast_to(np.asarray(geo[k], dtype=np.float64), (self.B, self.N))
-            else:
-                tab[i] = np.asarray(geo[k], dtype=np.float64)
-        ov = None
-        if n_main_override is not None:
-            ov = np.ascontiguousarray(n_main_override, dtype=np.float64)
-            assert ov.shape == (self.B,)
+        tab, ov = P.geometry_table(geo, self.B, self.N, per_reach), P.n_override(n_main_override, self.B)
         fn = self._lib.fs_batch_set_geometry_table_per_reach if per_reach else self._lib.fs_batch_set_geometry_table
-        A.check(fn(self._h, _dptr(tab), _dptr(ov) if ov is not None else None), "set_geometry_table")
+        A.check(fn(self._h, _dptr(tab), _opt(ov)), "set_geometry_table")
 
     def set_reach_nodes(self, n_nodes):
         """per-reach node counts (<= N of the batch): each reach its own channel length / grid (solver.py:34-38, :53-55)"""
         n = np.ascontiguousarray(n_nodes, dtype=np.int32)
         assert n.shape == (self.B,)
-        A.check(self._lib.fs_batch_set_reach_nodes(self._h, n.ctypes.data_as(A._I)), "set_reach_nodes")
+        A.check(self._lib.fs_batch_set_reach_nodes(self._h, _iptr(n)), "set_reach_nodes")
 
     def set_reach_scheme(self, theta=None, dt=None, dx=None):
         """per-reach theta / time step / spatial step (arrays [B]; None: the batch-wide value of set_scheme)"""
-        arrs = [None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (self.B,))) for v in (theta, dt, dx)]
-        A.check(self._lib.fs_batch_set_reach_scheme(self._h, *[None if a is None else _dptr(a) for a in arrs]), "set_reach_scheme")
+        arrs = [P.opt_per_reach(v, self.B) for v in (theta, dt, dx)]
+        A.check(self._lib.fs_batch_set_reach_scheme(self._h, *[_opt(a) for a in arrs]), "set_reach_scheme")
 
     def set_reach_tolerance(self, tolerance=None, max_iter=None):
         """per-reach convergence tolerance and iteration cap (arrays [B]; None: the batch-wide value of set_scheme): what each
         run(tolerance=, max_iter=) of the reference has of its own (preissmann.py:101)"""
-        tol = None if tolerance is None else np.ascontiguousarray(np.broadcast_to(np.asarray(tolerance, dtype=np.float64), (self.B,)))
-        mit = None if max_iter is None else np.ascontiguousarray(np.broadcast_to(np.asarray(max_iter, dtype=np.int32), (self.B,)))
-        A.check(self._lib.fs_batch_set_reach_tolerance(self._h, None if tol is None else _dptr(tol),
-                                                       None if mit is None else mit.ctypes.data_as(A._I)), "set_reach_tolerance")
+        tol, mit = P.opt_per_reach(tolerance, self.B), P.opt_per_reach(max_iter, self.B, np.int32)
+        A.check(self._lib.fs_batch_set_reach_tolerance(self._h, _opt(tol), None if mit is None else _iptr(mit)), "set_reach_tolerance")
 
     def set_boundary_per_reach(self, side: int, specs):
         """one BoundarySpec per reach, kinds free to differ: the closed-form kinds BC_FLOW_HYDROGRAPH .. BC_STORAGE and, in table /
@@ -132,113 +120,32 @@ class PreissmannBatch:
         curve of its own length) and BC_HOST_ROW on the reaches whose plugin has no device form (such a batch advances with
         iterate(), and set_host_rows() writes the rows of those reaches only); a spec's target is [n_levels] (sampled at that
         reach's own k * dt)"""
-        assert len(specs) == self.B
-        kinds = np.array([s.kind for s in specs], dtype=np.int32)
-        curves = {r: np.asarray(s.params.get("curve", np.empty((0, 2))), dtype=np.float64).reshape(-1, 2)
-                  for r, s in enumerate(specs) if s.kind == A.BC_STORAGE_CURVE}
-        rows = max([A.BC_MAX_PARAMS] + [len(A.SC_NAMES) + 2 * len(c) for c in curves.values()])
-        p = np.zeros((rows, self.B), dtype=np.float64)
-        tgt = None
-        for r, s in enumerate(specs):
-            if s.kind == A.BC_STORAGE_CURVE:       # the FS_SC_* scalars (missing ones 0, alpha 1), then stages, then areas
-                sc = {"alpha": 1.0}
-                sc.update({k: v for k, v in s.params.items() if k != "curve"})
-                sc["n_curve"] = float(len(curves[r]))
-                nf, nc = len(A.SC_NAMES), len(curves[r])
-                p[:nf, r] = [float(sc.get(k) or 0.0) for k in A.SC_NAMES]
-                p[nf:nf + nc, r] = curves[r][:, 0]
-                p[nf + nc:nf + 2 * nc, r] = curves[r][:, 1]
-            else:
-                for i, name in enumerate(_KIND_PARAMS.get(s.kind, ())):
-                    p[i, r] = float(s.params[name])
-            if s.target is not None:
-                if tgt is None:
-                    tgt = np.zeros((self.L, self.B), dtype=np.float64)
-                t = np.asarray(s.target, dtype=np.float64).reshape(-1)
-                n = min(self.L, t.shape[0])
-                tgt[:n, r] = t[:n]
-                tgt[n:, r] = t[n - 1]
-        A.check(self._lib.fs_batch_set_bc_per_reach_wide(self._h, side, kinds.ctypes.data_as(A._I), _dptr(p), rows,
-                                                         _dptr(tgt) if tgt is not None else None), "set_boundary_per_reach")
+        kinds, p, rows = P.bc_params_per_reach(specs, self.B)
+        tgt = P.bc_target_per_reach([s.target for s in specs], self.L, self.B)
+        A.check(self._lib.fs_batch_set_bc_per_reach_wide(self._h, side, _iptr(kinds), _dptr(p), rows, _opt(tgt)), "set_boundary_per_reach")
 
     def set_geometry_irregular(self, geo: dict, n_main_override: Optional[Sequence[float]] = None):
         """geo: the TABLE rows plus irr_x / irr_z [N, P] (rows padded beyond irr_npts), irr_npts [N]
-        (0 = trapezoid-family node) and irr_limits [N, 2] (IrregularSection.left/right_fp_limit)."""
-        per_reach = np.ndim(geo["irr_npts"]) == 2          # one channel per reach: irr_npts [B, N], irr_x / irr_z [B, N, P], irr_limits [B, N, 2]
-        lead = (self.B,) if per_reach else ()
-        tab = np.empty(lead + (A.GEO_NPARAM, self.N), dtype=np.float64)
-        for i, k in enumerate(A.GEO_ROWS):
-            tab[..., i, :] = np.asarray(geo[k], dtype=np.float64)
-        cnt = np.ascontiguousarray(geo["irr_npts"], dtype=np.int32)
-        x = np.ascontiguousarray(geo["irr_x"], dtype=np.float64)
-        z = np.ascontiguousarray(geo["irr_z"], dtype=np.float64)
-        lim = np.ascontiguousarray(geo["irr_limits"], dtype=np.float64)
-        assert cnt.shape == lead + (self.N,) and x.shape == z.shape and x.shape[:-1] == lead + (self.N,) and lim.shape == lead + (self.N, 2)
-        ov = None
-        if n_main_override is not None:
-            ov = np.ascontiguousarray(n_main_override, dtype=np.float64)
-            assert ov.shape == (self.B,)
+        (0 = trapezoid-family node) and irr_limits [N, 2] (IrregularSection.left/right_fp_limit); one channel per reach:
+        irr_npts [B, N], irr_x / irr_z [B, N, P], irr_limits [B, N, 2]"""
+        tab, cnt, x, z, lim, per_reach = P.irregular_arrays(geo, self.B, self.N)
+        ov = P.n_override(n_main_override, self.B)
         fn = self._lib.fs_batch_set_geometry_irregular_per_reach if per_reach else self._lib.fs_batch_set_geometry_irregular
-        A.check(fn(self._h, _dptr(tab), cnt.ctypes.data_as(A._I), x.shape[-1], _dptr(x), _dptr(z), _dptr(lim),
-                   _dptr(ov) if ov is not None else None), "set_geometry_irregular")
+        A.check(fn(self._h, _dptr(tab), _iptr(cnt), x.shape[-1], _dptr(x), _dptr(z), _dptr(lim), _opt(ov)), "set_geometry_irregular")
 
     def set_boundary(self, side: int, spec: BoundarySpec):
-        if spec.kind == A.BC_HOST_ROW:
-            # evaluated by the caller before every Newton iteration (set_host_rows / iterate)
-            A.check(self._lib.fs_batch_set_bc(self._h, side, spec.kind, None, 3, 1, None), "set_boundary")
-            return
-        if spec.kind == A.BC_STORAGE_CURVE:
-            # general LumpedStorage: the FS_SC_* scalars (missing ones default to 0, alpha to 1) + the area curve
-            curve = np.asarray(spec.params.get("curve", np.empty((0, 2))), dtype=np.float64)
-            sc = {"alpha": 1.0}
-            sc.update({k: v for k, v in spec.params.items() if k != "curve"})
-            per_reach = curve.ndim == 3 or any(np.ndim(v) > 0 for v in sc.values() if v is not None)
-            if per_reach:       # one reservoir per reach: scalars [B] (or shared), curve [B, n_curve, 2] (or shared [n_curve, 2])
-                curve = np.broadcast_to(curve.reshape((-1,) + curve.shape[-2:]) if curve.size else np.empty((1, 0, 2)), (self.B,) + curve.shape[-2:])
-                nc = curve.shape[1]
-                sc["n_curve"] = float(nc)
-                p = np.empty((len(A.SC_NAMES) + 2 * nc, self.B), dtype=np.float64)
-                for i, k in enumerate(A.SC_NAMES):
-                    v = sc.get(k)
-                    p[i] = 0.0 if v is None else v
-                p[len(A.SC_NAMES):len(A.SC_NAMES) + nc] = curve[:, :, 0].T
-                p[len(A.SC_NAMES) + nc:] = curve[:, :, 1].T
-                A.check(self._lib.fs_batch_set_bc(self._h, side, spec.kind, _dptr(p), p.shape[0], 1, None), "set_boundary")
-                return
-            curve = curve.reshape(-1, 2)
-            sc["n_curve"] = float(len(curve))
-            p = np.concatenate([[float(sc.get(k) or 0.0) for k in A.SC_NAMES], curve[:, 0], curve[:, 1]])
-            A.check(self._lib.fs_batch_set_bc(self._h, side, spec.kind, _dptr(p), len(p), 0, None), "set_boundary")
-            return
-        names = _KIND_PARAMS[spec.kind]
-        vals = [np.asarray(spec.params[n], dtype=np.float64) for n in names]
-        per_reach = any(v.ndim > 0 for v in vals)
-        if per_reach:
-            p = np.empty((len(names), self.B), dtype=np.float64)
-            for i, v in enumerate(vals):
-                p[i] = v
-        else:
-            p = np.array([float(v) for v in vals], dtype=np.float64)
-        tgt = None
-        if spec.target is not None:
-            t = np.asarray(spec.target, dtype=np.float64)
-            tgt = np.empty((self.L, self.B), dtype=np.float64)
-            n = min(self.L, t.shape[0])
-            tgt[:n] = t[:n, None] if t.ndim == 1 else t[:n]
-            tgt[n:] = tgt[n - 1]
-        A.check(self._lib.fs_batch_set_bc(self._h, side, spec.kind, _dptr(p) if len(names) else None, len(names),
-                                          1 if per_reach else 0, _dptr(tgt) if tgt is not None else None),
-                "set_boundary")
+        """one kind for the batch, its parameters shared or [B]; BC_HOST_ROW and BC_STORAGE_CURVE follow no hydrograph"""
+        p, n_params, per_reach = P.bc_params(spec, self.B)
+        tgt = None if spec.kind in (A.BC_HOST_ROW, A.BC_STORAGE_CURVE) else P.bc_target(spec.target, self.L, self.B)
+        A.check(self._lib.fs_batch_set_bc(self._h, side, spec.kind, _opt(p), n_params, per_reach, _opt(tgt)), "set_boundary")
 
     def set_state(self, h, Q):
-        h = np.ascontiguousarray(np.broadcast_to(np.asarray(h, dtype=np.float64), (self.B, self.N)))
-        Q = np.ascontiguousarray(np.broadcast_to(np.asarray(Q, dtype=np.float64), (self.B, self.N)))
+        h, Q = P.per_node(h, self.B, self.N), P.per_node(Q, self.B, self.N)
         A.check(self._lib.fs_batch_set_state(self._h, _dptr(h), _dptr(Q)), "set_state")
 
     def set_state_uniform(self, h, Q):
         """Steady-state IC of prismatic reaches: one depth and one flow per reach (channel.py:296-305)."""
-        h = np.ascontiguousarray(np.broadcast_to(np.asarray(h, dtype=np.float64), (self.B,)))
-        Q = np.ascontiguousarray(np.broadcast_to(np.asarray(Q, dtype=np.float64), (self.B,)))
+        h, Q = P.per_reach(h, self.B), P.per_reach(Q, self.B)
         A.check(self._lib.fs_batch_set_state_uniform(self._h, _dptr(h), _dptr(Q)), "set_state_uniform")
 
     IC_METHODS = {"linear": A.IC_LINEAR, "GVF_equation": A.IC_GVF, "steady-state": A.IC_STEADY}      # Channel's interpolation_method names
@@ -252,18 +159,11 @@ class PreissmannBatch:
         Returns dict(flags[B], node[B]): the IC_* bits of each reach and the node of its first supercritical evaluation (-1).
         strict=True raises the reference's RuntimeError for the first reach whose march met Fr > 1 (its depth is NaN upstream
         of that node; the other reaches are complete)."""
-        per = lambda v: None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (self.B,)))
-        flow, depth_ds, depth_us = per(flow), per(depth_ds), per(depth_us)
-        per_reach = 0
-        if bed_slope is not None:
-            # (None entries are the reference's undefined slope: NaN, which the library refuses as the reference does)
-            bed_slope = np.ascontiguousarray(np.array(bed_slope, dtype=np.float64))
-            assert bed_slope.shape in ((self.N,), (self.B, self.N))
-            per_reach = int(bed_slope.ndim == 2)
+        flow, depth_ds, depth_us = P.per_reach(flow, self.B), P.opt_per_reach(depth_ds, self.B), P.opt_per_reach(depth_us, self.B)
+        bed_slope, per_reach = P.bed_slope(bed_slope, self.B, self.N)
         info = np.empty((2, self.B), dtype=np.int32)
-        opt = lambda a: None if a is None else _dptr(a)
-        A.check(self._lib.fs_batch_init_state(self._h, self.IC_METHODS[method], _dptr(flow), opt(depth_us), opt(depth_ds), opt(bed_slope),
-                                              per_reach, info.ctypes.data_as(A._I)), "init_state")
+        A.check(self._lib.fs_batch_init_state(self._h, self.IC_METHODS[method], _dptr(flow), _opt(depth_us), _opt(depth_ds), _opt(bed_slope),
+                                              per_reach, _iptr(info)), "init_state")
         out = dict(flags=info[0].copy(), node=info[1].copy())
         bad = np.flatnonzero(out["flags"] & A.IC_SUPERCRITICAL)
         if strict and len(bad):
@@ -291,9 +191,7 @@ class PreissmannBatch:
     def set_host_rows(self, side: int, dh, dq, res):
         """Boundary row (d/dh, d/dQ, residual) of every reach at the current Newton vector (BC_HOST_ROW sides; with per-reach
         kinds the entries of the reaches whose boundary the device evaluates are ignored)."""
-        rows = np.empty((3, self.B), dtype=np.float64)
-        rows[0], rows[1], rows[2] = dh, dq, res
-        A.check(self._lib.fs_batch_set_host_rows(self._h, side, _dptr(rows)), "set_host_rows")
+        A.check(self._lib.fs_batch_set_host_rows(self._h, side, _dptr(P.host_rows(dh, dq, res, self.B))), "set_host_rows")
 
     def boundary_iterate(self):
         """[4, B]: h[0], Q[0], h[N-1], Q[N-1] of the current Newton vector."""
@@ -303,15 +201,17 @@ class PreissmannBatch:
 
     def restart(self, level: int, h, Q, h_guess, Q_guess, storage_stage=None):
         """Continue bit-exactly from `level`: state, Newton start vector of level + 1 and reservoir stage."""
-        arrs = [np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (self.B, self.N)))
-                for a in (h, Q, h_guess, Q_guess)]
-        st = None if storage_stage is None else np.ascontiguousarray(np.broadcast_to(np.asarray(storage_stage, dtype=np.float64), (self.B,)))
-        A.check(self._lib.fs_batch_restart(self._h, int(level), *[_dptr(a) for a in arrs], _dptr(st) if st is not None else None),
-                "restart")
+        arrs = [P.per_node(a, self.B, self.N) for a in (h, Q, h_guess, Q_guess)]
+        st = P.opt_per_reach(storage_stage, self.B)
+        A.check(self._lib.fs_batch_restart(self._h, int(level), *[_dptr(a) for a in arrs], _opt(st)), "restart")
 
     @property
     def level(self):
         return self._lib.fs_batch_level(self._h)
+
+    def _span(self, first, n):
+        """the level count of a [first, first + n) range: up to the current level unless given"""
+        return self.level - first + 1 if n is None else n
 
     # -- results --------------------------------------------------------------------------
     def state(self, out=None):
@@ -329,26 +229,25 @@ class PreissmannBatch:
 
     def hydrographs(self, first=0, n=None):
         """[n, 4, B]: depth[k,0], flow[k,0], depth[k,-1], flow[k,-1]."""
-        n = self.level + 1 - first if n is None else n
+        n = self._span(first, n)
         out = np.empty((n, 4, self.B))
         A.check(self._lib.fs_batch_get_hydrographs(self._h, first, n, _dptr(out)), "get_hydrographs")
         return out
 
     def iterations(self, first=0, n=None):
-        n = self.level + 1 - first if n is None else n
+        n = self._span(first, n)
         out = np.empty((n, self.B), dtype=np.int32)
-        A.check(self._lib.fs_batch_get_iterations(self._h, first, n, out.ctypes.data_as(C.POINTER(C.c_int32))),
-                "get_iterations")
+        A.check(self._lib.fs_batch_get_iterations(self._h, first, n, _iptr(out)), "get_iterations")
         return out
 
     def status(self):
         out = np.empty(self.B, dtype=np.int32)
-        A.check(self._lib.fs_batch_get_status(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))), "get_status")
+        A.check(self._lib.fs_batch_get_status(self._h, _iptr(out)), "get_status")
         return out
 
     def history_arrays(self, first=0, n=None):
         """depth, flow [n, B, N] (needs history=True)."""
-        n = self.level + 1 - first if n is None else n
+        n = self._span(first, n)
         h = np.empty((n, self.B, self.N)); Q = np.empty((n, self.B, self.N))
         A.check(self._lib.fs_batch_get_history(self._h, first, n, _dptr(h), _dptr(Q)), "get_history")
         return h, Q
@@ -360,14 +259,14 @@ class PreissmannBatch:
 
     def residual_trace(self, first=0, n=None):
         """[n, TRACE_CAP, B] ||R|| per Newton iteration (needs trace=True); zeros beyond a level's count."""
-        n = self.level + 1 - first if n is None else n
+        n = self._span(first, n)
         out = np.empty((n, A.TRACE_CAP, self.B))
         A.check(self._lib.fs_batch_get_residual_trace(self._h, first, n, _dptr(out)), "get_residual_trace")
         return out
 
     def storage_stages(self, first=0, n=None):
         """[n, B] reservoir stage per time level (storage boundary only)."""
-        n = self.level + 1 - first if n is None else n
+        n = self._span(first, n)
         out = np.empty((n, self.B))
         A.check(self._lib.fs_batch_get_storage_stages(self._h, first, n, _dptr(out)), "get_storage_stages")
         return out
@@ -377,12 +276,12 @@ class PreissmannBatch:
     def derive(self, first=0, n=None, fields=None):
         """Solver.prepare_results on the device (needs history=True): dict name -> [n, B, N] plus
         peak_amplitude [B, N]."""
-        n = self.level + 1 - first if n is None else n
+        n = self._span(first, n)
         want = set(self.DERIVED + ("peak_amplitude",)) if fields is None else set(fields)
         out = {k: np.empty((n, self.B, self.N)) for k in self.DERIVED if k in want}
         if "peak_amplitude" in want:
             out["peak_amplitude"] = np.empty((self.B, self.N))
-        ptr = lambda k: _dptr(out[k]) if k in out else None
+        ptr = lambda k: _opt(out.get(k))
         A.check(self._lib.fs_batch_derive(self._h, first, n, *[ptr(k) for k in self.DERIVED], ptr("peak_amplitude")),
                 "derive")
         return out
@@ -392,7 +291,7 @@ class PreissmannBatch:
         """The numbers of the reference's result summary (solver.py:203-229) for every reach over the levels [first, first + n):
         dict name -> [B] with the names of _abi.SUM_ROWS.  Level indices are relative to `first` (multiply by the reach's dt); a
         failed reach is summarised over the rows before its failing level, `levels` says how many."""
-        n = self.level + 1 - first if n is None else n
+        n = self._span(first, n)
         out = np.empty((len(A.SUM_ROWS), self.B))
         A.check(self._lib.fs_batch_summarize(self._h, int(first), int(n), _dptr(out)), "summarize")
         return {k: out[i] for i, k in enumerate(A.SUM_ROWS)}
@@ -401,29 +300,28 @@ class PreissmannBatch:
         """np.interp(xq, x_series, y_series + y_offset) for every reach (rows: _abi.ROW_*), dict(values [n_q, B], rmse [B] against
         `target` or None, monotone [B]: False where x descends somewhere in the range - np.interp is not defined there, and the
         values of that reach are those of a plain bisection)."""
-        n = self.level + 1 - first if n is None else n
+        n = self._span(first, n)
         xq = np.ascontiguousarray(xq, dtype=np.float64).reshape(-1)
-        off = None if y_offset is None else np.ascontiguousarray(np.broadcast_to(np.asarray(y_offset, dtype=np.float64), (self.B,)))
+        off = P.opt_per_reach(y_offset, self.B)
         tgt = None if target is None else np.ascontiguousarray(target, dtype=np.float64).reshape(-1)
         assert tgt is None or tgt.shape == xq.shape
         values = np.empty((len(xq), self.B))
         rmse = None if tgt is None else np.empty(self.B)
         info = np.empty(self.B, dtype=np.int32)
-        opt = lambda a: None if a is None else _dptr(a)
-        A.check(self._lib.fs_batch_lookup(self._h, int(first), int(n), int(x_row), int(y_row), opt(off), _dptr(xq), len(xq), opt(tgt),
-                                          _dptr(values), opt(rmse), info.ctypes.data_as(A._I)), "lookup")
+        A.check(self._lib.fs_batch_lookup(self._h, int(first), int(n), int(x_row), int(y_row), _opt(off), _dptr(xq), len(xq), _opt(tgt),
+                                          _dptr(values), _opt(rmse), _iptr(info)), "lookup")
         return dict(values=values, rmse=rmse, monotone=(info & 1) == 0)
 
     def bands(self, quantiles=(0.05, 0.5, 0.95), first=0, n=None):
         """Across the members, per level and signal: dict(min, max, mean, std [n, 4], quantiles [n, 4, n_q]: exact order
         statistics, numpy's default method; n_members [n]).  Failed members are left out."""
-        n = self.level + 1 - first if n is None else n
+        n = self._span(first, n)
         q = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
         mom = np.empty((n, 4, 4))
         qu = np.empty((n, 4, len(q)))
         cnt = np.empty(n, dtype=np.int32)
-        A.check(self._lib.fs_batch_bands(self._h, int(first), int(n), _dptr(q) if len(q) else None, len(q), _dptr(mom),
-                                         _dptr(qu) if len(q) else None, cnt.ctypes.data_as(A._I)), "bands")
+        A.check(self._lib.fs_batch_bands(self._h, int(first), int(n), _opt(q if len(q) else None), len(q), _dptr(mom),
+                                         _opt(qu if len(q) else None), _iptr(cnt)), "bands")
         return dict(min=mom[:, :, 0], max=mom[:, :, 1], mean=mom[:, :, 2], std=mom[:, :, 3], quantiles=qu, n_members=cnt)
 
     def last_step_ms(self):
@@ -444,7 +342,7 @@ class PreissmannBatch:
 
     def derive_device(self, first=0, n=None, fields=A.DERIVE_ALL):
         """prepare_results with the results left on the device; returns {name: device pointer}."""
-        n = self.level + 1 - first if n is None else n
+        n = self._span(first, n)
         A.check(self._lib.fs_batch_derive_device(self._h, first, n, int(fields)), "derive_device")
         names = self.DERIVED + ("peak_amplitude",)
         return {k: self._lib.fs_batch_derived_device_ptr(self._h, i) for i, k in enumerate(names) if fields & (1 << i)}
