@@ -44,6 +44,16 @@ class GerdHydrograph(Hydrograph):
             return cap
         return max(min(inflow, cap), self.turbine_flow)
 
+    @staticmethod
+    def pool_spec():
+        """the reservoir as data, from the constants build() and outlet_capacity() use: what PreissmannBatch.route_pool takes to
+        route every member of an ensemble on the device"""
+        from flowsim_amd.forcing import PoolSpec
+        curve = np.loadtxt(settings.gerd_volume_curve_path, delimiter=",", dtype=np.float64)
+        return PoolSpec(curve_stage=curve[:, 1], curve_volume=curve[:, 0],
+                        weirs=[(C_GATED, CREST_GATED, CREST_STEPPED), (C_STEPPED, CREST_STEPPED), (C_EMERGENCY, CREST_EMERGENCY)],
+                        base_flow=TURBINE_FLOW, vol_scale=1e-6, z_lo=CREST_GATED, z_hi=645.0)      # build's own bracket: brentq(a=CREST_GATED, b=645)
+
     def build(self, inflow_hydrograph, time_step, duration, initial_stage):
         curve = np.loadtxt(settings.gerd_volume_curve_path, delimiter=",", dtype=np.float64)
         vols, stages = curve[:, 0], curve[:, 1]                       # [1e6 m3], [m]

@@ -23,6 +23,7 @@
 
 #include "fs_buffer.hpp"
 #include "fs_entries.hpp"
+#include "fs_forcing.hpp"
 #include "fs_host_pack.hpp"
 #include "fs_init_state.hpp"
 #include "fs_reduce.hpp"
@@ -43,8 +44,13 @@ struct TraceRange {
 FS_ACTIVE_LIST(FS_DECLARE)
 #else
 // an experiment build is this translation unit alone, with a few step kernels: it has no initial-condition kernels (fs_part_init.hip)
-// and no post-processing kernels (fs_part_reduce.hip), and fs_batch_init_state, fs_batch_summarize, ... say so
+// no post-processing kernels (fs_part_reduce.hip) and no forcing kernels (fs_part_forcing.hip), and fs_batch_init_state,
+// fs_batch_summarize, fs_batch_set_bc_sampled ... say so
 namespace fs {
+bool launch_sample_target(const SampleArgs<double> &, hipStream_t) { return false; }
+bool launch_sample_target(const SampleArgs<float> &, hipStream_t) { return false; }
+bool launch_route_pool(const PoolArgs<double> &, hipStream_t) { return false; }
+bool launch_route_pool(const PoolArgs<float> &, hipStream_t) { return false; }
 bool launch_init_state(int, const InitArgs<double> &, hipStream_t) { return false; }
 bool launch_init_state(int, const InitArgs<float> &, hipStream_t) { return false; }
 bool launch_summarize(const ReduceArgs<double> &, double *, hipStream_t) { return false; }
@@ -237,6 +243,11 @@ struct fs_batch : Timeline {
   fs::DeviceBuffer ic_info;             // int32 [2][B]: what fs_batch_init_state reports per reach (allocated on first use)
   fs::DeviceBuffer red_in[3];           // double: what the caller handed to the last fs_batch_lookup / fs_batch_bands (offsets, abscissae or levels, targets)
   fs::DeviceBuffer red_out[3];          // results of the last fs_batch_summarize / lookup / bands, kept and reused (grown, never shrunk)
+  fs::DeviceBuffer frc_in[2][6];        // double / int32: what fs_batch_set_bc_sampled was handed per side (times, values, table_of, scale, offset, shift)
+  fs::DeviceBuffer frc_dt;              // double [B]: the per-reach time steps as the caller gave them (the forcing kernels compute in fp64), or empty
+  fs::DeviceBuffer pool_in[5];          // double: fs_batch_route_pool's curve stages, curve volumes, weirs, initial stages, weir multipliers
+  fs::DeviceBuffer pool_stage;          // double [max_levels][B]: the pool stages of the last fs_batch_route_pool
+  fs::DeviceBuffer pool_info;           // int32 [2][B]: what it reports per member
   fs::DeviceBuffer dbg;
   Staging stage;                        // pinned chunks for large host <-> device transfers
   fs::DeviceBuffer kc_scratch;          // long reaches: level constants [B][4][passes * 64 W M]
@@ -649,6 +660,17 @@ int fetch(fs_batch *b, void *dst, const void *dev, size_t bytes) {
 
 const char kNoReduceKernels[] = ": this build has no post-processing kernels";
 
+// ---- forcing on the device (fs_forcing.hpp) ----
+
+// the per-reach time steps in fp64 for the forcing kernels (nullptr: the batch's dt)
+int forcing_reach_dt(fs_batch *b, const double **out) {
+  *out = nullptr;
+  if (b->rs_host[1].empty()) { b->frc_dt.reset(); return 0; }
+  if (upload_f64(b->frc_dt, b->rs_host[1].data(), b->rs_host[1].size())) return -1;
+  *out = b->frc_dt.get<const double>();
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1029,6 +1051,126 @@ int fs_batch_init_state(fs_batch *b, int32_t method, const double *flow, const d
     HIP_TRY(hipStreamSynchronize(b->stream));
   }
   return 0;
+}
+
+int fs_batch_set_bc_sampled(fs_batch *b, int32_t side, int32_t kind, const double *params, int32_t n_params, const double *times,
+                            const double *values, int32_t n_pts, int32_t n_tables, const int32_t *table_of, const double *scale,
+                            const double *offset, const double *shift) {
+  if (!b) return fail("fs_batch_set_bc_sampled: null handle");
+  if (check_side("fs_batch_set_bc_sampled", side)) return -1;
+  if (kind != FS_BC_FLOW_HYDROGRAPH && kind != FS_BC_STAGE_HYDROGRAPH)
+    return fail("fs_batch_set_bc_sampled: kind must be FS_BC_FLOW_HYDROGRAPH or FS_BC_STAGE_HYDROGRAPH");
+  if (!b->have_scheme) return fail("fs_batch_set_bc_sampled: the scheme (fs_batch_set_scheme: dt) must be set first");
+  const size_t B = b->d.n_reaches, L = b->d.max_levels;
+  const bool tables = b->d.section_mode == FS_SEC_TABLE || b->d.section_mode == FS_SEC_IRREGULAR;
+  if (const char *err = fs::check_bc(side, kind, params, n_params, 0, true, B, tables)) return fail(err);
+  if (const char *err = fs::check_sampled_tables(times, values, n_pts, n_tables, table_of, B)) return fail(err);
+  FS_ON_DEVICE(b);
+  HIP_TRY(hipStreamSynchronize(b->stream));      // an earlier call's kernels are through with the inputs
+  b->have_bc[side] = false;                      // (until the target is filled: a failure below leaves the side unset, not half set)
+  if (replace_bc_buffers(b, side, params, (size_t)n_params, nullptr)) return -1;
+  HIP_TRY(b->bc_target[side].ensure(L * B * b->esz));
+  fs::DeviceBuffer *in = b->frc_in[side];
+  if (upload_f64(in[0], times, (size_t)n_pts) || upload_f64(in[1], values, (size_t)n_tables * n_pts)) return -1;
+  if (table_of) {
+    HIP_TRY(in[2].reserve(B * sizeof(int32_t)));
+    HIP_TRY(hipMemcpy(in[2].get(), table_of, B * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  const double *per[3] = {scale, offset, shift};
+  for (int i = 0; i < 3; ++i)
+    if (per[i] && upload_f64(in[3 + i], per[i], B)) return -1;
+  const double *reach_dt;
+  if (forcing_reach_dt(b, &reach_dt)) return -1;
+  {
+    TraceRange range_("flowsim:forcing");
+    const bool launched = with_real(b, [&](auto real) {
+      using R = decltype(real);
+      fs::SampleArgs<R> a;
+      a.target = b->bc_target[side].get<R>(); a.L = (int32_t)L; a.B = (int32_t)B; a.n_pts = n_pts; a.n_tables = n_tables;
+      a.times = in[0].get<const double>(); a.values = in[1].get<const double>();
+      a.table_of = table_of ? in[2].get<const int32_t>() : nullptr;
+      a.scale = scale ? in[3].get<const double>() : nullptr; a.offset = offset ? in[4].get<const double>() : nullptr;
+      a.shift = shift ? in[5].get<const double>() : nullptr;
+      a.reach_dt = reach_dt; a.dt = b->dt;
+      return fs::launch_sample_target(a, b->stream);
+    });
+    if (!launched) return fail("fs_batch_set_bc_sampled: this build has no forcing kernels");
+    HIP_TRY(hipGetLastError());
+  }
+  b->bc_kind[side] = kind; b->bc_stride[side] = 0;
+  b->have_bc[side] = true;
+  b->kinds_per_reach[side] = false; b->any_storage[side] = false; b->some_host_rows[side] = false;
+  if (b->reach_kinds && fill_side_kinds(b, side, kind)) return -1;
+  return 0;
+}
+
+int fs_batch_route_pool(fs_batch *b, int32_t side, const double *curve_stage, const double *curve_volume, int32_t n_curve,
+                        const double *weirs, int32_t n_w, double base_flow, double vol_scale, double z_lo, double z_hi,
+                        const double *initial_stage, const double *weir_scale, int32_t *info) {
+  if (!b) return fail("fs_batch_route_pool: null handle");
+  if (check_side("fs_batch_route_pool", side)) return -1;
+  if (!initial_stage) return fail("fs_batch_route_pool: null initial_stage");
+  if (const char *err = fs::check_pool(curve_stage, curve_volume, n_curve, weirs, n_w, base_flow, vol_scale, z_lo, z_hi)) return fail(err);
+  if (!b->have_bc[side] || b->kinds_per_reach[side] || b->bc_kind[side] != FS_BC_FLOW_HYDROGRAPH || !b->bc_target[side])
+    return fail("fs_batch_route_pool: this side must be an FS_BC_FLOW_HYDROGRAPH boundary of the whole batch with its target set "
+                "(fs_batch_set_bc or fs_batch_set_bc_sampled): the target is the pool's inflow");
+  const size_t B = b->d.n_reaches, L = b->d.max_levels;
+  for (size_t r = 0; r < B; ++r)
+    if (!(initial_stage[r] == initial_stage[r])) return fail("fs_batch_route_pool: initial_stage must be numbers");
+  FS_ON_DEVICE(b);
+  HIP_TRY(hipStreamSynchronize(b->stream));      // an earlier call's kernels are through with the inputs
+  fs::DeviceBuffer *in = b->pool_in;
+  if (upload_f64(in[0], curve_stage, (size_t)n_curve) || upload_f64(in[1], curve_volume, (size_t)n_curve)) return -1;
+  if (n_w > 0 && upload_f64(in[2], weirs, (size_t)n_w * 4)) return -1;
+  if (upload_f64(in[3], initial_stage, B)) return -1;
+  if (weir_scale && n_w > 0 && upload_f64(in[4], weir_scale, (size_t)n_w * B)) return -1;
+  const double *reach_dt;
+  if (forcing_reach_dt(b, &reach_dt)) return -1;
+  HIP_TRY(b->pool_stage.ensure(L * B * sizeof(double)));
+  HIP_TRY(b->pool_info.ensure(2 * B * sizeof(int32_t)));
+  HIP_TRY(hipMemsetAsync(b->pool_info.get(), 0, B * sizeof(int32_t), b->stream));
+  HIP_TRY(hipMemsetAsync(b->pool_info.get<int32_t>() + B, 0xff, B * sizeof(int32_t), b->stream));
+  {
+    TraceRange range_("flowsim:forcing");
+    const bool launched = with_real(b, [&](auto real) {
+      using R = decltype(real);
+      fs::PoolArgs<R> a;
+      a.target = b->bc_target[side].get<R>(); a.stage = b->pool_stage.get<double>(); a.info = b->pool_info.get<int32_t>();
+      a.L = (int32_t)L; a.B = (int32_t)B; a.n_curve = n_curve; a.n_w = n_w;
+      a.curve_stage = in[0].get<const double>(); a.curve_volume = in[1].get<const double>();
+      a.weirs = n_w > 0 ? in[2].get<const double>() : nullptr;
+      a.weir_scale = (weir_scale && n_w > 0) ? in[4].get<const double>() : nullptr;
+      a.initial_stage = in[3].get<const double>(); a.reach_dt = reach_dt;
+      a.dt = b->dt; a.base_flow = base_flow; a.vol_scale = vol_scale; a.z_lo = z_lo; a.z_hi = z_hi;
+      return fs::launch_route_pool(a, b->stream);
+    });
+    if (!launched) return fail("fs_batch_route_pool: this build has no forcing kernels");
+    HIP_TRY(hipGetLastError());
+  }
+  if (info) {
+    HIP_TRY(hipMemcpyAsync(info, b->pool_info.get(), 2 * B * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+  }
+  return 0;
+}
+
+int fs_batch_get_bc_target(fs_batch *b, int32_t side, int32_t first, int32_t n, double *out) {
+  if (!b || !out) return fail("fs_batch_get_bc_target: null argument");
+  if (check_side("fs_batch_get_bc_target", side)) return -1;
+  if (!b->have_bc[side] || !b->bc_target[side]) return fail("fs_batch_get_bc_target: this side has no target");
+  FS_ON_DEVICE(b);
+  if (check_levels(b, "fs_batch_get_bc_target", first, n)) return -1;
+  const size_t B = b->d.n_reaches;
+  return download(b, out, b->bc_target[side], (size_t)first * B, (size_t)n * B);
+}
+
+int fs_batch_get_pool_stages(fs_batch *b, int32_t first, int32_t n, double *out) {
+  if (!b || !out) return fail("fs_batch_get_pool_stages: null argument");
+  if (!b->pool_stage) return fail("fs_batch_get_pool_stages: no pool has been routed on this batch");
+  FS_ON_DEVICE(b);
+  if (check_levels(b, "fs_batch_get_pool_stages", first, n)) return -1;
+  const size_t B = b->d.n_reaches;
+  return fetch(b, out, b->pool_stage.get<const double>() + (size_t)first * B, (size_t)n * B * sizeof(double));
 }
 
 int fs_batch_step(fs_batch *b, int32_t n_steps) {

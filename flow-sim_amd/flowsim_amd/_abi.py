@@ -28,6 +28,8 @@ OK, MAX_ITER, NAN, STORAGE_RANGE, ILL_CONDITIONED, TEAM_STALL = 0, 1, 2, 3, 4, 5
 FLAG_HISTORY, FLAG_TRACE, FLAG_MONITOR = 1, 2, 4
 IC_LINEAR, IC_GVF, IC_STEADY = 0, 1, 2
 IC_SUPERCRITICAL, IC_CLAMPED, IC_FLOORED, IC_NO_ROOT = 1, 2, 4, 8
+POOL_NO_BRACKET = 1
+POOL_MAX_CURVE, POOL_MAX_WEIRS = 64, 8
 TRACE_CAP = 64
 DERIVE_ALL = 255
 # rows of fs_batch_summarize (FS_SUM_* of the header)
@@ -70,6 +72,11 @@ SIGNATURES = {
     "fs_batch_set_state": (C.c_int, [_P, _D, _D]),
     "fs_batch_set_state_uniform": (C.c_int, [_P, _D, _D]),
     "fs_batch_init_state": (C.c_int, [_P, C.c_int32, _D, _D, _D, _D, C.c_int32, _I]),
+    "fs_batch_set_bc_sampled": (C.c_int, [_P, C.c_int32, C.c_int32, _D, C.c_int32, _D, _D, C.c_int32, C.c_int32, _I, _D, _D, _D]),
+    "fs_batch_route_pool": (C.c_int, [_P, C.c_int32, _D, _D, C.c_int32, _D, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,
+                                      _D, _D, _I]),
+    "fs_batch_get_bc_target": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _D]),
+    "fs_batch_get_pool_stages": (C.c_int, [_P, C.c_int32, C.c_int32, _D]),
     "fs_batch_step": (C.c_int, [_P, C.c_int32]),
     "fs_batch_sync": (C.c_int, [_P]),
     "fs_batch_iterate": (C.c_int, [_P, _I]),

@@ -169,3 +169,60 @@ def host_rows(dh, dq, res, B):
     rows = np.empty((3, B), dtype=np.float64)
     rows[0], rows[1], rows[2] = dh, dq, res
     return rows
+
+
+# -- forcing built on the device ------------------------------------------------------------------
+def sample_tables(times, values):
+    """(times [K], values [n_tables, K]) of fs_batch_set_bc_sampled; values [K] is one table.  ValueError where the library would
+    refuse: no point, times not increasing, lengths that differ"""
+    t = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    v = v.reshape(1, -1) if v.ndim == 1 else v
+    if t.size < 1 or v.ndim != 2 or v.shape[0] < 1 or v.shape[1] != t.size:
+        raise ValueError("values must be [K] or [n_tables, K] for times [K], K >= 1")
+    if np.any(np.isnan(t)) or np.any(np.diff(t) <= 0):
+        raise ValueError("times must be increasing")
+    return t, v
+
+
+def table_index(table_of, n_tables, B):
+    """None or int32 [B] in 0 .. n_tables - 1"""
+    if table_of is None:
+        return None
+    idx = per_reach(table_of, B, np.int32)
+    if np.any(idx < 0) or np.any(idx >= n_tables):
+        raise ValueError("table_of must be 0 .. n_tables - 1")
+    return idx
+
+
+def pool_descriptor(curve_stage, curve_volume, weirs):
+    """(curve_stage [K], curve_volume [K], weirs [n_w, 4] = C, crest, ramp_top, 0) of fs_batch_route_pool; weirs: rows of
+    (C, crest) or (C, crest, ramp_top) - no ramp_top is the crest itself: no ramp"""
+    z = np.ascontiguousarray(curve_stage, dtype=np.float64).reshape(-1)
+    v = np.ascontiguousarray(curve_volume, dtype=np.float64).reshape(-1)
+    if z.shape != v.shape:
+        raise ValueError("curve_stage and curve_volume must have the same length")
+    if not 2 <= z.size <= A.POOL_MAX_CURVE:
+        raise ValueError(f"the volume curve takes 2 .. {A.POOL_MAX_CURVE} points")
+    if np.any(np.diff(z) <= 0):
+        raise ValueError("curve stages must be increasing")
+    if len(weirs) > A.POOL_MAX_WEIRS:
+        raise ValueError(f"at most {A.POOL_MAX_WEIRS} weirs")
+    w = np.zeros((len(weirs), 4), dtype=np.float64)
+    for i, row in enumerate(weirs):
+        row = tuple(float(x) for x in row)
+        if len(row) not in (2, 3):
+            raise ValueError("a weir is (C, crest) or (C, crest, ramp_top)")
+        w[i, 0], w[i, 1] = row[0], row[1]
+        w[i, 2] = row[2] if len(row) == 3 else row[1]
+    return z, v, w
+
+
+def weir_scale(v, n_w, B):
+    """None or [n_w, B] (a [n_w] column is shared by the members)"""
+    if v is None:
+        return None
+    v = np.asarray(v, dtype=np.float64)
+    if v.shape not in ((n_w,), (n_w, B)):
+        raise ValueError("weir_scale must be [n_weirs] or [n_weirs, B]")
+    return np.ascontiguousarray(np.broadcast_to(v[:, None] if v.ndim == 1 else v, (n_w, B)))

@@ -139,6 +139,49 @@ class PreissmannBatch:
         tgt = None if spec.kind in (A.BC_HOST_ROW, A.BC_STORAGE_CURVE) else P.bc_target(spec.target, self.L, self.B)
         A.check(self._lib.fs_batch_set_bc(self._h, side, spec.kind, _opt(p), n_params, per_reach, _opt(tgt)), "set_boundary")
 
+    def set_boundary_sampled(self, side: int, spec: BoundarySpec, times, values, table_of=None, scale=None, offset=None, shift=None):
+        """set_boundary for a flow or stage hydrograph whose target is sampled on the device: member r follows
+        offset[r] + scale[r] * np.interp(k * dt_r - shift[r], times, values[table_of[r]]) - Hydrograph.sample (hydrograph.py:26-32)
+        of a table the member scales, lifts and delays.  values: [K] or [n_tables, K]; table_of, scale, offset, shift: None, a scalar
+        or [B].  spec.target is not read.  Call after set_scheme (and set_reach_scheme, where used)."""
+        p, n_params, per_reach = P.bc_params(spec, self.B)
+        if per_reach:
+            raise ValueError("set_boundary_sampled takes parameters shared by the batch")
+        t, v = P.sample_tables(times, values)
+        idx = P.table_index(table_of, v.shape[0], self.B)
+        sc, off, sh = (P.opt_per_reach(a, self.B) for a in (scale, offset, shift))
+        A.check(self._lib.fs_batch_set_bc_sampled(self._h, side, spec.kind, _opt(p), n_params, _dptr(t), _dptr(v), t.size, v.shape[0],
+                                                  None if idx is None else _iptr(idx), _opt(sc), _opt(off), _opt(sh)), "set_boundary_sampled")
+
+    def route_pool(self, side: int, pool, initial_stage, weir_scale=None):
+        """Level-pool routing of the side's flow target through `pool` (forcing.PoolSpec), every member from its own initial_stage
+        (scalar or [B]; it is also the member's hold level): GerdHydrograph.build (gerd_discharge.py:12-56) for the whole batch on the
+        device.  The target becomes the release, pool_stages() the pool's stage.  weir_scale: None, [n_weirs] or [n_weirs, B]
+        multipliers of the weir coefficients (0: out of service).  Returns dict(flags[B]: POOL_* bits, level[B]: the first level at
+        which brentq had no bracket, else -1); such a member's rows are NaN from that level on."""
+        z, v, w = pool.arrays()
+        z0 = P.per_reach(initial_stage, self.B)
+        ws = P.weir_scale(weir_scale, len(w), self.B)
+        info = np.empty((2, self.B), dtype=np.int32)
+        A.check(self._lib.fs_batch_route_pool(self._h, side, _dptr(z), _dptr(v), z.size, _dptr(w), len(w), float(pool.base_flow),
+                                              float(pool.vol_scale), float(pool.z_lo), float(pool.z_hi), _dptr(z0), _opt(ws), _iptr(info)),
+                "route_pool")
+        return dict(flags=info[0].copy(), level=info[1].copy())
+
+    def bc_target(self, side: int, first=0, n=None):
+        """[n, B]: rows of the side's target as the kernels read it (n None: all max_levels)"""
+        n = self.L - first if n is None else n
+        out = np.empty((n, self.B))
+        A.check(self._lib.fs_batch_get_bc_target(self._h, side, int(first), int(n), _dptr(out)), "get_bc_target")
+        return out
+
+    def pool_stages(self, first=0, n=None):
+        """[n, B]: the pool stage per level of the last route_pool (n None: all max_levels)"""
+        n = self.L - first if n is None else n
+        out = np.empty((n, self.B))
+        A.check(self._lib.fs_batch_get_pool_stages(self._h, int(first), int(n), _dptr(out)), "get_pool_stages")
+        return out
+
     def set_state(self, h, Q):
         h, Q = P.per_node(h, self.B, self.N), P.per_node(Q, self.B, self.N)
         A.check(self._lib.fs_batch_set_state(self._h, _dptr(h), _dptr(Q)), "set_state")

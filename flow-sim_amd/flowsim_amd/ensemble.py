@@ -1,10 +1,10 @@
-"""Manning-n ensembles: many copies of one channel that differ only in the main-channel roughness,
-stepped together on the device (BASELINE.json configs[3]; the reference does this one member at a
+"""Ensembles: many copies of one channel stepped together on the device.  Manning-n ensembles differ only in the main-channel
+roughness; scenario ensembles (run_scenario_ensemble) in what the reach is forced with - inflow, pool level, outlets in service (BASELINE.json configs[3]; the reference does this one member at a
 time, cases/gerd_roseires/n_calibrate.py:55-67 -> model.run(n_main=...))."""
 import numpy as np
 
 from . import _abi as A
-from .batch import PreissmannBatch
+from .batch import BoundarySpec, PreissmannBatch
 from .hydromodel.preissmann import boundary_to_spec
 
 
@@ -45,6 +45,64 @@ def run_manning_ensemble(solver, n_main_values, tolerance=1e-4, max_iter=100, dt
             b.set_state(ics[:, :, 0], ics[:, :, 1])
         b.step(nt - 1)
         out = dict(iterations=b.iterations(0, nt), status=b.status())
+        if hydrographs:
+            out = dict(hydrographs=b.hydrographs(0, nt), **out)
+        if summaries:
+            out["summaries"] = b.summaries(0, nt)
+        if score is not None:
+            out["score"] = b.lookup(A.ROW_Q_IN, A.ROW_H_IN, score["xq"],
+                                    y_offset=score.get("y_offset"), target=score.get("target"), first=0, n=nt)
+        if bands is not None:
+            out["bands"] = b.bands(bands, 0, nt)
+        return out
+
+
+def run_scenario_ensemble(solver, pool, inflow_table, inflow_scale=None, inflow_shift=None, pool_level=None, weir_scale=None, n_main=None,
+                          initial="gvf", tolerance=1e-4, max_iter=100, dtype="f64", device=0, monitor=True, summaries=False, score=None,
+                          bands=None, hydrographs=True):
+    """Scenario ensembles: members that differ in what the reach is forced with - the inflow into the reservoir upstream of it
+    (`inflow_table` [K, 2], time [s] and flow, per member multiplied by inflow_scale and delayed by inflow_shift [s]), the pool
+    level the reservoir starts from (pool_level, required; it is also the member's hold level), the outlets in service (weir_scale
+    [n_weirs] or [n_weirs, B]: multipliers of the weir coefficients of `pool`, a forcing.PoolSpec) - and, optionally, in n_main.
+    Scalars are shared, arrays [B] make the ensemble.  The reference does this one member at a time: GerdHydrograph.build
+    (cases/gerd_roseires/gerd_discharge.py:12-56) and then model.run (model.py:36-113).
+
+    Order: the inflow is sampled on the device (PreissmannBatch.set_boundary_sampled), routed through every member's pool
+    (route_pool), row 0 of the release is each member's initial flow, from which its backwater profile is marched (init_state;
+    initial="gvf" is the only choice), then step and reduce.  Nothing per member runs on the host.  `solver` is a set-up
+    PreissmannSolver that provides the geometry, the scheme and the downstream boundary; its upstream boundary must be a flow
+    hydrograph, whose own table is not read.  The downstream rating curve stays the SHARED smooth gate curve of `solver`, built as
+    today from the default initial flow (model.py:79-81): it is not rebuilt per member.
+
+    A member whose pool leaves the bracket (the reference's ValueError) carries POOL_NO_BRACKET in 'pool' and ends with status NAN.
+    Post-processing keywords and what they add: as run_manning_ensemble.  Returns dict(hydrographs[nt, 4, B], iterations[nt, B],
+    status[B], initial_flow[B], pool=dict(flags[B], level[B])) and what the keywords add."""
+    if initial != "gvf":
+        raise ValueError("initial must be 'gvf': every member starts from the backwater profile of its own release")
+    if pool_level is None:
+        raise ValueError("pool_level is required: the level every member's reservoir starts from")
+    ch = solver.channel
+    if ch.upstream_boundary.condition != "flow_hydrograph":
+        raise ValueError("the upstream boundary of the solver must be a flow hydrograph")
+    table = np.asarray(inflow_table, dtype=np.float64)
+    sizes = {np.shape(v)[-1] for v in (inflow_scale, inflow_shift, pool_level, n_main, weir_scale)
+             if v is not None and np.ndim(v) > 0 and not (v is weir_scale and np.ndim(v) == 1)}
+    if len(sizes) > 1:
+        raise ValueError(f"per-member arguments of different lengths: {sorted(sizes)}")
+    B = sizes.pop() if sizes else 1
+    N, nt = solver.number_of_nodes, solver.number_of_time_levels
+    L = max(nt, 2)
+    n_vals = None if n_main is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n_main, dtype=np.float64), (B,)))
+    with PreissmannBatch(B, N, L, dtype=dtype, section_mode="table", device=device, monitor=monitor) as b:
+        b.set_scheme(solver.theta, solver.time_step, solver.spatial_step, tolerance, max_iter)
+        b.set_geometry_table(ch.node_geometry, n_main_override=n_vals)
+        b.set_boundary_sampled(A.UPSTREAM, BoundarySpec(A.BC_FLOW_HYDROGRAPH), table[:, 0], table[:, 1], scale=inflow_scale, shift=inflow_shift)
+        routed = b.route_pool(A.UPSTREAM, pool, pool_level, weir_scale=weir_scale)
+        flow0 = b.bc_target(A.UPSTREAM, 0, 1)[0]
+        b.set_boundary(A.DOWNSTREAM, boundary_to_spec(ch.downstream_boundary, L, solver.time_step))
+        b.init_state("GVF_equation", flow0, depth_ds=ch.downstream_boundary.initial_depth)
+        b.step(nt - 1)
+        out = dict(iterations=b.iterations(0, nt), status=b.status(), initial_flow=flow0, pool=routed)
         if hydrographs:
             out = dict(hydrographs=b.hydrographs(0, nt), **out)
         if summaries:

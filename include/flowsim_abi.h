@@ -270,6 +270,53 @@ enum { FS_IC_SUPERCRITICAL = 1, FS_IC_CLAMPED = 2, FS_IC_FLOORED = 4, FS_IC_NO_R
 int fs_batch_init_state(fs_batch *b, int32_t method, const double *flow, const double *depth_us, const double *depth_ds,
                         const double *bed_slope, int32_t bed_slope_per_reach, int32_t *info);
 
+/* ---- Boundary forcing built on the device ----
+ * What a hydrograph boundary follows, target[max_levels][B], computed where it is read instead of sampled on the host and uploaded.
+ * Both steps compute in fp64 whatever the batch dtype and round once when they store into the target.
+ *
+ * fs_batch_set_bc_sampled: fs_batch_set_bc(b, side, kind, params, n_params, 0, target) for FS_BC_FLOW_HYDROGRAPH and
+ * FS_BC_STAGE_HYDROGRAPH with
+ *     target[k][r] = offset[r] + scale[r] * np.interp(k * dt_r - shift[r], times, values[table_of[r]])
+ * i.e. Hydrograph.sample (hydrograph.py:26-32: np.interp over np.arange(n) * dt, end values held outside the table) of a table that
+ * member r scales, lifts and delays; scale, offset and shift NULL are 1, 0 and 0, and such a member's column is bit for bit what
+ * Hydrograph.sample returns.  times[n_pts] strictly increasing and shared, values[n_tables][n_pts], table_of[B] in 0 .. n_tables - 1
+ * (NULL: table 0).  dt_r is the reach's own step where fs_batch_set_reach_scheme gave one, else the batch's: the scheme (and the
+ * per-reach scheme, where used) must be set first, and a later change of dt does not resample.  The same validation as
+ * fs_batch_set_bc.  The call waits for the batch's earlier work before it uploads its inputs (blocking copies) and does not wait for
+ * its own kernel; if it fails after the arguments were accepted, the side is left without a boundary. */
+int fs_batch_set_bc_sampled(fs_batch *b, int32_t side, int32_t kind, const double *params, int32_t n_params, const double *times,
+                            const double *values, int32_t n_pts, int32_t n_tables, const int32_t *table_of, const double *scale,
+                            const double *offset, const double *shift);
+/* fs_batch_route_pool: level-pool routing of the side's target through a reservoir, GerdHydrograph.build
+ * (cases/gerd_roseires/gerd_discharge.py:12-56) generalised to data, every member with its own pool.  The side must hold an
+ * FS_BC_FLOW_HYDROGRAPH target: it is read as the inflow and overwritten, in place, with the release; the pool's stage goes to a buffer
+ * of the handle (fs_batch_get_pool_stages).  Per level k = 1 .. max_levels - 1 (gerd_discharge.py:25-56), with V = np.interp over
+ * (curve_stage, curve_volume):
+ *     f(z1) = (V(z1) - V(z0)) - (0.5 (qin1 + qin0) - 0.5 (release(qin1, z1) + qout0)) * dt_r * vol_scale
+ *     z1 = brentq(f, z_lo, z_hi) (scipy's defaults);  qout1 = release(qin1, z1)
+ * and level 0 is z0 = initial_stage[r], qout0 = release(qin0, z0).  release (gerd_discharge.py:58-68): above the member's hold level -
+ * its initial stage - the outlet capacity, at or below it max(min(inflow, capacity), base_flow).  capacity (gerd_discharge.py:70-94):
+ *     sum over the weirs of C_w * weir_scale[w][r] * max(0, z - crest_w)^1.5 * ramp_w(z), plus base_flow
+ * ramp_w rises linearly from 0 at crest_w to 1 at ramp_top_w (gerd_discharge.py:96-105) and is 1 where ramp_top_w <= crest_w.
+ * curve_stage[n_curve] strictly increasing, 2 <= n_curve <= 64; weirs[n_w][4] = C, crest, ramp_top, 0 (reserved), 0 <= n_w <= 8;
+ * vol_scale turns m3 into the curve's unit (GERD: 1e-6); z_lo < z_hi; initial_stage[B]; weir_scale[n_w][B] or NULL (1: gates out of
+ * service are 0).  A member whose f has one sign at both ends of the bracket at some level (brentq's ValueError) gets
+ * FS_POOL_NO_BRACKET; its target rows and stages from that level on are NaN, so that a later step reports FS_NAN for it; the rows before
+ * are complete.  info: NULL, or [2][B]: the FS_POOL_* bits of each member, then the first level without a bracket (else -1).  The call
+ * waits for the batch's earlier work before it uploads its inputs (blocking copies); it waits for its own kernel only when info is
+ * given. */
+enum { FS_POOL_NO_BRACKET = 1 };
+int fs_batch_route_pool(fs_batch *b, int32_t side, const double *curve_stage, const double *curve_volume, int32_t n_curve,
+                        const double *weirs, int32_t n_w, double base_flow, double vol_scale, double z_lo, double z_hi,
+                        const double *initial_stage, const double *weir_scale, int32_t *info);
+/* rows first .. first + n - 1 of the side's target as the kernels read it, out[n][B]: after fs_batch_set_bc the caller's table,
+ * after fs_batch_set_bc_sampled the samples, after fs_batch_route_pool the release (Hydrograph.table[:, 1] of the built
+ * GerdHydrograph; row 0 is what model.py:73 takes as the channel's initial flow) */
+int fs_batch_get_bc_target(fs_batch *b, int32_t side, int32_t first, int32_t n, double *out);
+/* the pool stage of every level of the last fs_batch_route_pool (stage_1 of gerd_discharge.py:45, which the reference does not keep),
+ * out[n][B] in fp64 */
+int fs_batch_get_pool_stages(fs_batch *b, int32_t first, int32_t n, double *out);
+
 /* THE HOT PATH: advances every reach by n_steps time levels (preissmann.py:108-161).  Results
  * stay on the device: boundary hydrographs, Newton counts, status, (history).  Asynchronous. */
 int fs_batch_step(fs_batch *b, int32_t n_steps);

@@ -1,0 +1,138 @@
+"""Host side of the forcing kernels (fs_batch_set_bc_sampled, fs_batch_route_pool): the outlet capacity, the release rule and one
+level of the pool recurrence of flow-sim_amd/csrc/fs_forcing.hpp are plain C++.  tests/forcing/forcing_driver.cpp is built here with
+the system compiler under AddressSanitizer and UBSan, run as a program over the members of tests/golden/pool_routing.npz (the
+reference's own GerdHydrograph.build, tools/gen_pool_routing_golden.py) and held to the reference's release and stage and to the
+evaluation counts of scipy's brentq, level by level."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN, ROOT
+
+CSRC = os.path.join(ROOT, "flow-sim_amd", "csrc")
+DRIVER = os.path.join(ROOT, "tests", "forcing", "forcing_driver.cpp")
+# GERD's outlets as fs_batch_route_pool takes them (C, crest, ramp_top, 0): cases/gerd_roseires/gerd_discharge.py
+WEIRS = np.array([[196.4017, 624.9, 640.0, 0.0], [447.3594, 640.0, 640.0, 0.0], [654.6723, 642.0, 642.0, 0.0]])
+BASE_FLOW, VOL_SCALE, Z_LO, Z_HI = 1562.5, 1e-6, 624.9, 645.0
+
+
+def numbers(a):
+    return " ".join(repr(float(v)) for v in np.ravel(a))
+
+
+@pytest.fixture(scope="module")
+def fx():
+    return np.load(os.path.join(GOLDEN, "pool_routing.npz"))
+
+
+@pytest.fixture(scope="module")
+def driver_output(tmp_path_factory, fx):
+    tmp = tmp_path_factory.mktemp("forcing")
+    exe = str(tmp / "forcing_driver")
+    cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off", "-fsanitize=address,undefined",
+           "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-I", CSRC, "-o", exe, DRIVER]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    tab = fx["inflow_table"]
+    levels = fx["release"].shape[0]
+    lines = [f"POOL {len(fx['curve_stage'])} {len(WEIRS)} {len(tab)} {levels} 3600.0 {BASE_FLOW!r} {VOL_SCALE!r} {Z_LO!r} {Z_HI!r} "
+             f"{numbers(fx['curve_stage'])} {numbers(fx['curve_volume'])} {numbers(WEIRS)} {numbers(tab[:, 0])} {numbers(tab[:, 1])}"]
+    for m in range(len(fx["scale"])):
+        lines.append(f"M {m} {numbers([fx['scale'][m], fx['shift'][m], fx['initial_stage'][m]])}")
+    lines.append("CHECKS")
+    path = tmp / "records.txt"
+    path.write_text("\n".join(lines) + "\n")
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    r = subprocess.run([exe, str(path)], capture_output=True, text=True, env=env, timeout=120)
+    assert r.returncode == 0 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
+    got = {}
+    for line in r.stdout.splitlines():
+        f = line.split()
+        if f[0] == "K":
+            got[("K", f[1])] = " ".join(f[2:])
+        else:
+            got[(f[0], int(f[1]))] = np.array([float(v) for v in f[2:]])
+    assert len([k for k in got if k[0] != "K"]) == 5 * len(fx["scale"])
+    return got
+
+
+def rows(fx, m):
+    """levels the reference completed for member m"""
+    lvl = int(fx["no_bracket_level"][m])
+    return fx["release"].shape[0] if lvl < 0 else lvl
+
+
+def test_the_fixture_holds_what_it_must(fx):
+    import json
+    tags = json.loads(str(fx["meta"]))["tags"]
+    assert len(tags) >= 24
+    for need in ("holds", "crosses", "emergency", "no_bracket"):
+        assert any(need in t for t in tags), need
+    assert np.all(fx["noise_spread"] < 1e-13)
+    assert np.sum(fx["no_bracket_level"] >= 0) == 1
+    # the default member is the reference's own default case (tests/golden/gerd_full.npz, an independent run)
+    us = np.load(os.path.join(GOLDEN, "gerd_full.npz"))["us_target"]
+    assert (fx["scale"][0], fx["shift"][0], fx["initial_stage"][0]) == (1.0, 0.0, 637.0)
+    assert np.array_equal(fx["release"][:len(us), 0], us)
+
+
+def test_sampled_inflow_is_np_interp_bit_for_bit(fx, driver_output):
+    tab = fx["inflow_table"]
+    t = np.arange(fx["release"].shape[0]) * 3600.0
+    for m in range(len(fx["scale"])):
+        want = fx["scale"][m] * np.interp(t - fx["shift"][m], tab[:, 0], tab[:, 1])
+        assert np.array_equal(driver_output[("S", m)], want), m
+
+
+def test_evaluation_counts_are_scipys_level_by_level(fx, driver_output):
+    for m in range(len(fx["scale"])):
+        n = rows(fx, m)
+        assert np.array_equal(driver_output[("E", m)][1:n], fx["evals"][1:n, m]), m
+
+
+def test_stage_and_release_are_the_references(fx, driver_output):
+    worst_z = worst_q = 0.0
+    for m in range(len(fx["scale"])):
+        n = rows(fx, m)
+        dz = np.max(np.abs(driver_output[("Z", m)][:n] - fx["stage"][:n, m]))
+        dq = np.max(np.abs(driver_output[("Q", m)][:n] - fx["release"][:n, m]) / np.abs(fx["release"][:n, m]))
+        worst_z, worst_q = max(worst_z, dz), max(worst_q, dq)
+        print(m, dz, dq)
+        assert dz <= 3e-11 and dq <= 1e-10, (m, dz, dq)
+    print("worst: stage", worst_z, "release", worst_q)
+
+
+def test_the_member_without_a_bracket_stops_where_the_reference_raises(fx, driver_output):
+    for m in range(len(fx["scale"])):
+        lvl = int(fx["no_bracket_level"][m])
+        assert int(driver_output[("F", m)][0]) == lvl, m
+        if lvl >= 0:
+            assert np.all(np.isnan(driver_output[("Z", m)][lvl:])) and np.all(np.isnan(driver_output[("Q", m)][lvl:]))
+            assert np.all(np.isfinite(driver_output[("Z", m)][:lvl]))
+
+
+REJECTIONS = {
+    "tables_null": "null table", "tables_none": "must be >= 1", "tables_descending": "times must be increasing",
+    "tables_repeated": "times must be increasing", "tables_nan": "times must be increasing", "tables_index_high": "table_of must be 0 .. n_tables - 1",
+    "tables_index_negative": "table_of must be 0 .. n_tables - 1",
+    "pool_null_curve": "null volume curve", "pool_curve_short": "2 .. 64 points", "pool_curve_long": "2 .. 64 points",
+    "pool_curve_descending": "curve stages must be increasing", "pool_volume_nan": "curve volumes must be numbers", "pool_nine_weirs": "at most 8 weirs",
+    "pool_null_weirs": "null weirs", "pool_negative_weir": "a weir needs C >= 0", "pool_reserved": "reserved and must be 0",
+    "pool_negative_base": "base_flow >= 0 and vol_scale > 0", "pool_zero_scale": "base_flow >= 0 and vol_scale > 0",
+    "pool_bracket_equal": "z_lo < z_hi", "pool_bracket_reversed": "z_lo < z_hi", "pool_bracket_nan": "z_lo < z_hi",
+}
+ACCEPTED = ("tables_ok", "tables_one_point", "pool_ok", "pool_full", "pool_no_weirs")
+
+
+def test_the_host_side_rejects_what_it_must_and_says_why(driver_output):
+    """fs::check_sampled_tables and fs::check_pool (what fs_batch_set_bc_sampled and fs_batch_route_pool run before anything goes to
+    the device), called directly: the Python packers refuse the same inputs first, so only a C caller ever meets these texts"""
+    texts = {k[1]: v for k, v in driver_output.items() if k[0] == "K"}
+    assert set(texts) == set(REJECTIONS) | set(ACCEPTED)
+    for name in ACCEPTED:
+        assert texts[name] == "ok", name
+    for name, part in REJECTIONS.items():
+        entry = "fs_batch_set_bc_sampled: " if name.startswith("tables") else "fs_batch_route_pool: "
+        assert texts[name].startswith(entry) and part in texts[name], (name, texts[name])
