@@ -370,14 +370,14 @@ template <typename R, bool TEAM> struct TeamSmem {
 };
 template <typename R> struct TeamSmem<R, false> {};
 
-template <typename R, int M, int W, bool SAVE, bool TEAM = false> struct Smem : SavedTerms<R, M, 64 * W, SAVE>, TeamSmem<R, TEAM> {
+template <typename R, int M, int W, bool SAVE, bool TEAM = false, int XA = alignof(R)> struct Smem : SavedTerms<R, M, 64 * W, SAVE>, TeamSmem<R, TEAM> {
   static constexpr int T = 64 * W;
   R kc[4][M][T];           // per-cell level-k constants, lane-minor (conflict-free ds_read_b64)
   R tree[W][4][64];        // per-wave records of the in-wave tree (Elim: 4 numbers per merge, 63 merges)
-  R xseg[2][W][8];         // wave segments, double-buffered by iteration parity
-  R xbc[2][4];             // upstream boundary row on (p_0, m_0): aU, bU, rU
+  alignas(XA) R xseg[2][W][8];         // wave segments, double-buffered by iteration parity
+  alignas(XA) R xbc[2][4];             // upstream boundary row on (p_0, m_0): aU, bU, rU
   R bcp[2][FS_BC_MAX_PARAMS];   // this reach's boundary parameters (fixed-size kinds), read every Newton iteration
-  R xnorm[2][W];
+  alignas(XA) R xnorm[2][W];
   int32_t xflag[2];
   int32_t xg[2][W];        // conditioning monitor: high word of the largest |u3| of each wave's tree
 };
@@ -455,7 +455,19 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
   constexpr bool kRegGeo = SEC == FS_SEC_TABLE && W == 1 && M <= 2;
   // kernels compiled for a boundary pair evaluate the two rows in every lane, without a branch (step 1 below)
   constexpr bool kFlatBC = BCK >= 2 && sizeof(R) == 8 && SEC == FS_SEC_TRAP_UNIFORM;   // measured: C5 fp64 +1.5 %; flagship -1.5 %, C4 -7 %, polyline -1.3 %
-  __shared__ Smem<R, M, W, kSaveTerms, kTeam> sm;
+  // Full lane grids of the rectangular fp64 kernels with 16 rows per lane (the flagship and its one- and two-wave siblings; round 9,
+  // profiles/round9/fold_reads.txt): the fold is ONE straight-line block - the downstream boundary row enters the last lane's last
+  // row by selects, not behind a branch - and the 4 M level constants are read from LDS kFoldAhead cells ahead of the cell that uses
+  // them.  Behind the branch the compiler sank every cell's arithmetic into one block and left all 4 M reads in front of it, under one
+  // wait, live in 128 registers from the first cell on: 366 registers against 344, 46 issue slots per iteration more, flagship -2.5 %.
+  // Distance 0 / 1 / 2 / 3 measured +2.3 / +1.9 / +2.5 / +2.4 %.  With 8 rows per lane the selects cost more slots than the moves they
+  // save (census); the ragged, team, polyline and fp32 forms keep their code.
+  constexpr bool kFoldFlat = !RAGGED && !kTeam && !kTail && sizeof(R) == 8 && SEC == FS_SEC_RECT_UNIFORM && M >= 16;
+  constexpr int kFoldAhead = 2;
+  // ... and there the posted segments, the upstream row and the norms are 16-byte aligned: the cross-wave step reads them as ds_read_b128
+  // instead of ds_read2_b64 pairs, all four waves at once right behind the barrier (flagship +1.9 % on top)
+  constexpr int kXAlign = kFoldFlat ? 16 : alignof(R);
+  __shared__ Smem<R, M, W, kSaveTerms, kTeam, kXAlign> sm;
 
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   int job = blockIdx.x;
@@ -794,9 +806,25 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
           }
         }
         R rcPrev = R(0);
+        R kq[kFoldFlat ? M : 1][4];               // kFoldFlat: the level constants of the cells, requested kFoldAhead cells ahead
+        auto read_kc = [&](int c) __attribute__((always_inline)) {
+          if constexpr (kFoldFlat) {
+            kq[c][0] = kcb[(0 * M + c) * T]; kq[c][1] = kcb[(1 * M + c) * T]; kq[c][2] = kcb2[(0 * M + c) * T]; kq[c][3] = kcb2[(1 * M + c) * T];
+          }
+        };
+        if constexpr (kFoldFlat) {
+#pragma unroll
+          for (int c = 0; c < kFoldAhead; ++c) read_kc(c);
+        }
 #pragma unroll
         for (int c = 0; c < M; ++c) {
-          const R k0 = kcb[(0 * M + c) * T], k1 = kcb[(1 * M + c) * T], k2 = kcb2[(0 * M + c) * T], k3 = kcb2[(1 * M + c) * T];
+          R k0, k1, k2, k3;
+          if constexpr (kFoldFlat) {
+            if (c + kFoldAhead < M) read_kc(c + kFoldAhead);      // (never past kc[3][M-1]; all of them behind the level pass: this iteration's fold)
+            k0 = kq[c][0]; k1 = kq[c][1]; k2 = kq[c][2]; k3 = kq[c][3];
+          } else {
+            k0 = kcb[(0 * M + c) * T]; k1 = kcb[(1 * M + c) * T]; k2 = kcb2[(0 * M + c) * T]; k3 = kcb2[(1 * M + c) * T];
+          }
           const NodeTerms<R> Rn = (kShareNode && c == M - 1) ? Rlast : terms_at(c + 1, h[c + 1], Q[c + 1]);
           save_terms(c + 1, Rn);
           const R i2tR = dt * Rn.rT;
@@ -832,6 +860,18 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
                 row.rho0 = isD ? -Drow.res : row.rho0; row.rc = isD ? R(0) : row.rc;
               }
               nrm2 = fma_(r2, c < TAIL ? mle : mlt, nrm2);    // cells only: not the boundary row, not the phantom cells behind it
+            } else if constexpr (kFoldFlat) {
+              // full lane grid: the one row that is not a cell is the last row of the last lane, the downstream boundary row.  Put in by
+              // selects, not behind a branch: the branch ends the block, the arithmetic of every cell sinks behind it and the fences
+              // between the cells then hold nothing but the constants' reads (all 4 M of them ahead of the first row)
+              if (c == M - 1) {
+                const bool cell = t != T - 1;
+                const R x = Drow.dh * i2tL, y = Drow.dq * i2c;
+                const R bal = x + y, bD = x - y;
+                r2 = cell ? r2 : R(0);
+                row.al = cell ? row.al : bal; row.D = cell ? row.D : bD; row.de = cell ? row.de : R(0);
+                row.rho0 = cell ? row.rho0 : -Drow.res; row.rc = cell ? row.rc : R(0);
+              }
             } else
             // rows beyond the cells: the downstream boundary row (on p and m of node N-1), then identity rows
             if (RAGGED || c == M - 1) {
@@ -875,6 +915,7 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
           if constexpr (M >= 8 && sizeof(R) == 4)
             asm volatile("" :: "v"(seg.u1), "v"(seg.u3), "v"(seg.ru), "v"(seg.d1), "v"(seg.d2), "v"(seg.d3), "v"(seg.rd), "v"(rcPrev));
           L = Rn; i2tL = i2tR;
+          if constexpr (!kTeam) { if (c == 0) FS_T(11); }     // (stamp builds: boundary rows' end to the end of the fold's first row; the rest of the fold stays in slot 0)
           __builtin_amdgcn_sched_barrier(0);        // one scheduling region per cell
         }
         seg.rc = rcPrev; rcLast = rcPrev;

@@ -64,12 +64,15 @@ CLASSES = [
     ("agpr move", r"v_accvgpr_"),
     ("dpp move", r"v_mov_b(32|64)_dpp|v_\w+_dpp"),
     ("select", r"v_cndmask_"),
-    ("fp64 arith", r"v_(fma|mul|add|sub|max|min|ldexp|trunc|rndne|frexp\w*|div_\w+)_f64"),
+    # (v_fmac_f64 is the two-address fma the register allocator picks where the addend dies: the same arithmetic.  Until round 9 it was
+    # missing here and counted as "other valu" - 244 of the flagship fold's "292 other" in the census files of rounds 5 and 6)
+    ("fp64 arith", r"v_(fma|fmac|mul|add|sub|max|min|ldexp|trunc|rndne|frexp\w*|div_\w+)_f64"),
+    ("fp32 arith", r"v_(fma|fmac|mul|add|sub|max|min)_f32"),
     ("lds read", r"ds_read|ds_load"),
     ("lds write", r"ds_write|ds_store"),
     ("s_nop", r"s_nop"),
 ]
-VALU_CLASSES = ("rcp/rsq f64", "trans f32", "agpr move", "dpp move", "select", "fp64 arith", "other valu")
+VALU_CLASSES = ("rcp/rsq f64", "trans f32", "agpr move", "dpp move", "select", "fp64 arith", "fp32 arith", "other valu")
 
 
 def classify(mn, dpp):
@@ -221,7 +224,7 @@ def main():
         print("no loop found")
         return 1
     loop, rows = res
-    cols = ["fp64 arith", "rcp/rsq f64", "trans f32", "agpr move", "dpp move", "select", "other valu", "lds read", "lds write", "s_nop", "scalar", "memory"]
+    cols = ["fp64 arith", "fp32 arith", "rcp/rsq f64", "trans f32", "agpr move", "dpp move", "select", "other valu", "lds read", "lds write", "s_nop", "scalar", "memory"]
     print(f"whole kernel {len(body)} instructions; Newton loop: instructions {loop[0]} .. {loop[1]} ({loop[1] - loop[0] + 1})")
     print(f"{'block':>8s} {'at':>6s} {'instr':>6s} " + " ".join(f"{c:>11s}" for c in cols) + f" {'valu slots':>11s}")
     total, tslots = collections.Counter(), 0.0

@@ -21,6 +21,8 @@ if A.kernel_table()[bt.kernel_index()].get("team"):          # a team's rows: (m
     W = min(16, W * ((N + 64 * W * bt.kernel_info()["cells_per_thread"] - 1) // (64 * W * bt.kernel_info()["cells_per_thread"])))
 names = ["fold", "bc", "tree-up", "barrier-wait", "cross-wave", "update(+accept tail)", "down+back", "loop-top", "acc:stores", "acc:hydro", "acc:level-pass", "team:post+wait"]
 per_it = out[:, :W, :].astype(np.float64) / its[:, None, None]
+if not A.kernel_table()[bt.kernel_index()].get("team"):      # slot 11 of the other kernels: the fold up to the end of its first row
+    names[0], names[11] = "fold:rows 1..", "fold:row 0"
 print(f"kernel {bt.kernel_info()}  ms {bt.last_step_ms():.2f}  mean its/step {its.mean()/K:.2f}")
 tot = per_it.sum(axis=2).mean()
 for w in range(W):
