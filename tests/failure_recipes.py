@@ -2,7 +2,7 @@
 FS_STORAGE_RANGE) at a level chosen by the test - shared by tests/test_failure_recipes.py, which checks on the CPU oracle
 that every recipe fails where and how it is meant to, with margins, and tests/test_gpu_failure_exits.py, which runs them.
 
-The cases are those of tests/test_gpu_instantiations.py (case_for: the smallest reach that fits each dispatch-table entry).
+The cases are those of tests/entry_recipes.py (case_for: the smallest reach that fits each dispatch-table entry).
 Every constant below was picked with the oracle alone; the margins it produced are written next to it and asserted by
 tests/test_failure_recipes.py for every entry."""
 import copy
@@ -10,17 +10,14 @@ import functools
 
 import numpy as np
 
+from entry_recipes import TABLE, case_for, fixture_problem, oracle_run, prismatic_problem  # noqa: F401
+from flowsim_amd import _abi as A
+from kernel_harness import entry_id, f32_of, find_entry  # noqa: F401
 from oracle import preissmann_oracle as O
-from test_gpu_instantiations import GENERAL_PAIRS, LIGHT_PAIRS, TABLE, _id, case_for, fixture_problem, oracle_run, prismatic_problem  # noqa: F401
 
 K_STAR = 2            # the failing level: level 1 converges before it, levels 3.. would follow in the same launch
 MARGIN = 100.0        # the factor the issue sets: decisions of the oracle that fp32 has to repeat are off the threshold by this much
 STATUS = {"nan": 2, "maxiter": 1, "storage": 3}
-
-
-def f32_of(e):
-    from flowsim_amd import _abi as A
-    return e["dtype"] == A.F32
 
 
 def suite_case(e):
@@ -84,7 +81,6 @@ SUBSTITUTED = {
 
 def substituted(e):
     """the key of SUBSTITUTED that applies to the entry's suite case, or None: the max-iter exit runs that case"""
-    from flowsim_amd import _abi as A
     p, _, _ = suite_case(e)
     if e["section_mode"] == A.SEC_IRREGULAR:
         return "polyline"
@@ -103,7 +99,6 @@ def substituted(e):
 
 def maxiter_base(e):
     """(problem, mode, override) the max-iter exit runs on: the suite's case or its substitute, at the max-iter tolerance"""
-    from flowsim_amd import _abi as A
     p, mode, override = suite_case(e)
     sec, why = e["section_mode"], substituted(e)
     if why == "polyline":
@@ -159,18 +154,7 @@ def case(e, exit_):
 
 
 # ---- FS_STORAGE_RANGE: the bracket [Y_min, Y_max] of the reservoir is tightened so that the stage leaves it at a known iteration ----
-def find_entry(**attrs):
-    """the first dispatch-table entry with these attributes (an attribute an entry does not carry counts as 0; tail: as -1)"""
-    def value(e, key):
-        return e.get("tail", -1) if key == "tail" else int(e.get(key) or 0)
-    for e in TABLE:
-        if all(value(e, key) == want for key, want in attrs.items()):
-            return e
-    raise KeyError(attrs)
-
-
 def _plain(dtype, sec, M, W, bck, **more):
-    from flowsim_amd import _abi as A
     return find_entry(dtype=A.F64 if dtype == "f64" else A.F32, section_mode=sec, cells_per_thread=M, waves_per_reach=W, boundary_class=bck,
                       diag=1, long_reach=0, team=0, **more)
 
@@ -209,7 +193,6 @@ STORAGE_Y_MAX = {
 
 def storage_case(name):
     """dict(good, bad: problems; mode; entry: the dispatch-table entry to force (None: the library's own choice); env)"""
-    from flowsim_amd import _abi as A
     R = A.SEC_RECT_UNIFORM
     env, mode = {}, "rect_uniform"
     if name == "one_wave":

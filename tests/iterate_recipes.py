@@ -7,7 +7,7 @@ Why: Newton's method corrects its own Jacobian.  A derivative that is off by 1e-
 it.  The first iterate x1 = x0 - J^-1 R(x0) can: with max_iter = m a level ends in FS_MAX_ITER after exactly m updates and
 fs_batch_get_guess holds x_m (include/flowsim_abi.h), which O.newton_run(max_iter_at={level: m}) returns as x_next.
 
-The cases are those of tests/test_gpu_instantiations.py (case_for: the smallest reach that uses each dispatch-table entry's
+The cases are those of tests/entry_recipes.py (case_for: the smallest reach that uses each dispatch-table entry's
 structure), shortened to two levels, as B = 3 reaches of the same channel whose initial states are off the fixed point at EVERY
 node, each reach with its own seed:
     h0 (1 + a_h sin(2 pi k_h x) + 0.2 a_h xi),   Q0 (1 + a_q cos(2 pi k_q x) + 0.2 a_q xi),   x = i / (N - 1), xi ~ N(0, 1)
@@ -24,8 +24,9 @@ import functools
 
 import numpy as np
 
+from entry_recipes import TABLE, case_for
+from kernel_harness import entry_id, f32_of, rel_err  # noqa: F401
 from oracle import preissmann_oracle as O
-from test_gpu_instantiations import TABLE, TOL, TOL_F32, _id, _nodes, case_for, rel_err  # noqa: F401
 
 B = 3                                  # reaches of one launch
 SEEDS = (11, 23, 37)
@@ -48,11 +49,6 @@ OFFSETS = {"prismatic": (0.10, 0.15, 7, 5, (1.0, 2.0), (-1.0, 2.0)),
            "deep": (0.02, 0.10, 3, 2, (1.0, -1.0), (-1.0, 1.0))}
 # the iterates held to the oracle: (level, m)
 ITERATES = ((1, 1), (1, 2), (2, 1))
-
-
-def f32_of(e):
-    from flowsim_amd import _abi as A
-    return e["dtype"] == A.F32
 
 
 def level_tol(e, N):

@@ -13,10 +13,7 @@ for p in (ROOT, os.path.join(ROOT, "flow-sim_amd"), HERE):
     sys.path.insert(0, p)
 from oracle import preissmann_oracle as O          # noqa: E402
 from fixture_batch import batch_from_problems      # noqa: E402
-
-
-def rel(got, want, floor):
-    return float(np.max(np.abs(got - want) / np.maximum(np.abs(want), floor)))
+from kernel_harness import rel_err                   # noqa: E402
 
 
 def main():
@@ -33,7 +30,7 @@ def main():
                 h, Q = b.history_arrays()
                 its = b.iterations()[:, 0]
             pick = lambda k, nd: fx[k][m] if m is not None and fx[k].ndim > nd else fx[k]
-            eh = max(eh, rel(h[:, 0], pick("depth", 2), 1e-3)); eq = max(eq, rel(Q[:, 0], pick("flow", 2), 1.0))
+            eh = max(eh, rel_err(h[:, 0], pick("depth", 2), 1e-3)); eq = max(eq, rel_err(Q[:, 0], pick("flow", 2), 1.0))
             same &= bool(np.array_equal(its, pick("iters", 1)))
         print(f"{os.path.basename(path)[:-4]:28s} {len(mem):2d} {meta['N']:5d} {meta['nt']:4d}  {eh:9.2e} {eq:9.2e}  {'identical' if same else 'DIFFER'}")
 

@@ -25,8 +25,8 @@ from fixture_batch import boundary_spec, merge_specs
 from flowsim_amd import BoundarySpec
 from flowsim_amd import _abi as A
 from flowsim_amd import _pack
+from host_pack_driver import CSRC, build_driver, line, run_driver
 from oracle import preissmann_oracle as O
-from test_host_pack import CSRC, build_driver, line, run_driver
 
 RECORD = os.path.join(GOLDEN, "batch_pack", "record.json")
 NF = len(A.SC_NAMES)

@@ -8,10 +8,11 @@ import numpy as np
 import pytest
 
 import failure_recipes as FR
+from oracle import c_oracle as CO
 from oracle import preissmann_oracle as O
 
 TABLE = FR.TABLE
-IDS = [FR._id(e) for e in TABLE]
+IDS = [FR.entry_id(e) for e in TABLE]
 PARITY = 1e-8          # the fp64 parity tolerance of the suite (storage margins are relative to it)
 
 
@@ -26,7 +27,7 @@ def test_the_library_is_built_and_every_entry_is_covered():
     for e in TABLE:
         for exit_ in ("nan", "maxiter"):
             good, bad, mode, _ = FR.case(e, exit_)            # raises for an entry without a recipe
-            assert good.nt - 1 > FR.K_STAR >= 2, FR._id(e)    # converged levels precede and would follow
+            assert good.nt - 1 > FR.K_STAR >= 2, FR.entry_id(e)    # converged levels precede and would follow
     reasons = [FR.substituted(e) for e in TABLE]
     assert set(reasons) - {None} <= set(FR.SUBSTITUTED) and reasons.count(None) >= 70      # most entries run the suite's own case
     assert set(FR.STORAGE_CASES) == {"one_wave", "multi_wave", "pair_excluded", "team", "long", "curve_table", "curve_polyline"}
@@ -56,11 +57,11 @@ def test_max_iter_recipe(e):
     for lvl, err in base["norms"]:
         last[lvl] = err
     for lvl in range(1, k):
-        print(f"{FR._id(e)}: level {lvl} converged in {base['iters'][lvl]} iterations at ||R|| = {last[lvl] / tol:.1e} tol")
+        print(f"{FR.entry_id(e)}: level {lvl} converged in {base['iters'][lvl]} iterations at ||R|| = {last[lvl] / tol:.1e} tol")
         assert last[lvl] < tol / FR.MARGIN, (lvl, last[lvl] / tol)
     ref = _trace(bad, k)
     at_k = [err for lvl, err in ref["norms"] if lvl == k]
-    print(f"{FR._id(e)}: level {k} after max_iter = {bad.max_iter} iterations ||R|| = {at_k[-1] / tol:.1e} tol")
+    print(f"{FR.entry_id(e)}: level {k} after max_iter = {bad.max_iter} iterations ||R|| = {at_k[-1] / tol:.1e} tol")
     assert ref["status"] == FR.STATUS["maxiter"] and ref["fail_level"] == k and ref["iters"][k] == bad.max_iter == len(at_k)
     assert np.all(np.isfinite(at_k)) and at_k[-1] > FR.MARGIN * tol, at_k[-1] / tol
     fast = FR.oracle_run(bad)                       # the oracle the GPU test compares with (C where it applies)
@@ -109,7 +110,6 @@ def _small_cases():
 def test_the_two_oracles_agree_on_a_failure(name, p):
     """status, failing level, the iteration count of every level (the failing one included: the count include/flowsim_abi.h
     defines) and the rows before the failing level"""
-    from oracle import c_oracle as CO
     a, b = _trace(p, None), CO.run(p)
     k = a["fail_level"]
     assert a["status"] == b["status"] == FR.STATUS[name.split("-")[0]] and b["fail_level"] == k

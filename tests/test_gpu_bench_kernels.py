@@ -13,14 +13,14 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from fixture_batch import batch_from_problems
+from flowsim_amd import _abi as A
+from kernel_harness import entry_of, rel_err
 from oracle import preissmann_oracle as O
+from synth import rect_problem
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-8
-
-
-def rel_err(got, want, floor):
-    return float(np.max(np.abs(got - want) / np.maximum(np.abs(want), floor)))
 
 
 def check_rows(b, depth, flow, iters, j=0):
@@ -34,16 +34,10 @@ def check_rows(b, depth, flow, iters, j=0):
     assert np.array_equal(b.iterations(0, nt)[:, j], iters)
 
 
-def entry_of(b):
-    from flowsim_amd import _abi as A
-    return A.kernel_table()[b.kernel_index()]
-
-
 def test_c3_flagship_kernel_at_4096_nodes_against_the_reference():
     """BASELINE configs[2] shape: rectangular, 4096 nodes, flow hydrograph -> normal depth, fp64, no history: the
     <double, RECT_UNIFORM, 16, 4, full, normal depth, DIAG = false> instantiation of BENCH_r01."""
     from flowsim_amd import BoundarySpec, PreissmannBatch
-    from flowsim_amd import _abi as A
     from flowsim_amd.synthetic import c3_reach_parameters, inflow_table, normal_depth_rect
     fx, meta = O.load_fixture(os.path.join(GOLDEN, "c3_4096.npz"))
     B, N, nt = meta["B"], meta["N"], meta["nt"]
@@ -81,7 +75,6 @@ def test_c5_kernel_at_512_nodes_against_the_reference(dtype):
     <R, TRAP_UNIFORM, 8, 1, full, rating power, DIAG = false> instantiations.  fp32 is the throughput mode:
     tolerance 1e-3, hydrographs within 5e-4 of the fp64 reference."""
     from flowsim_amd import BoundarySpec, PreissmannBatch
-    from flowsim_amd import _abi as A
     from flowsim_amd.synthetic import c5_reach_parameters, inflow_table, normal_depth_trap
     fx, meta = O.load_fixture(os.path.join(GOLDEN, "c5_512.npz"))
     B, N, nt = meta["B"], meta["N"], meta["nt"]
@@ -119,8 +112,6 @@ def test_c5_kernel_at_512_nodes_against_the_reference(dtype):
 def test_gerd_roseires_over_all_384_levels_against_the_reference(chunks):
     """BASELINE configs[3] member: cases/gerd_roseires over its whole simulation (settings.py:3-8) in the ensemble
     kernel <double, TABLE, 2, 1, gate curve, DIAG = false>; in one launch and in four (chunked stepping)."""
-    from fixture_batch import batch_from_problems
-    from flowsim_amd import _abi as A
     fx, meta = O.load_fixture(os.path.join(GOLDEN, "gerd_full.npz"))
     assert meta["nt"] == 385 and meta["N"] == 121
     p = O.problem_from_fixture(fx, meta)
@@ -142,8 +133,6 @@ def test_the_tail_only_form_gives_the_bits_of_the_ragged_kernel(monkeypatch):
     general ragged instantiation of the same shape: the rows behind the boundary row are phantom cells there and identity rows here,
     and neither can reach a real unknown (the boundary row's super-diagonal is zero) - hydrographs, state, start vector and counts are
     bit-identical over 48 levels of cases/gerd_roseires and over an 8-member Manning-n ensemble."""
-    from fixture_batch import batch_from_problems
-    from flowsim_amd import _abi as A
     table = A.kernel_table()
     plain = [e["index"] for e in table if e["section_mode"] == A.SEC_TABLE and e["dtype"] == A.F64 and (e["cells_per_thread"], e["waves_per_reach"]) == (2, 1)
              and e["boundary_class"] == 2 + A.BC_RATING_BLEND and e["diag"] == 0 and e["tail"] == -1]
@@ -172,9 +161,6 @@ def test_dispatch_prefers_the_most_specific_instantiation():
     """fs::pick's ordering (fs_dispatch.hpp; on the CPU: tests/test_dispatch.py): smallest capacity, then fewest waves per reach, then the most specific
     variant (boundary pair fixed > closed-form rows > general; no-history build when the batch keeps none)."""
     from flowsim_amd import BoundarySpec, PreissmannBatch
-    from flowsim_amd import _abi as A
-    from synth import rect_problem
-    from fixture_batch import batch_from_problems
     want = {                                   # N -> (M, W, full, class with / without history)
         4096: (16, 4, 1, 2 + A.BC_NORMAL_DEPTH), 4000: (16, 4, 0, 2 + A.BC_NORMAL_DEPTH), 2048: (16, 2, 1, 2 + A.BC_NORMAL_DEPTH),
         1024: (16, 1, 1, 2 + A.BC_NORMAL_DEPTH), 512: (8, 1, 1, 2 + A.BC_NORMAL_DEPTH), 300: (8, 1, 0, 2 + A.BC_NORMAL_DEPTH),

@@ -6,17 +6,16 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
-from oracle import preissmann_oracle as O
 import case_builders as CB
+from conftest import GOLDEN
+import fixture_batch as FB
+from fixture_batch import batch_from_problems, boundary_spec
 from flowsim_amd import PreissmannBatch, _abi as A
+from kernel_harness import rel_err
+from oracle import preissmann_oracle as O
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-8
-
-
-def rel(got, want, floor):
-    return float(np.max(np.abs(got - want) / np.maximum(np.abs(want), floor)))
 
 
 @pytest.mark.parametrize("name", sorted(CB.BUILDERS))
@@ -25,10 +24,10 @@ def test_case_through_reference_api(name):
     solver, tol = CB.BUILDERS[name]()
     solver.run(tolerance=tol, verbose=0)
     assert solver.depth.shape == (meta["nt"], meta["N"])
-    assert rel(solver.depth, fx["depth"], 1e-3) <= TOL
-    assert rel(solver.flow, fx["flow"], 1.0) <= TOL
+    assert rel_err(solver.depth, fx["depth"], 1e-3) <= TOL
+    assert rel_err(solver.flow, fx["flow"], 1.0) <= TOL
     assert np.array_equal(solver.iterations, fx["iters"])
-    assert rel(solver.unknowns, fx["final_unknowns"], 1e-3) <= 1e-7     # Newton vector seeding the next level
+    assert rel_err(solver.unknowns, fx["final_unknowns"], 1e-3) <= 1e-7     # Newton vector seeding the next level
     # derived fields of prepare_results exist and are consistent
     assert solver.level.shape == solver.depth.shape and np.all(solver.area > 0)
     np.testing.assert_allclose(solver.velocity * solver.area, solver.flow, rtol=1e-12)
@@ -40,7 +39,7 @@ def test_example_storage_stage_hydrograph():
     solver.run(tolerance=tol, verbose=0)
     st = solver.channel.downstream_boundary.lumped_storage
     got = np.array(st.stage_hydrograph)[1:, 1]                 # [0] is the level-0 entry prepare_results inserts
-    assert rel(got, fx["storage_stage"][:, 1], 1e-3) <= TOL
+    assert rel_err(got, fx["storage_stage"][:, 1], 1e-3) <= TOL
     assert abs(solver.flow[1, -1] - (-999.9613412523)) < 1e-6   # the reference's negative first outflow
 
 
@@ -49,8 +48,8 @@ def test_synthetic_trapezoid_power_rating():
     for mem in range(meta["B"]):
         solver, tol = CB.synthetic_trap(mem)
         solver.run(tolerance=tol, verbose=0)
-        assert rel(solver.depth, fx["depth"][mem], 1e-3) <= TOL
-        assert rel(solver.flow, fx["flow"][mem], 1.0) <= TOL
+        assert rel_err(solver.depth, fx["depth"][mem], 1e-3) <= TOL
+        assert rel_err(solver.flow, fx["flow"][mem], 1.0) <= TOL
         assert np.array_equal(solver.iterations, fx["iters"][mem])
 
 
@@ -88,7 +87,7 @@ def test_manning_ensemble_batch_matches_sequential_reference_runs():
         hy = res["hydrographs"][:, :, i]
         for col, (arr, node, floor) in enumerate(((fx["depth"], 0, 1e-3), (fx["flow"], 0, 1.0),
                                                   (fx["depth"], -1, 1e-3), (fx["flow"], -1, 1.0))):
-            assert rel(hy[:, col], arr[i][:, node], floor) <= TOL, (i, col)
+            assert rel_err(hy[:, col], arr[i][:, node], floor) <= TOL, (i, col)
         assert np.array_equal(res["iterations"][:, i], fx["iters"][i])
 
 
@@ -101,11 +100,11 @@ def test_derived_fields_kernel_matches_reference_post_processing(name):
     solver.run(tolerance=tol, verbose=0)
     assert solver._derived is not None
     for field in ("level", "area", "top_width", "froude_number", "velocity", "wave_celerity"):
-        assert rel(getattr(solver, field), fx["derived_" + field], 1e-6) <= TOL, field
+        assert rel_err(getattr(solver, field), fx["derived_" + field], 1e-6) <= TOL, field
     np.testing.assert_allclose(solver.amplitude, fx["derived_amplitude"], rtol=0, atol=1e-8 * np.abs(fx["depth"]).max())
     np.testing.assert_allclose(solver.peak_amplitude, fx["derived_peak_amplitude"], rtol=0, atol=1e-8 * np.abs(fx["depth"]).max())
     if "derived_storage_outflow" in fx.files:
-        assert rel(solver.storage_stage, fx["derived_storage_stage"], 1e-3) <= TOL
+        assert rel_err(solver.storage_stage, fx["derived_storage_stage"], 1e-3) <= TOL
         np.testing.assert_allclose(solver.storage_outflow, fx["derived_storage_outflow"], rtol=1e-6, atol=1e-4)
 
 
@@ -138,10 +137,10 @@ def test_plugins_without_a_device_form_run_through_host_rows(name):
     solver, tol = CB.HOST_ROW_BUILDERS[name]()
     assert not solver.channel.downstream_boundary.has_device_form()
     solver.run(tolerance=tol, verbose=0)
-    assert rel(solver.depth, fx["depth"], 1e-3) <= TOL
-    assert rel(solver.flow, fx["flow"], 1.0) <= TOL
+    assert rel_err(solver.depth, fx["depth"], 1e-3) <= TOL
+    assert rel_err(solver.flow, fx["flow"], 1.0) <= TOL
     assert np.array_equal(solver.iterations, fx["iters"])
-    assert rel(solver.unknowns, fx["final_unknowns"], 1e-3) <= 1e-7
+    assert rel_err(solver.unknowns, fx["final_unknowns"], 1e-3) <= 1e-7
     if name == "gerd_gates":       # the gates did move: the outflow jumps by an order of magnitude and comes back
         q = solver.flow[:, -1]
         assert q[26] < 2200 and q[27] > 15000 and q[36] < 2200
@@ -154,14 +153,13 @@ def test_plugins_without_a_device_form_run_through_host_rows(name):
     else:
         st = solver.channel.downstream_boundary.lumped_storage
         got = np.array(st.stage_hydrograph)[1:, 1]
-        assert rel(got, fx["storage_stage"][:, 1], 1e-3) <= TOL
+        assert rel_err(got, fx["storage_stage"][:, 1], 1e-3) <= TOL
 
 
 def test_one_iteration_per_launch_equals_the_fused_loop(monkeypatch):
     """fs_batch_iterate (one Newton iteration per launch, iteration count carried across launches) against fs_batch_step
     (the whole loop in one launch) on device-evaluated boundaries, both through the instantiation fs_batch_iterate uses
     (boundary class -1): the same kernel code, so the same bits."""
-    from fixture_batch import batch_from_problems
     for name, B in (("gerd", 1), ("storage_curve_poly_losses", 1), ("irr_mixed", 1), ("gerd_ensemble", 8)):
         fx, meta = O.load_fixture(os.path.join(GOLDEN, name + ".npz"))
         probs = [O.problem_from_fixture(fx, meta, m) for m in (range(B) if meta.get("B") else [None])]
@@ -191,7 +189,6 @@ def test_restart_continues_bit_exactly():
     """A run stopped at level k and continued in a NEW batch from (state, Newton start vector, reservoir stage) gives
     the bits of the uninterrupted single launch: after the first level the start vector differs from the state (SURVEY
     F2), so both travel (fs_batch_restart).  Chunked stepping of one batch likewise."""
-    from fixture_batch import batch_from_problems
     for name in ("example", "synthetic_rect_512", "gerd", "storage_curve_power_trap", "irr_mixed", "synthetic_trap_64"):
         fx, meta = O.load_fixture(os.path.join(GOLDEN, name + ".npz"))
         probs = [O.problem_from_fixture(fx, meta, m) for m in (range(meta["B"]) if meta.get("B") else [None])]
@@ -223,7 +220,6 @@ def test_bed_level_monte_carlo_in_one_launch_equals_members_run_singly():
     """SURVEY 8b per-reach geometry: 4 096 members of cases/gerd_roseires, each with its own perturbed bed profile and
     bankfull depths (fs_batch_set_geometry_table_per_reach), in ONE launch; eight of them run alone - through the shared-table
     entry point, as a batch of one - give the same bits."""
-    from fixture_batch import boundary_spec
     fx, meta = O.load_fixture(os.path.join(GOLDEN, "gerd.npz"))
     p = O.problem_from_fixture(fx, meta)
     B, K = 4096, 4
@@ -257,7 +253,6 @@ def test_restart_guards():
     """what fs_batch_restart refuses or restricts: a storage boundary without the reservoir stage of the restart level (the
     run would silently go on from stage 0), and - for a batch that keeps a history - ranges that begin before the restart
     level (those rows were not restored; amplitudes then refer to the restart state)"""
-    from fixture_batch import batch_from_problems
     from flowsim_amd._abi import FlowsimError
     fx, meta = O.load_fixture(os.path.join(GOLDEN, "example.npz"))              # fixed depth behind a LumpedStorage
     p = O.problem_from_fixture(fx, meta)
@@ -291,7 +286,6 @@ def test_restart_guards():
 
 def test_a_new_state_closes_a_level_left_open_by_iterate():
     """fs_batch_iterate leaves its level open until every reach has accepted it; both state setters start over"""
-    from fixture_batch import batch_from_problems
     fx, meta = O.load_fixture(os.path.join(GOLDEN, "akbari.npz"))              # steady-state initial condition: one depth, one flow
     p = O.problem_from_fixture(fx, meta)
     with batch_from_problems([p], mode="table") as b:
@@ -333,7 +327,6 @@ def test_derived_fields_can_stay_on_the_device():
     """fs_batch_derive_device: the prepare_results kernel with its outputs left in HBM (buffers owned and reused by the
     handle); the host-copy entry point is the same kernel plus the download."""
     import ctypes
-    from fixture_batch import batch_from_problems
     fx, meta = O.load_fixture(os.path.join(GOLDEN, "akbari.npz"))
     p = O.problem_from_fixture(fx, meta)
     with batch_from_problems([p]) as b:
@@ -343,8 +336,8 @@ def test_derived_fields_can_stay_on_the_device():
         ptr2 = b.derive_device(0, p.nt, fields=2 | 8)
         assert ptr1 == ptr2                                      # no reallocation for a call of the same size
         host = b.derive(0, p.nt, fields=("area", "froude_number"))
-        assert rel(host["area"][:, 0], fx["derived_area"], 1e-6) <= TOL
-        assert rel(host["froude_number"][:, 0], fx["derived_froude_number"], 1e-6) <= TOL
+        assert rel_err(host["area"][:, 0], fx["derived_area"], 1e-6) <= TOL
+        assert rel_err(host["froude_number"][:, 0], fx["derived_froude_number"], 1e-6) <= TOL
 
 
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
@@ -354,7 +347,6 @@ def test_derived_fields_in_batches_of_any_size(name, dtype):
     elements allow it and falls back to single elements otherwise: B = 1 .. 4 copies of a reach (N = 30, 21, 121, so both
     paths and the ragged last thread occur in either precision) give, reach by reach, the bits of the batch of one, and
     that one the reference's prepare_results arrays"""
-    from fixture_batch import batch_from_problems
     if dtype == "f32" and name != "akbari":
         pytest.skip("fp32: the rectangular case only (N = 30: B*N % 4 is 2, 0, 2, 0)")
     fx, meta = O.load_fixture(os.path.join(GOLDEN, name + ".npz"))
@@ -372,7 +364,7 @@ def test_derived_fields_in_batches_of_any_size(name, dtype):
             ref = d
             if dtype == "f64":
                 for f in ("area", "froude_number", "velocity"):
-                    assert rel(d[f][:, 0], fx["derived_" + f][:nlev], 1e-6) <= TOL, f
+                    assert rel_err(d[f][:, 0], fx["derived_" + f][:nlev], 1e-6) <= TOL, f
         for f in fields:
             for j in range(B):
                 got = d[f][j] if f == "peak_amplitude" else d[f][:, j]
@@ -383,11 +375,8 @@ def test_derived_fields_in_batches_of_any_size(name, dtype):
 def test_batches_on_two_devices_in_one_process():
     """every entry point switches to its batch's device and back: a batch on device 1 configured and stepped
     while device 0 is current, next to a batch on device 0"""
-    from flowsim_amd import _abi as A
     if A.device_count() < 2:
         pytest.skip("one GPU visible")
-    from fixture_batch import batch_from_problems
-    import fixture_batch as FB
     from flowsim_amd import PreissmannBatch
     fx, meta = O.load_fixture(os.path.join(GOLDEN, "akbari.npz"))
     p = O.problem_from_fixture(fx, meta)
@@ -407,5 +396,5 @@ def test_batches_on_two_devices_in_one_process():
         b.step(p.nt - 1)
     for b in out:
         h, Q = b.history_arrays()
-        assert rel(Q[:, 0], fx["flow"], 1.0) <= TOL
+        assert rel_err(Q[:, 0], fx["flow"], 1.0) <= TOL
         b.close()

@@ -6,47 +6,27 @@ is that of the end of the previous call, a restart begins from FS_OK again, and 
 The failures are made by data alone (tests/failure_recipes.py; tests/test_failure_recipes.py checks on the CPU that each recipe
 fails at the level and iteration it is meant to, by a margin): none of them is a device fault."""
 import copy
+import os
 
 import numpy as np
 import pytest
 
+import case_builders as CB
+from conftest import GOLDEN
+from entry_recipes import TABLE
 import failure_recipes as FR
+from fixture_batch import boundary_spec, merge_specs
+from flowsim_amd import _abi as A
+from kernel_harness import TOL, TOL_F32, assert_same_bits, batch_for_entry, entry_id, rel_err, snapshot
 from oracle import preissmann_oracle as O
-from test_gpu_instantiations import TABLE, TOL, TOL_F32, _id, rel_err
 
 pytestmark = pytest.mark.gpu
 K = FR.K_STAR
 CASES = [(e, x) for e in TABLE for x in ("nan", "maxiter")]
 
 
-def _batch(probs, e, mode, override=None, history=None):
-    from fixture_batch import batch_from_problems
-    history = bool(e["diag"]) if history is None else history
-    return batch_from_problems(probs, mode=mode, dtype="f32" if FR.f32_of(e) else "f64", history=history, n_main_override=override)
-
-
-def _snap(b, nt, upto=None):
-    """everything a caller can read, as one dict; history rows only up to level `upto` (rows never written hold no promise)"""
-    out = dict(status=b.status().copy(), iters=b.iterations(0, nt), hyd=b.hydrographs(0, nt), state=b.state(), level=b.level)
-    if b.history:
-        out["hist"] = tuple(a[:nt if upto is None else upto + 1] for a in b.history_arrays(0, nt))
-    return out
-
-
-def _same(a, b, keys=("status", "iters", "hyd", "state", "hist")):
-    for k in keys:
-        if k in a or k in b:
-            x, y = a[k], b[k]
-            if isinstance(x, tuple):
-                assert all(np.array_equal(u, v, equal_nan=True) for u, v in zip(x, y)), k
-            else:
-                assert np.array_equal(x, y, equal_nan=True), k
-
-
 def _restore(b, good):
     """the unedited boundaries and a generous iteration cap"""
-    from fixture_batch import boundary_spec, merge_specs
-    from flowsim_amd import _abi as A
     b.set_scheme(good.theta, good.dt, good.dx, good.tol, 100)
     b.set_boundary(A.UPSTREAM, merge_specs([boundary_spec(good.us, good.nt)], 1))
     b.set_boundary(A.DOWNSTREAM, merge_specs([boundary_spec(good.ds, good.nt)], 1))
@@ -55,7 +35,7 @@ def _restore(b, good):
 # ---------------------------------------------------------------------------------------------------------------------------
 # 2. every instantiation, two exits
 # ---------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("e,exit_", CASES, ids=[f"{_id(e)}-{x}" for e, x in CASES])
+@pytest.mark.parametrize("e,exit_", CASES, ids=[f"{entry_id(e)}-{x}" for e, x in CASES])
 def test_failure_exit_of_an_instantiation(e, exit_, monkeypatch):
     good, bad, mode, override = FR.case(e, exit_)
     f32, nt = FR.f32_of(e), good.nt
@@ -66,35 +46,35 @@ def test_failure_exit_of_an_instantiation(e, exit_, monkeypatch):
     monkeypatch.setenv("FS_KERNEL_INDEX", str(e["index"]))
     storage = good.ds.storage is not None
 
-    with _batch([good], e, mode, override) as b:               # the same entry without the failure
+    with batch_for_entry([good], e, mode, override) as b:               # the same entry without the failure
         b.step(nt - 1)
         assert b.kernel_index() == e["index"] and np.all(b.status() == 0), b.status()
-        clean = _snap(b, nt)
+        clean = snapshot(b, nt)
 
-    with _batch([bad], e, mode, override) as b:                # one launch over the failing level
+    with batch_for_entry([bad], e, mode, override) as b:                # one launch over the failing level
         initial = b.state()
         stage0 = b.storage_stage() if storage else None
         b.step(n1)
         assert b.kernel_index() == e["index"]
-        one = _snap(b, nt, K - 1)
+        one = snapshot(b, nt, K - 1)
         if storage:                                            # the stage that belongs to that state, not the last accepted level's
             assert np.array_equal(b.storage_stage(), stage0)
         failed_guess = b.guess()
         b.step(1)                                              # a later launch leaves the reach alone
-        _same(one, _snap(b, nt, K - 1))
+        assert_same_bits(one, snapshot(b, nt, K - 1))
         assert b.level == n1 + 1
 
-    with _batch([bad], e, mode, override) as b:                # the same run, split ahead of the failing level
+    with batch_for_entry([bad], e, mode, override) as b:                # the same run, split ahead of the failing level
         b.step(K - 1)
         before = b.state()
         guess = b.guess()
         stage = b.storage_stage() if storage else None
         b.step(n1 - (K - 1))
-        split = _snap(b, nt, K - 1)
+        split = snapshot(b, nt, K - 1)
         if storage:
             assert np.array_equal(b.storage_stage(), stage) and stage[0] != 0
         b.step(1)
-        _same(split, _snap(b, nt, K - 1))
+        assert_same_bits(split, snapshot(b, nt, K - 1))
         # restart ahead of the failing level, with the unedited target and a generous cap: FS_OK again, and the run completes
         _restore(b, good)
         b.restart(K - 1, *before, *guess, stage)
@@ -123,7 +103,7 @@ def test_failure_exit_of_an_instantiation(e, exit_, monkeypatch):
         assert rel_err(one["hist"][0][:K, 0], d[:K], 1e-3) <= tol and rel_err(one["hist"][1][:K, 0], f[:K], 1.0) <= tol
         assert all(np.array_equal(x[:K], y[:K]) for x, y in zip(one["hist"], clean["hist"]))
     # one launch == split launches, except for the state: that of the end of the call before the failing one
-    _same(one, split, keys=("status", "iters", "hyd", "hist"))
+    assert_same_bits(one, split, fields=("status", "iters", "hyd", "hist"))
     assert all(np.array_equal(x, y) for x, y in zip(one["state"], initial))
     assert all(np.array_equal(x, y) for x, y in zip(split["state"], before))
     if exit_ == "nan":                                         # the vector the failing level ended with: not a start vector
@@ -144,7 +124,6 @@ def test_failure_exit_of_an_instantiation(e, exit_, monkeypatch):
 # ---------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", FR.STORAGE_CASES)
 def test_storage_range_exit(name, monkeypatch):
-    from flowsim_amd import _abi as A
     c = FR.storage_case(name)
     bad, mode, e = c["bad"], c["mode"], c["entry"]
     ref = FR.oracle_run(bad)
@@ -158,24 +137,24 @@ def test_storage_range_exit(name, monkeypatch):
         pair = FR._plain("f64", A.SEC_RECT_UNIFORM, 16, 4, 2 + A.BC_NORMAL_DEPTH, full=1)
         assert pair["boundary_class"] >= 2 and bad.N == 64 * pair["cells_per_thread"] * pair["waves_per_reach"]
         monkeypatch.setenv("FS_KERNEL_INDEX", str(pair["index"]))
-        with _batch([bad], pair, mode) as b:
+        with batch_for_entry([bad], pair, mode) as b:
             with pytest.raises(A.FlowsimError, match="FS_KERNEL_INDEX"):
                 b.step(1)
         monkeypatch.delenv("FS_KERNEL_INDEX")
         e = pair                         # (dtype and history of the batch below)
     else:
         monkeypatch.setenv("FS_KERNEL_INDEX", str(e["index"]))
-    with _batch([bad], e, mode) as b:
+    with batch_for_entry([bad], e, mode) as b:
         stage0 = b.storage_stage()
         b.step(nt - 2)
         chosen = TABLE[b.kernel_index()]
-        got = _snap(b, nt, k - 1)
+        got = snapshot(b, nt, k - 1)
         stages = b.storage_stages(0, nt)[:, 0]
         # the reservoir stage of a failed reach is that of the end of the previous call, like its state (one_wave, the general
         # reservoirs: levels were accepted in this launch before the failing one)
         assert np.array_equal(b.storage_stage(), stage0)
         b.step(1)
-        _same(got, _snap(b, nt, k - 1))
+        assert_same_bits(got, snapshot(b, nt, k - 1))
     if c["entry"] is None:               # ... and left alone it picks a kernel of a general class
         assert chosen["boundary_class"] in (0, 1) and chosen["section_mode"] == A.SEC_RECT_UNIFORM, chosen
     else:
@@ -203,7 +182,6 @@ def test_storage_range_exit(name, monkeypatch):
 # 4. isolation: good, failing, good in one launch
 # ---------------------------------------------------------------------------------------------------------------------------
 def _family_entry(family):
-    from flowsim_amd import _abi as A
     R, T, I = A.SEC_RECT_UNIFORM, A.SEC_TABLE, A.SEC_IRREGULAR
     if family == "one-wave":
         return FR._plain("f64", R, 2, 1, 0, full=0)
@@ -263,13 +241,11 @@ def test_a_failing_reach_leaves_its_neighbours_alone(family, exit_, monkeypatch)
     monkeypatch.setenv("FS_KERNEL_INDEX", str(e["index"]))
     def batch(probs):
         if not own_ds:
-            return _batch(probs, e, mode, override)
-        from fixture_batch import boundary_spec
-        from flowsim_amd import _abi as A
+            return batch_for_entry(probs, e, mode, override)
         plain = [copy.copy(p) for p in probs]
         for p in plain:
             p.ds = good.ds
-        b = _batch(plain, e, mode, override)
+        b = batch_for_entry(plain, e, mode, override)
         b.set_boundary_per_reach(A.DOWNSTREAM, [boundary_spec(p.ds, p.nt) for p in probs])
         return b
 
@@ -278,13 +254,13 @@ def test_a_failing_reach_leaves_its_neighbours_alone(family, exit_, monkeypatch)
             b.set_reach_tolerance(None, [100, 100])
         b.step(nt - 1)
         assert b.kernel_index() == e["index"]
-        alone = _snap(b, nt)
+        alone = snapshot(b, nt)
     with batch([good, bad, other]) as b:
         if caps:
             b.set_reach_tolerance(None, caps)
         b.step(nt - 1)
         assert b.kernel_index() == e["index"]
-        mixed = _snap(b, nt)
+        mixed = snapshot(b, nt)
     keep = [0, 2]
     assert mixed["status"][1] == ref["status"] == FR.STATUS[exit_]
     assert mixed["iters"][k, 1] == ref["iters"][k] and np.all(mixed["iters"][k + 1:, 1] == 0)
@@ -305,13 +281,12 @@ def test_one_iteration_per_launch_closes_a_failed_reach(exit_, monkeypatch):
     """fs_batch_iterate on a TABLE batch with a failing reach among good ones: the open count reaches 0 at every level, the level
     advances, and every reach - the failed one included - ends as the fused loop (fs_batch_step through the same instantiation)
     leaves it, bit for bit"""
-    from flowsim_amd import _abi as A
     e = FR.find_entry(dtype=A.F64, section_mode=A.SEC_TABLE, boundary_class=-1, long_reach=0, cells_per_thread=2)
     good, bad, mode, override = FR.maxiter_case(e) if exit_ == "maxiter" else FR.nan_case(FR._plain("f64", A.SEC_TABLE, 2, 1, 0, full=0))
     probs = [good, bad, _scaled(good, 1.1)]
     caps = [100, bad.max_iter, 100]
     nt = good.nt
-    with _batch(probs, e, mode, override) as a, _batch(probs, e, mode, override) as b:
+    with batch_for_entry(probs, e, mode, override) as a, batch_for_entry(probs, e, mode, override) as b:
         for x in (a, b):
             x.set_reach_tolerance(None, caps)
         launches = 0
@@ -324,10 +299,10 @@ def test_one_iteration_per_launch_closes_a_failed_reach(exit_, monkeypatch):
         monkeypatch.setenv("FS_KERNEL_INDEX", str(b.kernel_index()))
         a.step(nt - 1)
         assert a.kernel_index() == b.kernel_index()
-        fused, opened = _snap(a, nt, K - 1), _snap(b, nt, K - 1)
+        fused, opened = snapshot(a, nt, K - 1), snapshot(b, nt, K - 1)
         guesses = a.guess(), b.guess()
     assert fused["status"][1] == FR.STATUS[exit_] and fused["status"][0] == fused["status"][2] == 0
-    _same(fused, opened, keys=("status", "iters", "hyd"))
+    assert_same_bits(fused, opened, fields=("status", "iters", "hyd"))
     keep = [0, 2]
     assert all(np.array_equal(x[keep], y[keep]) for x, y in zip(fused["state"], opened["state"]))
     assert all(np.array_equal(x[keep], y[keep]) for x, y in zip(*guesses))
@@ -343,9 +318,6 @@ EXAMPLE_Y_MAX = 23.4      # cases/example: the oracle's reservoir stage is <= 18
 
 def test_the_drop_in_solver_raises_the_reference_errors_for_nan_and_storage_range():
     """(the max-iter error: tests/test_gpu_dropin.py, test_non_convergence_raises_like_the_reference)"""
-    import os
-    import case_builders as CB
-    from conftest import GOLDEN
     # FS_NAN: the reference notices a NaN only with diagnos (preissmann.py:133-137); without it the norm test never passes
     # and the level runs into the iteration cap (:124-126)
     for diagnos, message in ((False, "Convergence within 7 iterations couldn't be achieved."), (True, "NaN in system assembly")):

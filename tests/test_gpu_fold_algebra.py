@@ -9,21 +9,16 @@ Bounds: 1e-8 relative (the project's parity bar) with identical Newto
 import numpy as np
 import pytest
 
+from fixture_batch import batch_from_problems
+from flowsim_amd import _abi as A
+from kernel_harness import entry_of, rel_err
 from oracle import c_oracle
 from oracle import preissmann_oracle as O
+from synth import akbari_shape, normal_depth_trap, trap_problem
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-8
 TOL_F32 = 5e-4
-
-
-def rel_err(got, want, floor):
-    return float(np.max(np.abs(got - want) / np.maximum(np.abs(want), floor)))
-
-
-def entry_of(b):
-    from flowsim_amd import _abi as A
-    return A.kernel_table()[b.kernel_index()]
 
 
 def check_rows(b, refs, tol=TOL, counts=True):
@@ -60,7 +55,6 @@ def c3_problem(b, n, S0, Qb, hn, target):
 def c3_batch():
     """as bench.py builds its headline batch (build_batch, workload c3): no history, no trace, no monitor"""
     from flowsim_amd import BoundarySpec, PreissmannBatch
-    from flowsim_amd import _abi as A
     from flowsim_amd.synthetic import c3_reach_parameters, inflow_table, normal_depth_rect
     B, N, nt = C3["B"], C3["N"], C3["nt"]
     b_, n_, S0, Qb = c3_reach_parameters(0, B)
@@ -93,7 +87,6 @@ def c3_reference():
 
 
 def assert_flagship(b):
-    from flowsim_amd import _abi as A
     e = entry_of(b)
     assert (e["cells_per_thread"], e["waves_per_reach"], e["full"], e["diag"]) == (16, 4, 1, 0), e
     assert e["boundary_class"] == 2 + A.BC_NORMAL_DEPTH and e["dtype"] == A.F64, e
@@ -126,7 +119,6 @@ def test_chunked_stepping_gives_the_bits_of_one_launch():
 # ---- a bed step that differs from cell to cell: what cq dz inside kc3 can get wrong and a prismatic reach cannot show ----
 @pytest.mark.parametrize("N", [121, 100])      # 121: the ensemble shape; 100: padding rows behind node N - 1 (lanes 50 .. 63)
 def test_varying_bed_step_on_the_two_rows_per_lane_table_kernel(N):
-    from fixture_batch import batch_from_problems
     rng = np.random.default_rng(20261018 + N)
     dx, dt, nt, S0 = 500.0, 600.0, 9, 4e-4
     drop = S0 * dx * (0.25 + 1.5 * rng.random(N - 1))                 # random positive bed drops per cell, mean slope S0
@@ -134,7 +126,6 @@ def test_varying_bed_step_on_the_two_rows_per_lane_table_kernel(N):
     geo["z_bed"] = np.concatenate([np.cumsum(drop[::-1])[::-1], [0.0]])
     geo["b_main"][:] = 40.0; geo["m_main"][:] = 1.5
     geo["n_main"][:] = 0.03; geo["n_left"][:] = 0.03; geo["n_right"][:] = 0.03
-    from synth import akbari_shape, normal_depth_trap
     Qb = 120.0
     hn = normal_depth_trap(40.0, 1.5, 0.03, S0, Qb)
     tgt = np.array([akbari_shape(Qb, 2 * Qb, 5 * 3600.0, 15 * 3600.0, k * dt) for k in range(nt)])
@@ -159,9 +150,7 @@ def test_varying_bed_step_on_the_two_rows_per_lane_table_kernel(N):
 # ---- a one-wave kernel that shares the fold: bench.py's C5 reaches, 512 nodes, in both precisions ----
 def test_one_wave_trapezoid_kernel_in_both_precisions():
     from flowsim_amd import BoundarySpec, PreissmannBatch
-    from flowsim_amd import _abi as A
     from flowsim_amd.synthetic import c5_reach_parameters, inflow_table, normal_depth_trap
-    from synth import trap_problem
     B, N, nt, dt, dx = 4, 512, 9, 1800.0, 500.0
     b_, m_, n_, S0, Qb = c5_reach_parameters(0, B)
     hn = normal_depth_trap(b_, m_, n_, S0, Qb)

@@ -30,11 +30,12 @@ import functools
 import numpy as np
 import pytest
 
+from flowsim_amd import _abi as A
+from kernel_harness import TOL, assert_same_bits, entry_of, rel_err, snapshot
 from oracle import c_oracle
 from oracle import preissmann_oracle as O
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-8
 B, LEVELS = 3, 4
 THETA, DT, DX, LEVEL_TOL = 0.6, 600.0, 250.0, 1e-6
 SHAPES = {4096: (16, 4), 2048: (16, 2), 1024: (16, 1), 512: (8, 1)}
@@ -44,10 +45,6 @@ ENTRY = {"normal": (1, None, 0), "power": (0, 0, 1), "fixed": (1, 1, 1)}
 RATING_EXPONENT = 1.5
 STARTS = ("uniform", "rippled")
 RIPPLE = 0.01
-
-
-def rel_err(got, want, floor):
-    return float(np.max(np.abs(got - want) / np.maximum(np.abs(want), floor)))
 
 
 def _parameters(N):
@@ -97,7 +94,6 @@ def _reference(N, ds, start="uniform"):
 
 def _batch(N, ds, start="uniform", history=False, monitor=False):
     from flowsim_amd import BoundarySpec, PreissmannBatch
-    from flowsim_amd import _abi as A
     b_, n_, S0, Qb, hn, tgt = _parameters(N)
     b = PreissmannBatch(B, N, LEVELS + 1, dtype="f64", section_mode="rect_uniform", history=history, monitor=monitor)
     b.set_scheme(THETA, DT, DX, LEVEL_TOL, 100)
@@ -118,8 +114,7 @@ def _batch(N, ds, start="uniform", history=False, monitor=False):
 
 
 def _assert_entry(b, shape, ds, full=None, diag=None):
-    from flowsim_amd import _abi as A
-    e = A.kernel_table()[b.kernel_index()]
+    e = entry_of(b)
     full = ENTRY[ds][0] if full is None else full
     diag = ENTRY[ds][2] if diag is None else diag
     want_class = 2 + A.BC_NORMAL_DEPTH if ENTRY[ds][1] is None else ENTRY[ds][1]
@@ -140,11 +135,6 @@ def _against_the_oracle(b, refs, what):
         print(f"FOLD-READS {what} reach {j}: depth {max(eh):.3e} flow {max(eq):.3e}  counts {its[1:, j]} oracle {r['iters'][1:]}")
         assert max(eh) <= TOL and max(eq) <= TOL, (what, j, eh, eq)
         assert np.array_equal(its[:, j], r["iters"]), (what, j, its[:, j], r["iters"])
-
-
-def _snap(b):
-    nt = LEVELS + 1
-    return b.state() + b.guess() + (b.hydrographs(0, nt), b.iterations(0, nt), b.status().copy())
 
 
 @pytest.mark.parametrize("start", STARTS)
@@ -168,11 +158,9 @@ def test_two_launches_of_two_levels_give_the_bits_of_one_of_four(N, ds, start):
             for n in chunks:
                 b.step(n)
             _assert_entry(b, SHAPES[N], ds)
-            out.append(_snap(b))
-    assert np.all(out[0][-1] == 0), out[0][-1]
-    names = ("depth", "flow", "next start depth", "next start flow", "hydrograph rows", "Newton counts", "status")
-    for name, one, two in zip(names, *out):
-        assert np.array_equal(one, two), (N, ds, start, name)
+            out.append(snapshot(b, LEVELS + 1, fields=("state", "guess", "hyd", "iters", "status")))
+    assert np.all(out[0]["status"] == 0), out[0]["status"]
+    assert_same_bits(*out, what=(N, ds, start))
 
 
 @pytest.mark.parametrize("start", STARTS)

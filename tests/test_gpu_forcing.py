@@ -15,6 +15,7 @@ from flowsim_amd import _abi as A
 from flowsim_amd.batch import BoundarySpec, PreissmannBatch
 from flowsim_amd.forcing import PoolSpec
 from flowsim_amd.hydromodel.hydrograph import Hydrograph
+from kernel_harness import rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -225,13 +226,9 @@ def test_order_and_misuse_leave_the_batch_usable(fx, pool):
 TOL = 1e-8                                              # the suite's parity bar (tests/test_gpu_dropin.py)
 
 
-def rel(a, b, floor):
-    return float(np.max(np.abs(a - b) / np.maximum(np.abs(b), floor)))
-
-
 def assert_same_run(got, want, label):
     for col, floor in enumerate((1e-3, 1.0, 1e-3, 1.0)):          # h[0], Q[0], h[N-1], Q[N-1]
-        err = rel(got["hydrographs"][:, col], want["hydrographs"][:, col], floor)
+        err = rel_err(got["hydrographs"][:, col], want["hydrographs"][:, col], floor)
         print(label, "column", col, "relative error", err)
         assert err <= TOL, (label, col, err)
     assert np.array_equal(got["iterations"], want["iterations"]), label

@@ -7,13 +7,15 @@ Newton counts - and reaches that converge early must sit still while the others 
 import numpy as np
 import pytest
 
+from entry_recipes import prismatic_problem
+from fixture_batch import boundary_spec, hetero_batch_from_problems
+from flowsim_amd import BoundarySpec, _abi as A
 from oracle import preissmann_oracle as O
 
 pytestmark = pytest.mark.gpu
 
 
 def problems(B, seed=11):
-    from test_gpu_instantiations import prismatic_problem
     rng = np.random.default_rng(seed)
     out = []
     for i in range(B):
@@ -30,7 +32,6 @@ def problems(B, seed=11):
 
 
 def run_device(ps):
-    from fixture_batch import hetero_batch_from_problems
     with hetero_batch_from_problems(ps, mode="table", history=False) as b:
         b.step(ps[0].nt - 1)
         assert np.all(b.status() == 0)
@@ -38,8 +39,6 @@ def run_device(ps):
 
 
 def run_host_rows(ps):
-    from fixture_batch import boundary_spec, hetero_batch_from_problems
-    from flowsim_amd import BoundarySpec, _abi as A
     a = np.array([p.ds.rc["a"] for p in ps]); e = np.array([p.ds.rc["b"] for p in ps])
     with hetero_batch_from_problems(ps, mode="table", history=False) as b:
         b.set_boundary(A.DOWNSTREAM, BoundarySpec(A.BC_HOST_ROW))       # batch-wide kind (flowsim_abi.h); upstream stays per reach
@@ -73,8 +72,6 @@ def test_a_batch_of_host_evaluated_boundaries_follows_the_device_kind():
 
 def run_mixed(ps, host):
     """the reaches in `host` bring their downstream row from the host, the others keep the device's rating curve - one batch"""
-    from fixture_batch import boundary_spec, hetero_batch_from_problems
-    from flowsim_amd import BoundarySpec, _abi as A
     a = np.array([p.ds.rc["a"] for p in ps]); e = np.array([p.ds.rc["b"] for p in ps])
     with hetero_batch_from_problems(ps, mode="table", history=False) as b:
         b.set_boundary_per_reach(A.DOWNSTREAM, [BoundarySpec(A.BC_HOST_ROW) if r in host else boundary_spec(p.ds, p.nt) for r, p in enumerate(ps)])
@@ -116,8 +113,6 @@ def test_host_rows_on_some_reaches_of_a_batch_only():
 
 def test_the_ends_come_back_as_they_are_on_the_device():
     """fs_batch_get_boundary_iterate against the full Newton vector (fs_batch_get_guess), ragged reaches, fp64"""
-    from fixture_batch import hetero_batch_from_problems
-    from flowsim_amd import BoundarySpec, _abi as A
     ps = problems(17, seed=5)
     with hetero_batch_from_problems(ps, mode="table", history=False) as b:
         b.set_boundary(A.DOWNSTREAM, BoundarySpec(A.BC_HOST_ROW))

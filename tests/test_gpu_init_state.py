@@ -11,8 +11,10 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from fixture_batch import batch_from_problems, is_rect_uniform, per_reach_polyline_batch
 from flowsim_amd import PreissmannBatch
 from flowsim_amd import _abi as A
+from kernel_harness import rel_err
 from oracle import preissmann_oracle as O
 from oracle.gen_random_sweep import build_from_recipe
 
@@ -74,7 +76,6 @@ def check_against(h, Q, members, what):
 
 # ---- 1. backwater --------------------------------------------------------------------------------------------------------------
 def test_backwater_matches_the_reference_in_one_heterogeneous_launch():
-    from fixture_batch import is_rect_uniform
     cases = BY_IC["GVF_equation"]
     assert len(cases) == 23 and {m["N"] for _, _, m in cases} >= {3, 257}
     probs = [O.problem_from_fixture(fx, m) for _, fx, m in cases]
@@ -105,7 +106,6 @@ def mirror_bed_slopes(m):
 
 
 def test_normal_depth_matches_the_reference(monkeypatch):
-    from fixture_batch import batch_from_problems
     cases = BY_IC["steady-state"]
     assert len(cases) == 19
     trap = [c for c in cases if c[2]["family"] != "polyline"]
@@ -154,7 +154,6 @@ def test_linear_matches_the_reference():
 
 # ---- 4. the ensemble form ------------------------------------------------------------------------------------------------------
 def test_ensemble_members_start_from_their_own_backwater_profile():
-    from fixture_batch import batch_from_problems
     path = os.path.join(GOLDEN, "gerd_ensemble.npz")
     fx, meta = O.load_fixture(path)
     probs = [O.problem_from_fixture(fx, meta, k) for k in range(meta["B"])]
@@ -173,7 +172,6 @@ def test_ensemble_members_start_from_their_own_backwater_profile():
 # ---- 5. polylines --------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("walk", [False, True], ids=["stage_tables", "edge_walk"])
 def test_polyline_backwater_matches_the_reference(walk, monkeypatch):
-    from fixture_batch import per_reach_polyline_batch
     gold = np.load(os.path.join(GOLDEN, "init_state_polyline.npz"))
     poly = [c for c in CASES if c[2]["family"] == "polyline"]
     assert len(poly) == 12
@@ -198,7 +196,6 @@ def first_case(ic, family, min_nt=4):
 
 @pytest.mark.parametrize("which", ["trapezoid", "polyline"])
 def test_the_batch_is_where_set_state_would_leave_it(which):
-    from fixture_batch import batch_from_problems
     i, fx, m = first_case("GVF_equation", "trap") if which == "trapezoid" else first_case("steady-state", "polyline")
     p = O.problem_from_fixture(fx, m)
     mode = "table" if which == "trapezoid" else "irregular"
@@ -223,8 +220,7 @@ def test_the_batch_is_where_set_state_would_leave_it(which):
             assert np.array_equal(fb, ft)
         its = b.iterations(0, 4)
         assert np.array_equal(its, twin.iterations(0, 4))
-    rel = lambda got, want, floor: float(np.max(np.abs(got - want) / np.maximum(np.abs(want), floor)))
-    assert rel(hb[:, 0], fx["depth"][:4], 1e-3 * m["h_n"]) <= 1e-8 and rel(Qb[:, 0], fx["flow"][:4], 1e-3 * m["Qb"]) <= 1e-8
+    assert rel_err(hb[:, 0], fx["depth"][:4], 1e-3 * m["h_n"]) <= 1e-8 and rel_err(Qb[:, 0], fx["flow"][:4], 1e-3 * m["Qb"]) <= 1e-8
     assert np.array_equal(its[:, 0], fx["iters"][:4])
 
 

@@ -9,14 +9,13 @@ tables and the irr_* / sweep fixtures): 1e-8 with identical Newton counts, and c
 import numpy as np
 import pytest
 
+from fixture_batch import per_reach_polyline_batch
+from flowsim_amd import _abi as A
+from kernel_harness import rel_err
 from oracle import preissmann_oracle as O
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-8
-
-
-def rel_err(got, want, floor):
-    return float(np.max(np.abs(got - want) / np.maximum(np.abs(want), floor)))
 
 
 def long_polyline_problem(N, levee, seed, n_steps):
@@ -61,8 +60,6 @@ def long_polyline_problem(N, levee, seed, n_steps):
 
 
 def test_long_polyline_reaches_against_the_oracle():
-    from fixture_batch import per_reach_polyline_batch
-    from flowsim_amd import _abi as A
     n_steps = 2
     probs = [long_polyline_problem(3000, False, 11, n_steps), long_polyline_problem(9000, True, 12, n_steps)]
     # the levee reach really has two wetted runs somewhere (the path that walks temporary sub-sections)

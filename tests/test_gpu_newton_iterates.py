@@ -32,13 +32,17 @@ import functools
 import numpy as np
 import pytest
 
+from entry_recipes import TABLE, fixture_problem
+import failure_recipes as FR
+from fixture_batch import hetero_batch_from_problems
+from flowsim_amd import _abi as A
 import iterate_recipes as IR
+from kernel_harness import TOL, TOL_F32, batch_for_entry, capacity, entry_id, entry_of, rel_err
 from oracle import preissmann_oracle as O
-from test_gpu_instantiations import TABLE, TOL, TOL_F32, _id, fixture_problem, rel_err
 
 pytestmark = pytest.mark.gpu
 FS_MAX_ITER = 1
-IDS = [_id(e) for e in TABLE]
+IDS = [entry_id(e) for e in TABLE]
 
 
 def family(e):
@@ -48,13 +52,10 @@ def family(e):
 
 
 def _batch(probs, e, mode, override, **kw):
-    from fixture_batch import batch_from_problems
-    cap = 64 * e["cells_per_thread"] * e["waves_per_reach"] * (64 // e["waves_per_reach"] if (e.get("long_reach") or e.get("team")) else 1)
-    assert probs[0].N <= cap, "recipe does not fit the entry"
+    assert probs[0].N <= capacity(e), "recipe does not fit the entry"
     if override is not None:
         override = np.broadcast_to(override, (len(probs),))
-    kw.setdefault("history", bool(e["diag"]))
-    return batch_from_problems(probs, mode=mode, dtype="f32" if IR.f32_of(e) else "f64", n_main_override=override, **kw)
+    return batch_for_entry(probs, e, mode, override, **kw)
 
 
 def _compare(e, what, guess, refs, key):
@@ -64,7 +65,7 @@ def _compare(e, what, guess, refs, key):
         h, Q = IR.unknowns(ref[key])
         eh, eq = rel_err(guess[0][r], h, 1e-3), rel_err(guess[1][r], Q, 1.0)
         worst = [max(worst[0], eh), max(worst[1], eq)]
-    print(f"ITERATE {_id(e)} | {family(e)} | {what} | depth {worst[0]:.3e} flow {worst[1]:.3e}")
+    print(f"ITERATE {entry_id(e)} | {family(e)} | {what} | depth {worst[0]:.3e} flow {worst[1]:.3e}")
     return worst
 
 
@@ -113,7 +114,7 @@ def test_level_2_iterate_against_the_oracle(e, monkeypatch):
         assert b.kernel_index() == e["index"]
         status, its, guess = b.status().copy(), b.iterations(0, 3), b.guess()
     want = np.array([ref[(2, 1)]["iters"][1] for ref in refs])
-    print(f"ITERATE {_id(e)} | {family(e)} | level-1 counts {its[1]} oracle {want}")
+    print(f"ITERATE {entry_id(e)} | {family(e)} | level-1 counts {its[1]} oracle {want}")
     eh, eq = _compare(e, "level 2, m = 1", guess, refs, (2, 1))
     assert np.all(first == 0), first
     assert np.all(status == FS_MAX_ITER), status
@@ -132,10 +133,9 @@ def _traced(index):
 TRACED = [e for e in TABLE if e["diag"] and not IR.f32_of(e)]
 
 
-@pytest.mark.parametrize("e", TRACED, ids=[_id(e) for e in TRACED])
+@pytest.mark.parametrize("e", TRACED, ids=[entry_id(e) for e in TRACED])
 def test_residual_trace_from_the_perturbed_start(e, monkeypatch):
     """two levels with the residual trace on: the norm of every Newton iteration against the oracle's"""
-    from flowsim_amd import _abi as A
     probs, mode, override = IR.iterate_case(e)
     p0 = probs[0]
     monkeypatch.setenv("FS_KERNEL_INDEX", str(e["index"]))
@@ -154,7 +154,7 @@ def test_residual_trace_from_the_perturbed_start(e, monkeypatch):
             got = trace[k, :len(want), r]
             assert np.all(trace[k, len(want):, r] == 0)
             worst = max(worst, float(np.max(np.abs(got - want) / (1e-6 * want + 1e-9 * want[0] + 1e-12))))
-    print(f"ITERATE {_id(e)} | {family(e)} | residual trace, counts {its[1:, 0]} | worst deviation {worst:.3e} of the allowance")
+    print(f"ITERATE {entry_id(e)} | {family(e)} | residual trace, counts {its[1:, 0]} | worst deviation {worst:.3e} of the allowance")
     for r, ref in enumerate(_traced(e["index"])):
         for k in (1, 2):
             want = np.array([err for lvl, err in ref["norms"] if lvl == k])[:A.TRACE_CAP]
@@ -163,8 +163,6 @@ def test_residual_trace_from_the_perturbed_start(e, monkeypatch):
 
 # ---- fs_batch_iterate: one launch per Newton iteration, the same vectors ----
 def _iterate_entry(kind):
-    import failure_recipes as FR
-    from flowsim_amd import _abi as A
     if kind == "table":
         return FR.find_entry(dtype=A.F64, section_mode=A.SEC_TABLE, boundary_class=-1, long_reach=0, cells_per_thread=2)
     return FR._plain("f64", A.SEC_IRREGULAR, 2, 1, 0, full=0)
@@ -172,7 +170,6 @@ def _iterate_entry(kind):
 
 @pytest.mark.parametrize("kind", ["table", "polyline"])
 def test_one_iteration_per_launch_gives_the_same_iterates(kind):
-    from flowsim_amd import _abi as A
     e = _iterate_entry(kind)
     probs, mode, override = IR.iterate_case(e)
     refs = IR.references(e)
@@ -182,7 +179,7 @@ def test_one_iteration_per_launch_gives_the_same_iterates(kind):
             for _ in range(m):
                 n_open = b.iterate()
                 assert n_open == IR.B and b.level == 0
-            chosen = A.kernel_table()[b.kernel_index()]
+            chosen = entry_of(b)
             assert chosen["section_mode"] == e["section_mode"] and chosen["dtype"] == A.F64
             assert np.all(b.status() == 0)
             worst.append(_compare(e, f"fs_batch_iterate x {m}", b.guess(), refs, (1, m)))
@@ -192,7 +189,6 @@ def test_one_iteration_per_launch_gives_the_same_iterates(kind):
 
 def test_one_iteration_per_launch_on_a_ragged_batch():
     """three channels of their own, 26 / 41 / 21 nodes, one batch (fs_batch_set_reach_nodes): each reach's iterates are the oracle's"""
-    from fixture_batch import hetero_batch_from_problems
     probs = [IR.perturbed(fixture_problem(name, 8), seed) for name, seed in zip(("bc_trap_poly", "bc_compound_normal", "storage_curve_closed"), IR.SEEDS)]
     assert len({p.N for p in probs}) == 3
     for m in (1, 2):

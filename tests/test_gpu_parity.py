@@ -11,7 +11,12 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, fixture_paths
+from fixture_batch import batch_from_problems, boundary_spec, hetero_batch_from_problems, is_rect_uniform
+from flowsim_amd import _abi as A
+from kernel_harness import rel_err
+from oracle import c_oracle
 from oracle import preissmann_oracle as O
+from synth import rect_problem, trap_problem
 
 pytestmark = pytest.mark.gpu
 
@@ -20,17 +25,11 @@ FIXTURES = fixture_paths()
 
 
 def boundary_kind(bc):
-    from fixture_batch import boundary_spec
     return boundary_spec(bc, 4).kind
 
 
 def is_rect(p):
-    from fixture_batch import is_rect_uniform
     return is_rect_uniform(p)
-
-
-def rel_err(got, want, floor):
-    return float(np.max(np.abs(got - want) / np.maximum(np.abs(want), floor)))
 
 
 def problems_of(path):
@@ -45,7 +44,6 @@ def golden(fx, name, i, B, base_ndim):
 
 
 def run_and_compare(path, mode, shape=None, monkeypatch=None):
-    from fixture_batch import batch_from_problems
     fx, meta, probs = problems_of(path)
     B = meta.get("B")
     if "geo_irr_npts" in fx.files and mode == "table":
@@ -126,7 +124,6 @@ def test_irregular_mode_kernel_shapes(shape, monkeypatch):
 @pytest.mark.parametrize("name", ["irr_single", "irr_levee", "irr_mixed"])
 def test_irregular_derived_fields(name):
     """fs_batch_derive on polyline nodes against the reference's Solver.prepare_results output."""
-    from fixture_batch import batch_from_problems
     fx, meta, probs = problems_of(os.path.join(GOLDEN, name + ".npz"))
     with batch_from_problems(probs) as b:
         b.step(probs[0].nt - 1)
@@ -153,8 +150,6 @@ def test_irregular_mode_rejects_bad_input():
 
 def test_oracle_agreement_on_fresh_inputs():
     """Seeded inputs that are not in any fixture: HIP path vs CPU oracle (rect channel, N=300)."""
-    from fixture_batch import batch_from_problems
-    from synth import rect_problem
     probs = [rect_problem(300, seed=s, n_steps=6) for s in range(5)]
     with batch_from_problems(probs) as b:
         b.step(6)
@@ -172,8 +167,6 @@ def test_batch_invariance_bitwise():
     (The two lanes that share a node move their copies of it by the same bits - the shared node's p comes from the same
     two numbers on both sides - so what a launch writes back at its end is exactly what the registers would have
     carried on.)"""
-    from fixture_batch import batch_from_problems
-    from synth import rect_problem
     for N in (1000, 4096, 300):
         probs = [rect_problem(N, seed=s, n_steps=4) for s in range(6)]
         with batch_from_problems(probs) as b:
@@ -195,8 +188,6 @@ def test_batch_invariance_bitwise():
 def test_steady_state_is_a_fixed_point():
     """Uniform flow at normal depth with constant inflow: one Newton iteration per level, state unchanged
     (property (v))."""
-    from fixture_batch import batch_from_problems
-    from synth import rect_problem
     probs = [rect_problem(4096, seed=s, n_steps=3, steady=True) for s in range(3)]
     with batch_from_problems(probs, history=False) as b:
         b.step(3)
@@ -211,8 +202,6 @@ def test_steady_state_is_a_fixed_point():
 
 def test_full_width_reach_against_oracle():
     """N = 4096 (BASELINE configs[2] node count): 2 reaches x 2 levels against the oracle."""
-    from fixture_batch import batch_from_problems
-    from synth import rect_problem
     probs = [rect_problem(4096, seed=s, n_steps=2) for s in (11, 12)]
     with batch_from_problems(probs) as b:
         b.step(2)
@@ -231,7 +220,6 @@ def test_api_misuse_is_reported_not_computed():
     """Argument checks of the C ABI: the messages of the reference where it has them
     (boundary.py:33, :83-87), otherwise a plain description; nothing runs with a half-configured batch."""
     from flowsim_amd import BoundarySpec, PreissmannBatch
-    from flowsim_amd import _abi as A
     import ctypes as C
     E = A.FlowsimError
     for bad in ((0, 30, 5), (1, 1, 5), (1, 30, 1), (1, 40000, 5)):        # (reaches beyond 32 768 nodes: no kernel, not even the multi-pass one)
@@ -277,7 +265,6 @@ def test_api_misuse_is_reported_not_computed():
         with pytest.raises(E, match="no field requested|without FS_FLAG_HISTORY"):
             nb.derive_device(0, 2, fields=0)
     # the one-iteration-per-launch entry points (host-evaluated boundary rows)
-    from fixture_batch import batch_from_problems
     fx, meta = O.load_fixture(os.path.join(GOLDEN, "bc_compound_normal.npz"))
     p = O.problem_from_fixture(fx, meta)
     with batch_from_problems([p], mode="table") as tb:
@@ -300,9 +287,6 @@ def test_api_misuse_is_reported_not_computed():
 def test_eight_wave_shape_on_a_full_width_reach(monkeypatch):
     """M = 8, W = 8 (two waves per SIMD; level-0 tree records kept in registers and handed to the
     pair lane by quad_perm in the down-sweep): not the default shape, selected here through the override."""
-    from fixture_batch import batch_from_problems
-    from oracle import c_oracle
-    from synth import rect_problem
     monkeypatch.setenv("FS_KERNEL_SHAPE", "8,8")
     probs = [rect_problem(4096, seed=s, n_steps=2) for s in (21, 22)]
     with batch_from_problems(probs) as b:
@@ -321,8 +305,6 @@ def test_general_storage_row_needs_a_table_or_polyline_batch():
     """The uniform-geometry kernels are compiled without the general reservoir row (its Brent iteration is the one
     out-of-line call of the boundary code and costs every kernel that carries it ~100 registers): such a batch
     is refused when it is stepped, with the way out in the message; table mode takes the same channel."""
-    from fixture_batch import batch_from_problems
-    from flowsim_amd import _abi as A
     fx, meta, probs = problems_of(os.path.join(GOLDEN, "storage_curve_closed.npz"))
     p = probs[0]
     assert boundary_kind(p.ds) == A.BC_STORAGE_CURVE
@@ -337,8 +319,6 @@ def test_general_storage_row_needs_a_table_or_polyline_batch():
 
 def test_max_iter_and_status_reporting():
     """max_iter exhausted -> status 1 and the level is not advanced (preissmann.py:124-126)."""
-    from fixture_batch import batch_from_problems
-    from synth import rect_problem
     p = rect_problem(200, seed=3, n_steps=2)
     p.max_iter = 1
     with batch_from_problems([p]) as b:
@@ -351,9 +331,6 @@ def test_max_iter_and_status_reporting():
 def test_ragged_node_counts_against_the_c_oracle(N):
     """Smallest (one cell), off-by-one around every lane / wave capacity and the largest supported
     reach (4096 nodes): padding cells, the last-lane bookkeeping and the cross-wave fold."""
-    from fixture_batch import batch_from_problems
-    from oracle import c_oracle
-    from synth import rect_problem
     probs = [rect_problem(N, seed=100 + N + s, n_steps=3) for s in range(2)]
     with batch_from_problems(probs) as b:
         b.step(3)
@@ -376,10 +353,7 @@ def test_reaches_longer_than_the_lane_grid_against_the_c_oracle(N, mode, monkeyp
     FS_NO_TEAM=1 - the multi-pass kernel of fs_long.hpp (state in HBM / L2, two sweeps per Newton iteration).  Same bar as
     everywhere: the pivoted C oracle to 1e-8 with identical Newton counts; three reaches per batch, chunked stepping equal to one
     launch bit for bit."""
-    from fixture_batch import batch_from_problems, hetero_batch_from_problems
     from flowsim_amd import _abi as A_
-    from oracle import c_oracle
-    from synth import rect_problem
     multipass = mode.endswith("-multipass")
     mode = mode.split("-")[0]
     if multipass:
@@ -418,9 +392,6 @@ def test_long_reaches_of_different_lengths_in_one_batch():
     kernel: its state loads and stores run with consecutive lanes on consecutive nodes and are transposed through LDS, so the
     clamped copies beyond a reach's last node, passes that are half empty and waves that hold no node at all each occur here -
     seeded lengths around the pass (2 048 rows) and wave (512 rows) boundaries.  Pivoted C oracle, 1e-8, equal Newton counts."""
-    from fixture_batch import hetero_batch_from_problems
-    from oracle import c_oracle
-    from synth import rect_problem
     rng = np.random.default_rng(4242)
     lengths = [4097, 9999, 2048 * 3 + 1, 2048 * 4, 512 * 9 + 1, int(rng.integers(4200, 9000)), int(rng.integers(4200, 9000))]
     probs = []
@@ -448,9 +419,7 @@ def test_gerd_roseires_at_a_spatial_step_of_25_m():
     """cases/gerd_roseires refined to dx = 25 m: 4 817 nodes of compound sections with curvature and the gate curve - more than
     a table kernel keeps on chip; against the C oracle over the first levels"""
     from cases.gerd_roseires.model import build as build_gerd
-    from fixture_batch import batch_from_problems
     from flowsim_amd.hydromodel.preissmann import boundary_to_spec
-    from oracle import c_oracle
     solver, _ = build_gerd(inflow_hyd_func=None, sim_duration=4 * 3600, spatial_step=25)
     ch = solver.channel
     N = solver.number_of_nodes
@@ -483,8 +452,6 @@ def test_gerd_roseires_at_a_spatial_step_of_25_m():
 def test_failing_reach_does_not_disturb_its_neighbours():
     """One reach of a batch runs out of Newton iterations (its inflow jumps by three orders of
     magnitude); the others finish, bit-identical to a batch without it, and each status is its own."""
-    from fixture_batch import batch_from_problems
-    from synth import rect_problem
     probs = [rect_problem(300, seed=40 + s, n_steps=4) for s in range(4)]
     bad = rect_problem(300, seed=44, n_steps=4)
     bad.us.target = bad.us.target.copy()
@@ -513,7 +480,6 @@ def test_failing_reach_does_not_disturb_its_neighbours():
 # ---------------------------------------------------------------------------------------------
 def trap_batch(fx, meta, dtype="f64", tol=None, history=True):
     from flowsim_amd import BoundarySpec, PreissmannBatch
-    from flowsim_amd import _abi as A
     B, N, nt = meta["B"], meta["N"], meta["nt"]
     prm = fx["params"]                      # [B, (b, m, n, S0, Q_base, h_n, rc_a, rc_b)]
     b = PreissmannBatch(B, N, nt, dtype=dtype, section_mode="trap_uniform", history=history)
@@ -556,7 +522,6 @@ def test_fp32_trapezoid_tracks_the_fp64_reference():
 
 
 def test_fp32_rectangular_tracks_the_fp64_reference():
-    from fixture_batch import batch_from_problems
     fx, meta, probs = problems_of(os.path.join(GOLDEN, "synthetic_rect_512.npz"))
     for p in probs:
         p.tol = 1e-3
@@ -581,7 +546,6 @@ SINGULAR_PIVOT_REACHES = [(4, 506130), (9, 111108), (3, 154763), (3, 180059), (3
 
 def _singular_pivot_problems(N, n_steps, tol):
     from flowsim_amd.synthetic import c5_reach_parameters
-    from synth import trap_problem
     probs = []
     for seed, idx in SINGULAR_PIVOT_REACHES:
         b, m, n, S0, Qb = (float(v[0]) for v in c5_reach_parameters(idx, 1, seed))
@@ -594,7 +558,6 @@ def test_fp32_rides_through_a_singular_pivot_block(shape, monkeypatch):
     """fp32, 512 nodes, the whole hydrograph: every reach converges at every level - no pivoting, no perturbation -
     and stays within 5e-3 of the fp64 run of the same reach (the fp32 mode stops Newton at a residual norm of
     1e-3)."""
-    from fixture_batch import batch_from_problems
     monkeypatch.setenv("FS_KERNEL_SHAPE", shape)
     n_steps = 36
     out = {}
@@ -612,8 +575,6 @@ def test_fp32_rides_through_a_singular_pivot_block(shape, monkeypatch):
 
 def test_fp64_near_singular_pivot_block_against_the_c_oracle():
     """The same reaches in fp64 against the partially pivoted banded LU of the C oracle."""
-    from fixture_batch import batch_from_problems
-    from oracle import c_oracle
     probs = _singular_pivot_problems(500, 6, 1e-6)     # 8 cells per lane, ragged, rating-curve instantiation
     with batch_from_problems(probs, mode="trap_uniform") as b:
         b.step(6)
@@ -632,9 +593,6 @@ def test_trapezoid_reaches_that_fill_the_wave_exactly(N):
     """General-section kernels take a lane's last node from its right neighbour (kShareNode, fs_kernel.hpp); lane 63 has none
     and evaluates the node itself when the reach fills the wave to the last cell (N - 1 = 64 M), one cell
     less leaves a padding cell there, one more moves to the next shape."""
-    from fixture_batch import batch_from_problems
-    from oracle import c_oracle
-    from synth import trap_problem
     probs = [trap_problem(30.0 + 10 * i, 1.5, 0.03, 4e-4, 60.0 + 25 * i, N, 4, dt=900.0, dx=400.0) for i in range(3)]
     with batch_from_problems(probs, mode="trap_uniform") as b:
         b.step(4)
@@ -652,9 +610,6 @@ def test_flow_regime_grid_against_the_c_oracle():
     """Bed slope x spatial step x base flow, from backwater-resolved grids (h / h* = 250) to kinematic ones
     (h / h* = 0.02, Froude up to 0.8): the unpivoted tree elimination against partially pivoted LU on both
     sides of the depth h* where round 1's pivot block changed sign (tools/scan_regimes.py prints the table)."""
-    from fixture_batch import batch_from_problems
-    from oracle import c_oracle
-    from synth import trap_problem
     for S0 in (1e-4, 1e-3, 5e-3):
         for dx in (100.0, 500.0, 2000.0):
             for q in (0.3, 1.0, 4.0):
@@ -676,7 +631,6 @@ def test_kernels_compiled_for_a_boundary_pair_match_the_general_ones(case, monke
     general kernels of the same shape (FS_KERNEL_GENERAL=1): same rows, same source - equal iteration counts,
     hydrographs equal to a few ulp (the compiler contracts a row inlined next to one kind differently from
     the same row next to nine), and fewer registers (which is the point of them)."""
-    from fixture_batch import batch_from_problems
     if case.startswith("rect"):
         _, _, probs = problems_of(os.path.join(GOLDEN, "synthetic_rect_512.npz"))
         mode = "rect_uniform"
@@ -705,7 +659,6 @@ def test_kernels_compiled_for_a_boundary_pair_match_the_general_ones(case, monke
 def test_batches_without_history_run_the_same_numbers(case, monkeypatch):
     """Batches created without FS_FLAG_HISTORY / FS_FLAG_TRACE get the instantiations compiled without those
     stores (DIAG = 0, fs_entry_list.hpp): same hydrographs to a few ulp, same iteration counts."""
-    from fixture_batch import batch_from_problems
     if case.startswith("trap"):
         probs, mode = _singular_pivot_problems(512, 5, 1e-6)[:3], "trap_uniform"
     else:
@@ -731,7 +684,6 @@ def test_full_size_batch_properties():
     (ii) identical to the 256-reach batch, (iii) every reach converges, (iv) mass balance of the
     routed wave: inflow - outflow volume equals the change of storage to 1e-9 of the inflow volume."""
     from flowsim_amd import BoundarySpec, PreissmannBatch
-    from flowsim_amd import _abi as A
     from flowsim_amd.synthetic import c3_reach_parameters, inflow_table, normal_depth_rect
     N, K, dt, dx = 4096, 6, 600.0, 250.0
     b0, n0, S0, Qb0 = c3_reach_parameters(0, 256)
@@ -772,9 +724,6 @@ def test_full_size_batch_properties():
 
 def test_sixteen_full_width_reaches_against_the_c_oracle():
     """N = 4096, 16 different channels, 6 levels: HIP path vs the compiled CPU oracle."""
-    from fixture_batch import batch_from_problems
-    from oracle import c_oracle as CO
-    from synth import rect_problem
     probs = [rect_problem(4096, seed=100 + s, n_steps=6) for s in range(16)]
     with batch_from_problems(probs, mode="rect_uniform") as b:
         b.step(6)
@@ -782,7 +731,7 @@ def test_sixteen_full_width_reaches_against_the_c_oracle():
         its = b.iterations()
         assert np.all(b.status() == 0)
     for i, p in enumerate(probs):
-        out = CO.run(p)
+        out = c_oracle.run(p)
         assert rel_err(h[:, i], out["depth"], 1e-3) <= TOL
         assert rel_err(Q[:, i], out["flow"], 1.0) <= TOL
         assert np.array_equal(its[:, i], out["iters"])

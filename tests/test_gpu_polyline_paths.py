@@ -14,43 +14,27 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from flowsim_amd import _abi as A
 from oracle import preissmann_oracle as O
 
+from fixture_batch import batch_from_problems, hetero_batch_from_problems, per_reach_polyline_batch
+from kernel_harness import TOL, capacity, kernel_table, rel_err
 import poly_edges as PE
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-8
 
 
-def rel_err(got, want, floor):
-    return float(np.max(np.abs(got - want) / np.maximum(np.abs(want), floor)))
-
-
-def _entries():
-    try:
-        from flowsim_amd import _abi as A
-        return [e for e in A.kernel_table() if e["section_mode"] == A.SEC_IRREGULAR]
-    except Exception:            # library not built: collection must not fail (the gpu run builds first)
-        return []
-
-
-ENTRIES = _entries()
+ENTRIES = [e for e in kernel_table() if e["section_mode"] == A.SEC_IRREGULAR]
 
 
 def test_the_polyline_entries_are_there():
     """an empty table (library missing or not importable) must fail here, not collect every test below as a skip"""
-    from flowsim_amd import _abi as A
     assert ENTRIES and len(ENTRIES) == sum(e["section_mode"] == A.SEC_IRREGULAR for e in A.kernel_table())
 
 
 def _id(e):
     return (f"{e['index']:03d}-{e['cells_per_thread']}x{e['waves_per_reach']}-bc{e['boundary_class']}"
             f"{'' if e['diag'] else '-nodiag'}{'-long' if e.get('long_reach') else ''}")
-
-
-def capacity(e):
-    cap = 64 * e["cells_per_thread"] * e["waves_per_reach"]
-    return cap * (64 // e["waves_per_reach"]) if e.get("long_reach") else cap
 
 
 def fits(e, p):
@@ -85,7 +69,6 @@ def fixture(name):
 
 def run_entry(e, p, monkeypatch, history, walk=False):
     """(hydrographs, final state, iterations, history or None, poly_tables) of problem p on entry e"""
-    from fixture_batch import batch_from_problems
     monkeypatch.setenv("FS_KERNEL_INDEX", str(e["index"]))
     if walk:
         monkeypatch.setenv("FS_POLY_WALK", "1")
@@ -172,7 +155,6 @@ BATCH_ENTRIES = [e for e in ENTRIES if not e.get("long_reach") and e["boundary_c
 def test_batch_placement_is_bitwise(e, monkeypatch):
     """~70 reaches, every one its own channel and node count, channels at indices 0, 1, 63, 64 and B-1 among others: each reach
     gives the bits of its own one-reach run on the same entry (memory: B N (KP + 32 P) 8 bytes of stage tables, ~60 MB here)"""
-    from fixture_batch import per_reach_polyline_batch
     base = [common(case(s)[0]) for s in BATCH_KINDS]
     base = [q for q in base if fits(e, q)]
     B = 70
@@ -219,12 +201,9 @@ def test_batch_placement_is_bitwise(e, monkeypatch):
 def test_launch_context_does_not_leak(e, monkeypatch):
     """a case, then a class -1 per-reach table batch (another kernel, large LDS, other data), then the same case: the same bits.  A read
     of LDS or registers before they are written shows up here as a difference."""
-    from fixture_batch import batch_from_problems
     spec = specs_for(e)[0] if e.get("long_reach") else ("near_vertex_mixed", 64, 3)
     p = case(spec)[0]
     first = run_entry(e, p, monkeypatch, history=bool(e["diag"]))
-    from fixture_batch import hetero_batch_from_problems
-    from flowsim_amd import _abi as A
     mids = []
     for name in ("storage_curve_poly_losses", "storage_curve_power_trap", "storage_curve_closed"):
         fx, meta = O.load_fixture(os.path.join(GOLDEN, name + ".npz"))

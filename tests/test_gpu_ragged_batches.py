@@ -13,21 +13,21 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from fixture_batch import batch_from_problems, boundary_spec, hetero_batch_from_problems, merge_specs
+from flowsim_amd import _abi as A
+from kernel_harness import rel_err
+from oracle import c_oracle
 from oracle import preissmann_oracle as O
+from synth import rect_problem
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-8
-
-
-def rel(a, b, floor):
-    return float(np.max(np.abs(a - b) / np.maximum(np.abs(b), floor)))
 
 
 def _uniform_batch(probs, mode, N, node_counts=None, pad_value=-777.0, nodes_after_state=False):
     """one RECT / TRAP_UNIFORM batch of prismatic problems with (optionally) ragged node counts; the state rows are padded with a
     sentinel no kernel may ever look at"""
     from flowsim_amd import BoundarySpec, PreissmannBatch
-    from flowsim_amd import _abi as A
     B, p0 = len(probs), probs[0]
     b = PreissmannBatch(B, N, p0.nt, section_mode=mode, history=True)
     b.set_scheme(p0.theta, p0.dt, p0.dx, p0.tol, p0.max_iter)
@@ -46,7 +46,6 @@ def _uniform_batch(probs, mode, N, node_counts=None, pad_value=-777.0, nodes_aft
 
 @pytest.mark.parametrize("mode", ["rect_uniform", "trap_uniform"])
 def test_derived_fields_of_a_ragged_uniform_batch(mode):
-    from synth import rect_problem
     lengths = [37, 90, 128, 61]
     probs = []
     for s, n in enumerate(lengths):
@@ -78,7 +77,6 @@ def test_derived_fields_of_a_ragged_uniform_batch(mode):
 
 @pytest.mark.parametrize("nodes_after_state", [False, True])
 def test_level0_hydrograph_row_holds_each_reachs_last_node(nodes_after_state):
-    from synth import rect_problem
     lengths = [20, 64, 33]
     probs = [rect_problem(n, seed=800 + s, n_steps=2, steady=False) for s, n in enumerate(lengths)]
     for q in probs:                                          # a sloping initial profile: the last node differs from its neighbours
@@ -91,8 +89,6 @@ def test_level0_hydrograph_row_holds_each_reachs_last_node(nodes_after_state):
 
 
 def test_restart_with_per_reach_kinds_needs_the_storage_stage_whichever_reach_has_the_storage():
-    from fixture_batch import hetero_batch_from_problems
-    from flowsim_amd import _abi as A
     # two channels of the reference's random sweep: reach 0 ends in a fixed depth, reach 1 in a LumpedStorage (closed form)
     sweep = {i: (fx, m) for i, fx, m in O.sweep_cases(os.path.join(GOLDEN, "random_sweep.npz"))}
     p_plain, p_store = (O.problem_from_fixture(*sweep[i]) for i in (14, 11))
@@ -112,7 +108,6 @@ def test_restart_with_per_reach_kinds_needs_the_storage_stage_whichever_reach_ha
 
 
 def test_stage_tables_beyond_the_bound_fall_back_to_the_edge_walk(monkeypatch):
-    from fixture_batch import batch_from_problems
     fx, meta = O.load_fixture(os.path.join(GOLDEN, "irr_levee.npz"))
     p = O.problem_from_fixture(fx, meta)
     p.nt = 9
@@ -126,7 +121,7 @@ def test_stage_tables_beyond_the_bound_fall_back_to_the_edge_walk(monkeypatch):
             assert np.all(b.status() == 0)
             res[cap] = b.history_arrays(0, p.nt) + (b.iterations(0, p.nt),)
     for h, Q, its in res.values():
-        assert rel(h[:, 0], fx["depth"][:9], 1e-3) <= TOL and rel(Q[:, 0], fx["flow"][:9], 1.0) <= TOL
+        assert rel_err(h[:, 0], fx["depth"][:9], 1e-3) <= TOL and rel_err(Q[:, 0], fx["flow"][:9], 1.0) <= TOL
         assert np.array_equal(its[:, 0], fx["iters"][:9])
 
 
@@ -134,9 +129,6 @@ def test_a_ragged_batch_of_long_uniform_reaches_on_the_team_kernel():
     """Reaches of 4 097 ... 16 384 nodes in ONE rectangular batch (per-reach node counts): every reach a team of four workgroups
     (fs_kernel.hpp, TEAM), of which a shorter reach leaves one, two or three with nothing but identity rows - they still post,
     wait and decide with the others.  Pivoted C oracle, 1e-8, identical Newton counts; the sentinel padding is never read."""
-    from flowsim_amd import _abi as A
-    from oracle import c_oracle
-    from synth import rect_problem
     lengths = [4097, 9999, 16384, 6145, 12289]
     probs = [rect_problem(n, seed=1500 + s, n_steps=3) for s, n in enumerate(lengths)]
     with _uniform_batch(probs, "rect_uniform", max(lengths), lengths) as b:
@@ -149,7 +141,7 @@ def test_a_ragged_batch_of_long_uniform_reaches_on_the_team_kernel():
         hyd = b.hydrographs(0, 4)
     for r, (n, q) in enumerate(zip(lengths, probs)):
         ref = c_oracle.run(q)
-        assert rel(h[:, r, :n], ref["depth"], 1e-3) <= TOL and rel(Q[:, r, :n], ref["flow"], 1.0) <= TOL, n
+        assert rel_err(h[:, r, :n], ref["depth"], 1e-3) <= TOL and rel_err(Q[:, r, :n], ref["flow"], 1.0) <= TOL, n
         assert np.array_equal(its[:, r], ref["iters"]), n
         assert np.array_equal(hyd[:, 2, r], h[:, r, n - 1]) and np.array_equal(hyd[:, 3, r], Q[:, r, n - 1])
 
@@ -159,9 +151,7 @@ def test_team_kernel_is_deterministic_and_chunk_invariant_at_size():
     chip): two runs give the same bits, stepping level by level gives the same bits as one launch, every reach converges with the
     counts of the first run, and three of the reaches agree with the pivoted C oracle."""
     from flowsim_amd import BoundarySpec, PreissmannBatch
-    from flowsim_amd import _abi as A
     from flowsim_amd.synthetic import c3_reach_parameters, inflow_table, normal_depth_rect
-    from oracle import c_oracle
     B, N, K = 1024, 16384, 4
     b_, n_, S0, Qb = c3_reach_parameters(0, B); hn = normal_depth_rect(b_, n_, S0, Qb); L = (N - 1) * 250.0
 
@@ -189,8 +179,8 @@ def test_team_kernel_is_deterministic_and_chunk_invariant_at_size():
                       ds=O.BC("normal_depth", bed_level=0.0, bed_slope=float(S0[r])), theta=0.6, dt=600.0, dx=250.0, nt=K + 1, tol=1e-6)
         ref = c_oracle.run(p)
         assert np.array_equal(one[1][:, r], ref["iters"])
-        assert rel(one[0][:, 2, r], ref["depth"][:, -1], 1e-3) <= TOL and rel(one[0][:, 3, r], ref["flow"][:, -1], 1.0) <= TOL
-        assert rel(one[2][0][r], ref["depth"][-1], 1e-3) <= TOL and rel(one[2][1][r], ref["flow"][-1], 1.0) <= TOL
+        assert rel_err(one[0][:, 2, r], ref["depth"][:, -1], 1e-3) <= TOL and rel_err(one[0][:, 3, r], ref["flow"][:, -1], 1.0) <= TOL
+        assert rel_err(one[2][0][r], ref["depth"][-1], 1e-3) <= TOL and rel_err(one[2][1][r], ref["flow"][-1], 1.0) <= TOL
 
 
 def test_one_general_reservoir_per_reach():
@@ -199,9 +189,7 @@ def test_one_general_reservoir_per_reach():
     area curve + power outflow curve + losses on a trapezoid, a closed reservoir - as ONE batch, every reach its own channel table and its own
     reservoir (scalars, area curve, outflow curve, losses); brentq in the reference, Brent in the kernel.  Each against its fixture: 1e-8,
     identical Newton counts, the reservoir stages included."""
-    from fixture_batch import boundary_spec, merge_specs
     from flowsim_amd import PreissmannBatch
-    from flowsim_amd import _abi as A
     names = ("storage_curve_poly_losses", "storage_curve_power_trap", "storage_curve_closed")
     fxs = [O.load_fixture(os.path.join(GOLDEN, n + ".npz")) for n in names]
     probs = [O.problem_from_fixture(fx, meta) for fx, meta in fxs]
@@ -221,10 +209,10 @@ def test_one_general_reservoir_per_reach():
         its = b.iterations(0, p0.nt)
         stages = b.storage_stages(0, p0.nt)
     for r, ((fx, meta), p) in enumerate(zip(fxs, probs)):
-        assert rel(h[:, r], fx["depth"], 1e-3) <= TOL and rel(Q[:, r], fx["flow"], 1.0) <= TOL, names[r]
+        assert rel_err(h[:, r], fx["depth"], 1e-3) <= TOL and rel_err(Q[:, r], fx["flow"], 1.0) <= TOL, names[r]
         assert np.array_equal(its[:, r], fx["iters"]), names[r]
         if "storage_stage" in fx.files:
-            assert rel(stages[1:, r], fx["storage_stage"][:, 1], 1e-3) <= TOL, names[r]
+            assert rel_err(stages[1:, r], fx["storage_stage"][:, 1], 1e-3) <= TOL, names[r]
 
 
 def test_general_reservoirs_behind_some_reaches_of_a_batch():
@@ -234,8 +222,6 @@ def test_general_reservoirs_behind_some_reaches_of_a_batch():
     cases/akbari_firoozi (C2); boundary kinds that differ at both ends, 17 ... 41 nodes, seven (theta, dt, dx) triples, two tolerances
     (every reach its own: fs_batch_set_reach_tolerance), 21 ... 49 levels.  Each reach against its fixture: 1e-8, identical Newton
     counts (C1's 13 iterations of the first level among them), reservoir stages."""
-    from fixture_batch import boundary_spec, hetero_batch_from_problems
-    from flowsim_amd import _abi as A
     names = ("storage_curve_poly_losses", "bc_trap_poly", "storage_curve_closed", "bc_compound_normal", "bc_stage_fixed",
              "storage_curve_power_trap", "bc_us_fixed_ds_flow", "bc_us_normal_ds_stage", "bc_us_rating_ds_stage", "storage_curve_poly_losses",
              "example", "akbari")        # BASELINE configs C1 and C2: tolerance 1e-4 next to the others' 1e-6 (fs_batch_set_reach_tolerance)
@@ -261,16 +247,15 @@ def test_general_reservoirs_behind_some_reaches_of_a_batch():
         assert e["boundary_class"] == -1
     for r, ((fx, meta), p) in enumerate(zip(fxs, probs)):
         assert st[r] == 0 or p.nt < L, (names[r], st[r])
-        assert rel(h[:p.nt, r, :p.N], fx["depth"], 1e-3) <= TOL and rel(Q[:p.nt, r, :p.N], fx["flow"], 1.0) <= TOL, names[r]
+        assert rel_err(h[:p.nt, r, :p.N], fx["depth"], 1e-3) <= TOL and rel_err(Q[:p.nt, r, :p.N], fx["flow"], 1.0) <= TOL, names[r]
         assert np.array_equal(its[:p.nt, r], fx["iters"]), names[r]
         if "storage_stage" in fx.files:
-            assert rel(stages[1:p.nt, r], fx["storage_stage"][:, 1], 1e-3) <= TOL, names[r]
+            assert rel_err(stages[1:p.nt, r], fx["storage_stage"][:, 1], 1e-3) <= TOL, names[r]
 
 
 def test_per_reach_kinds_are_checked_reach_by_reach():
     """fs_batch_set_bc_per_reach(_wide): what the reference raises per Boundary object (boundary.py:33, :83-87) comes back per reach"""
     from flowsim_amd import BoundarySpec, PreissmannBatch
-    from flowsim_amd import _abi as A
     E = A.FlowsimError
     nd = BoundarySpec(A.BC_NORMAL_DEPTH, dict(bed_slope=1e-3, bed_level=0.0))
     flow = BoundarySpec(A.BC_FLOW_HYDROGRAPH, {}, np.full(4, 10.0))
@@ -306,8 +291,6 @@ def test_a_team_that_misses_a_member_gives_the_reach_up_instead_of_spinning_on(m
     at 8 192 nodes) waits for a member that never starts.  After about eight seconds of polling the waiting member ends its reach with
     FS_TEAM_STALL; the other reaches complete as if nothing had happened, the launch returns, and the next launch on the handle works."""
     import time
-    from flowsim_amd import _abi as A
-    from synth import rect_problem
     probs = [rect_problem(8192, seed=1700 + s, n_steps=2) for s in range(4)]
     with _uniform_batch(probs, "rect_uniform", 8192) as good:
         good.step(2)

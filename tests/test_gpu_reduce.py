@@ -14,6 +14,8 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+import failure_recipes as FR
+from fixture_batch import batch_from_problems
 from flowsim_amd import _abi as A
 from oracle import preissmann_oracle as O
 
@@ -53,7 +55,6 @@ _open = []
 @functools.lru_cache(maxsize=None)
 def run(case, B, dtype):
     """(batch, hydrographs [NT, 4, B], status [B]) of a batch stepped to level NT - 1; the batch stays open for the module"""
-    from fixture_batch import batch_from_problems
     b = batch_from_problems(members(case, B, dtype), mode="auto", dtype=dtype, history=False)
     _open.append(b)
     b.step(NT - 1)
@@ -205,8 +206,6 @@ def test_bands(case, B, dtype):
 
 
 def test_one_failing_member_between_good_ones():
-    import failure_recipes as FR
-    from fixture_batch import batch_from_problems
     good = members("akbari", 4, "f64")[:3]
     assert FR.K_STAR == 2
     bad = FR.edited(good[1], FR.K_STAR, np.nan)          # NaN in the target hydrograph at level 2

@@ -26,17 +26,19 @@ import functools
 import numpy as np
 import pytest
 
+from entry_recipes import fixture_problem, prismatic_problem
 import failure_recipes as FR
+from flowsim_amd import _abi as A
 import iterate_recipes as IR
+from kernel_harness import FIELDS, TOL, TOL_F32, assert_same_bits, batch_for_entry, rel_err, snapshot
 from oracle import preissmann_oracle as O
-from test_gpu_instantiations import TOL, TOL_F32, fixture_problem, prismatic_problem, rel_err
+from synth import rect_problem
 
 LEVELS = 3
 FS_NAN, FS_MAX_ITER = 2, 1
 
 
 def _entry(name):
-    from flowsim_amd import _abi as A
     nd = 2 + A.BC_NORMAL_DEPTH
     rect = dict(section_mode=A.SEC_RECT_UNIFORM, boundary_class=nd, long_reach=0, team=0)
     if name == "full-16x4":
@@ -60,8 +62,6 @@ NODES = {"full-16x4": 4096, "ragged-1025": 1025, "ragged-3073": 3073, "full-16x1
 
 def _base(name):
     """(entry, unperturbed problem of LEVELS levels, section mode of the batch)"""
-    from flowsim_amd import _abi as A
-    from synth import rect_problem
     e = _entry(name)
     if name == "trap-8x1":
         downstream = {A.BC_NORMAL_DEPTH: "normal", A.BC_RATING_POWER: "power", A.BC_RATING_BLEND: "blend"}[e["boundary_class"] - 2]
@@ -95,23 +95,8 @@ def _case(name):
     return dict(e=e, probs=probs, mode=mode, full=full, first=first)
 
 
-def _batch(probs, e, mode, **kw):
-    from fixture_batch import batch_from_problems
-    kw.setdefault("history", bool(e["diag"]))
-    return batch_from_problems(probs, mode=mode, dtype="f32" if IR.f32_of(e) else "f64", **kw)
-
-
 def _snap(b, nt):
-    out = dict(status=b.status().copy(), iters=b.iterations(0, nt), hyd=b.hydrographs(0, nt), state=b.state(), guess=b.guess())
-    if b.history:
-        out["hist"] = b.history_arrays(0, nt)
-    return out
-
-
-def _same(a, b, what):
-    for k in a:
-        x, y = (a[k], b[k]) if isinstance(a[k], tuple) else ((a[k],), (b[k],))
-        assert all(np.array_equal(u, v, equal_nan=True) for u, v in zip(x, y)), (what, k)
+    return snapshot(b, nt, fields=FIELDS + ("guess",))
 
 
 def _tol(e):
@@ -142,7 +127,7 @@ def test_every_level_against_the_oracle(name, monkeypatch):
     c = _case(name)
     e, probs, tol = c["e"], c["probs"], _tol(c["e"])
     monkeypatch.setenv("FS_KERNEL_INDEX", str(e["index"]))
-    with _batch(probs, e, c["mode"]) as b:
+    with batch_for_entry(probs, e, c["mode"]) as b:
         b.step(LEVELS)
         assert b.kernel_index() == e["index"]
         s = _snap(b, LEVELS + 1)
@@ -170,7 +155,7 @@ def test_the_first_iterate_against_the_oracle(name, monkeypatch):
     e, probs, tol = c["e"], c["probs"], _tol(c["e"])
     p0 = probs[0]
     monkeypatch.setenv("FS_KERNEL_INDEX", str(e["index"]))
-    with _batch(probs, e, c["mode"]) as b:
+    with batch_for_entry(probs, e, c["mode"]) as b:
         b.set_scheme(p0.theta, p0.dt, p0.dx, IR.ITER_TOL, 1)
         b.step(1)
         assert b.kernel_index() == e["index"]
@@ -190,24 +175,24 @@ def test_one_launch_is_three_launches_and_a_restart_continues(name, monkeypatch)
     c = _case(name)
     e, probs, nt = c["e"], c["probs"], LEVELS + 1
     monkeypatch.setenv("FS_KERNEL_INDEX", str(e["index"]))
-    with _batch(probs, e, c["mode"]) as b:
+    with batch_for_entry(probs, e, c["mode"]) as b:
         b.step(LEVELS)
         one = _snap(b, nt)
-    with _batch(probs, e, c["mode"]) as b:
+    with batch_for_entry(probs, e, c["mode"]) as b:
         b.step(1)
         state1, guess1 = b.state(), b.guess()
         b.step(1); b.step(1)
         assert b.kernel_index() == e["index"]
         three = _snap(b, nt)
-    _same(one, three, "one launch of three levels against three launches of one")
+    assert_same_bits(one, three, what="one launch of three levels against three launches of one")
     assert np.all(one["status"] == 0)
-    with _batch(probs, e, c["mode"]) as b:           # a fresh batch continues from level 1 of the split run
+    with batch_for_entry(probs, e, c["mode"]) as b:           # a fresh batch continues from level 1 of the split run
         b.restart(1, *state1, *guess1)
         b.step(LEVELS - 1)
         assert b.kernel_index() == e["index"]
         again = dict(status=b.status().copy(), iters=b.iterations(2, LEVELS - 1), hyd=b.hydrographs(2, LEVELS - 1), state=b.state(), guess=b.guess())
     want = dict(status=one["status"], iters=one["iters"][2:], hyd=one["hyd"][2:], state=one["state"], guess=one["guess"])
-    _same(want, again, "restart from level 1")
+    assert_same_bits(want, again, what="restart from level 1")
 
 
 @pytest.mark.gpu
@@ -216,18 +201,18 @@ def test_a_batch_of_three_is_each_reach_alone(name, monkeypatch):
     c = _case(name)
     e, probs, nt = c["e"], c["probs"], LEVELS + 1
     monkeypatch.setenv("FS_KERNEL_INDEX", str(e["index"]))
-    with _batch(probs, e, c["mode"]) as b:
+    with batch_for_entry(probs, e, c["mode"]) as b:
         b.step(LEVELS)
         together = _snap(b, nt)
     for r, p in enumerate(probs):
-        with _batch([p], e, c["mode"]) as b:
+        with batch_for_entry([p], e, c["mode"]) as b:
             b.step(LEVELS)
             assert b.kernel_index() == e["index"]
             alone = _snap(b, nt)
         # reach r of the batch: status [B]; iters [levels, B]; hyd [levels, 4, B]; state, guess ([B, N], [B, N]); hist ([levels, B, N], ...)
         pick = {k: v[r:r + 1] if k == "status" else v[..., r:r + 1] if k in ("iters", "hyd") else
                 tuple(a[:, r:r + 1] if k == "hist" else a[r:r + 1] for a in v) for k, v in together.items()}
-        _same(pick, alone, f"reach {r} alone")
+        assert_same_bits(pick, alone, what=f"reach {r} alone")
 
 
 # ---- the normal-depth row: the usual case, a boundary bed level of its own (the retained block), an adverse slope ----
@@ -275,7 +260,7 @@ def test_the_normal_depth_row_against_the_oracle(name, case, monkeypatch):
     p0 = probs[0]
     monkeypatch.setenv("FS_KERNEL_INDEX", str(e["index"]))
     for m in ROW_ITERATES[case]:
-        with _batch(probs, e, c["mode"]) as b:
+        with batch_for_entry(probs, e, c["mode"]) as b:
             b.set_scheme(p0.theta, p0.dt, p0.dx, IR.ITER_TOL, m)
             b.step(1)
             assert b.kernel_index() == e["index"]
@@ -300,11 +285,11 @@ def test_a_nan_target_ends_in_fs_nan(name, monkeypatch):
     ref = FR.oracle_run(bad[0])
     assert ref["status"] == FS_NAN and ref["fail_level"] == K
     monkeypatch.setenv("FS_KERNEL_INDEX", str(e["index"]))
-    with _batch(bad, e, c["mode"]) as b:
+    with batch_for_entry(bad, e, c["mode"]) as b:
         b.step(LEVELS)
         assert b.kernel_index() == e["index"]
         s = _snap(b, LEVELS + 1)
-    with _batch(c["probs"], e, c["mode"]) as b:
+    with batch_for_entry(c["probs"], e, c["mode"]) as b:
         b.step(LEVELS)
         clean = _snap(b, LEVELS + 1)
     assert list(s["status"]) == [FS_NAN, 0, 0], s["status"]

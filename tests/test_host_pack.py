@@ -21,40 +21,20 @@ import json
 import os
 import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN
 from flowsim_amd import _abi as A
 from oracle import preissmann_oracle as O
 
+from host_pack_driver import CSRC, build_driver, line, run_driver
 import poly_edges as PE
 
-CSRC = os.path.join(ROOT, "flow-sim_amd", "csrc")
-DRIVER = os.path.join(ROOT, "tests", "host_pack", "host_pack_driver.cpp")
 RECORD = os.path.join(GOLDEN, "host_pack", "record.json")
 NFIXED, N_CURVE, SURFACE_AREA = len(A.SC_NAMES), A.SC_NAMES.index("n_curve"), A.SC_NAMES.index("surface_area")
 DEFAULT_CAP = 8 << 30
-
-
-def build_driver(out_dir, include_dirs):
-    exe = os.path.join(str(out_dir), "host_pack_driver")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-           "-fno-omit-frame-pointer"]
-    for d in include_dirs:
-        cmd += ["-I", str(d)]
-    r = subprocess.run(cmd + ["-o", exe, DRIVER], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
-def run_driver(exe, args):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe, *args], capture_output=True, text=True, env=env, timeout=600)
-    assert r.returncode == 0 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
-    return r.stdout
 
 
 def sha(a):
@@ -181,10 +161,6 @@ def curve_column(variant, rows):
 
 CURVES = [(-1, True), (0, True), (0, False), (1, True), (2, True), (2, False), (3, True), (3, False)]
 NEED = [0, 1, 1, 2, 4, 5, 10, 5]
-
-
-def line(what, *fields):
-    return what + " " + " ".join(float(v).hex() if isinstance(v, (float, np.floating)) else str(int(v)) for v in fields)
 
 
 def check_lines():

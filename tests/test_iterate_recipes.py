@@ -10,7 +10,7 @@ import iterate_recipes as IR
 from oracle import preissmann_oracle as O
 
 TABLE = IR.TABLE
-IDS = [IR._id(e) for e in TABLE]
+IDS = [IR.entry_id(e) for e in TABLE]
 BAR = 1e-8                 # the fp64 parity bar of the suite
 EPS = 1e-4                 # the relative error of a Jacobian ingredient that must show
 SENSITIVITY = 50 * BAR     # ... by at least this much in x1
@@ -93,7 +93,7 @@ def test_exit_state_and_movement(e):
         hmin = min(float(np.min(h)) for h, _ in vectors)
         h1 = IR.unknowns(refs[(1, 1)])[0]
         frac = float(np.mean(np.abs(h1 - p.h0) / p.h0 > 1e-4))
-        print(f"{IR._id(e)} reach {r}: min depth {hmin:.3f}, max Froude {fr:.3f}, nodes moved by the first update {100 * frac:.2f} %, "
+        print(f"{IR.entry_id(e)} reach {r}: min depth {hmin:.3f}, max Froude {fr:.3f}, nodes moved by the first update {100 * frac:.2f} %, "
               f"level-1 counts ahead of the level-2 iterate {lvl2['iters'][1]}")
         assert hmin > 0 and fr < FROUDE_MAX
         assert frac >= 0.99
@@ -129,7 +129,7 @@ def test_the_first_iterate_sees_every_jacobian_ingredient(e, monkeypatch):
             with monkeypatch.context() as m:
                 m.setattr(O, "node_terms", _scaled_terms(key))
                 got = moved(first_iterate(p), clean)
-            print(f"{IR._id(e)} reach {r}: {key} (1 + {EPS:g}) moves x1 by {got:.2e}")
+            print(f"{IR.entry_id(e)} reach {r}: {key} (1 + {EPS:g}) moves x1 by {got:.2e}")
             assert got >= SENSITIVITY, (key, got)
         rows = {"us": O.boundary_eval(p.us, O._one(p.geo, 0), p.h0[0], p.Q0[0], 1, p.dt),
                 "ds": O.boundary_eval(p.ds, O._one(p.geo, p.N - 1), p.h0[-1], p.Q0[-1], 1, p.dt, Q_old=p.Q0[-1], store={"Y_prev": None})}
@@ -140,7 +140,7 @@ def test_the_first_iterate_sees_every_jacobian_ingredient(e, monkeypatch):
                 with monkeypatch.context() as m:
                     m.setattr(O, "boundary_eval", _scaled_row(side, slot))
                     got = moved(first_iterate(p), clean)
-                print(f"{IR._id(e)} reach {r}: {side} {getattr(p, side).kind} {name} (1 + {EPS:g}) moves x1 by {got:.2e}")
+                print(f"{IR.entry_id(e)} reach {r}: {side} {getattr(p, side).kind} {name} (1 + {EPS:g}) moves x1 by {got:.2e}")
                 assert got >= SENSITIVITY, (side, name, got)
 
 
@@ -158,5 +158,5 @@ def test_the_reference_iterate_is_stable_to_rounding(e, monkeypatch):
         with monkeypatch.context() as m:
             m.setattr(O, "assemble", noisy)
             worst = max(moved(first_iterate(p), clean) for _ in range(DRAWS))
-        print(f"{IR._id(e)} reach {r}: noise of {NOISE:.1e} on R and the Jacobian moves x1 by {worst:.2e}")
+        print(f"{IR.entry_id(e)} reach {r}: noise of {NOISE:.1e} on R and the Jacobian moves x1 by {worst:.2e}")
         assert worst < STABILITY, worst

@@ -26,18 +26,19 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from fixture_batch import batch_from_problems, is_rect_uniform
+from flowsim_amd import _abi as A
+from kernel_harness import rel_err
+from oracle import c_oracle as CO
 from oracle import preissmann_oracle as O
 from oracle.gen_random_sweep import build_from_recipe
+from random_cases import random_problem
 
 PATH = os.path.join(GOLDEN, "near_critical.npz")
 CASES = list(O.sweep_cases(PATH))
 TOL = 1e-8
 ILL = 4                      # FS_ILL_CONDITIONED
 COND_LIMIT = 1e12            # the reference's own threshold (rcond < 1e-12, preissmann.py:142)
-
-
-def rel_err(got, want, floor):
-    return float(np.max(np.abs(got - want) / np.maximum(np.abs(want), floor)))
 
 
 def label(c):
@@ -62,7 +63,6 @@ def test_the_fixture_is_what_it_says():
 
 @pytest.mark.parametrize("case", CASES, ids=[label(c) for c in CASES])
 def test_oracles_reproduce_the_reference_up_to_its_own_conditioning_limit(case):
-    from oracle import c_oracle as CO
     _, fx, m = case
     p = O.problem_from_fixture(fx, m)
     for run in (O.newton_run, CO.run):
@@ -91,7 +91,6 @@ _seen = {}
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", CASES, ids=[label(c) for c in CASES])
 def test_kernel_reproduces_the_reference_or_says_that_it_cannot(case):
-    from fixture_batch import batch_from_problems, is_rect_uniform
     i, fx, m = case
     p = O.problem_from_fixture(fx, m)
     modes = ["table"] + (["rect_uniform"] if is_rect_uniform(p) else [])
@@ -164,11 +163,8 @@ def test_a_batch_without_history_watches_its_conditioning_by_default():
     supercritical scan (profiles/round2/supercritical_scan.txt: seeds 5932, 6685, 6373, 5684 - Froude 1.08 ... 1.48, 1.5e-4 ... 8e-3 away from
     the pivoted oracle) come back flagged from such a batch.  (monitor=False - what bench.py asks for - selects the kernels compiled without
     diagnostics where the batch's shape has one.)"""
-    import test_gpu_random_cases as T
-    from fixture_batch import batch_from_problems
-    from flowsim_amd import _abi as A
     for seed in (5932, 6685, 6373, 5684):
-        p, info = T.random_problem(seed)
+        p, info = random_problem(seed)
         mode = "rect_uniform" if (not info["trapezoid"] and info["ds"] != "blend") else "table"
         with batch_from_problems([p], mode=mode, history=False, monitor=True) as b:       # (the helper's default follows `history`; PreissmannBatch's is True)
             b.step(p.nt - 1)

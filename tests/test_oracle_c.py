@@ -7,16 +7,14 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, fixture_paths
+from kernel_harness import rel_err
 from oracle import c_oracle as CO
 from oracle import preissmann_oracle as O
+from synth import rect_problem
 
 # the C restatement covers the trapezoid family with closed-form boundaries; polyline channels and the
 # brentq-based general LumpedStorage are pinned by the numpy oracle (test_oracle_irregular.py, test_oracle_golden.py)
 FIXTURES = [p for p in fixture_paths() if not os.path.basename(p).startswith(("irr_", "storage_curve_"))]
-
-
-def rel_err(got, want, floor):
-    return float(np.max(np.abs(got - want) / np.maximum(np.abs(want), floor)))
 
 
 @pytest.mark.parametrize("path", FIXTURES, ids=[os.path.basename(p)[:-4] for p in FIXTURES])
@@ -33,7 +31,6 @@ def test_c_oracle_matches_reference_fixtures(path):
 
 
 def test_c_and_numpy_oracles_agree_on_fresh_inputs():
-    from synth import rect_problem
     for seed in (21, 22):
         p = rect_problem(700, seed=seed, n_steps=5)
         a, b = O.newton_run(p), CO.run(p)

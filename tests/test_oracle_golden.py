@@ -12,14 +12,11 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, fixture_paths
+from kernel_harness import rel_err
 from oracle import preissmann_oracle as O
 
 FIXTURES = fixture_paths()
 TOL = 1e-8
-
-
-def rel_err(got, want, floor):
-    return float(np.max(np.abs(got - want) / np.maximum(np.abs(want), floor)))
 
 
 def members(meta):

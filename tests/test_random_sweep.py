@@ -20,6 +20,9 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from fixture_batch import batch_from_problems, hetero_batch_from_problems, is_rect_uniform
+from kernel_harness import rel_err
+from oracle import c_oracle as CO
 from oracle import preissmann_oracle as O
 from oracle.gen_random_sweep import build_from_recipe
 
@@ -27,10 +30,6 @@ PATH = os.environ.get("FS_SWEEP_FIXTURE", os.path.join(GOLDEN, "random_sweep.npz
 SOAK = "FS_SWEEP_FIXTURE" in os.environ
 CASES = list(O.sweep_cases(PATH))
 TOL = 1e-8
-
-
-def rel_err(got, want, floor):
-    return float(np.max(np.abs(got - want) / np.maximum(np.abs(want), floor)))
 
 
 def label(c):
@@ -75,7 +74,6 @@ def test_oracles_reproduce_the_reference(case):
     assert r["status"] == 0
     compare(r["depth"], r["flow"], r["iters"], fx, m)
     if m["family"] != "polyline" and m["ds_kind"] != "storage_curve":        # the C restatement: trapezoid family, closed-form boundaries
-        from oracle import c_oracle as CO
         rc = CO.run(p)
         assert rc["status"] == 0
         compare(rc["depth"], rc["flow"], rc["iters"], fx, m)
@@ -84,7 +82,6 @@ def test_oracles_reproduce_the_reference(case):
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", CASES, ids=[label(c) for c in CASES])
 def test_kernel_reproduces_the_reference(case):
-    from fixture_batch import batch_from_problems, is_rect_uniform
     _, fx, m = case
     p = O.problem_from_fixture(fx, m)
     # (the general storage row is compiled into the table / polyline kernels only: fs_batch_step says so otherwise)
@@ -111,7 +108,6 @@ def test_kernel_reproduces_the_trapezoid_family_cases_as_three_heterogeneous_bat
     node table, node count (2 ... 257), theta, time and space step, boundary kinds and number of levels - what the reference
     builds per Channel / Solver object (channel.py:213-241, solver.py:34-38,53-55), here as per-reach tables of one launch
     (geometry [param][node][reach])."""
-    from fixture_batch import hetero_batch_from_problems
     fam = [(i, fx, m) for i, fx, m in CASES if m["family"] != "polyline" and m["ds_kind"] != "storage_curve"]
     assert len(fam) >= 48 or SOAK
     groups = {}
