@@ -26,6 +26,7 @@
 #include "fs_forcing.hpp"
 #include "fs_host_pack.hpp"
 #include "fs_init_state.hpp"
+#include "fs_member_geo.hpp"
 #include "fs_reduce.hpp"
 
 // ROCTx ranges around the phases a system trace should show (rocprofv3 --marker-trace): uploads, downloads, the step launch,
@@ -44,9 +45,11 @@ struct TraceRange {
 FS_ACTIVE_LIST(FS_DECLARE)
 #else
 // an experiment build is this translation unit alone, with a few step kernels: it has no initial-condition kernels (fs_part_init.hip)
-// no post-processing kernels (fs_part_reduce.hip) and no forcing kernels (fs_part_forcing.hip), and fs_batch_init_state,
-// fs_batch_summarize, fs_batch_set_bc_sampled ... say so
+// no post-processing kernels (fs_part_reduce.hip), no forcing kernels (fs_part_forcing.hip) and no geometry kernels
+// (fs_part_geometry.hip), and fs_batch_init_state, fs_batch_summarize, fs_batch_set_bc_sampled ... say so
 namespace fs {
+bool launch_member_sections(const MemberGeoArgs &, hipStream_t) { return false; }
+bool launch_member_tables(const MemberGeoArgs &, hipStream_t) { return false; }
 bool launch_sample_target(const SampleArgs<double> &, hipStream_t) { return false; }
 bool launch_sample_target(const SampleArgs<float> &, hipStream_t) { return false; }
 bool launch_route_pool(const PoolArgs<double> &, hipStream_t) { return false; }
@@ -219,6 +222,8 @@ struct fs_batch : Timeline {
   fs::DeviceBuffer poly_x, poly_z, poly_lim, poly_n;     // poly_n: int32
   fs::DeviceBuffer poly_tz;             // stage tables of the polylines (fs_poly.hpp)
   int poly_K = 0;
+  int poly_P = 0;                       // max_pts of the polylines on the device
+  fs::DeviceBuffer member_in[9];        // double / int32: fs_batch_set_geometry_irregular_members' shared channel (x, z, limits, n_pts, table) and transforms (dz_left, dz_main, dz_right, n_scale)
   size_t geo_reach_stride = 0, poly_reach_stride = 0;     // per-reach geometry (elements between the tables of two reaches), 0: shared
   fs::DeviceBuffer reach_nodes;         // int32 [B] per-reach node counts (heterogeneous batch) or empty
   std::vector<int32_t> reach_nodes_host;      // its host copy (empty: every reach has n_nodes): where a reach's last node is
@@ -799,6 +804,7 @@ static int set_irregular(fs_batch *b, const double *table, const int32_t *n_pts,
                   "device (" + g_err + "); lower FS_POLY_TABLE_MAX_BYTES to fall back to the edge walk");
     b->poly_K = (int)P;
   }
+  b->poly_P = (int)P;
   if (upload(b, b->geo_table, plan.tabs.data(), plan.tabs.size()) || upload(b, b->poly_x, plan.xt.data(), plan.xt.size()) ||
       upload(b, b->poly_z, plan.zt.data(), plan.zt.size()) || upload(b, b->poly_lim, plan.lim.data(), plan.lim.size())) return -1;
   HIP_TRY(b->poly_n.ensure(n_sets * N * 4));
@@ -822,6 +828,71 @@ int fs_batch_set_geometry_irregular_per_reach(fs_batch *b, const double *tables,
   if (!b) return fail("fs_batch_set_geometry_irregular: null argument");
   if (b->d.n_reaches == 1) return set_irregular(b, tables, n_pts, max_pts, x, z, limits, n_main_override, 1);
   return set_irregular(b, tables, n_pts, max_pts, x, z, limits, n_main_override, (size_t)b->d.n_reaches);
+}
+
+// One surveyed channel and per-member transforms: the members' polylines, tables and stage tables are built on the device
+// (fs_member_geo.hpp); only the shared channel and the transforms cross the bus.
+int fs_batch_set_geometry_irregular_members(fs_batch *b, const double *table, const int32_t *n_pts, int32_t max_pts, const double *x,
+                                            const double *z, const double *limits, const double *dz_left, const double *dz_main,
+                                            const double *dz_right, const double *n_scale) {
+  if (!b || !table || !n_pts || !x || !z || !limits) return fail("fs_batch_set_geometry_irregular_members: null argument");
+  if (b->d.section_mode != FS_SEC_IRREGULAR) return fail("fs_batch_set_geometry_irregular_members: batch was created with another section_mode");
+  if (max_pts < 2) return fail("fs_batch_set_geometry_irregular: max_pts must be >= 2");
+  FS_ON_DEVICE(b);
+  const size_t B = b->d.n_reaches, N = b->d.n_nodes, P = max_pts;
+  if (const char *err = fs::check_member_transforms(n_pts, dz_left, dz_main, dz_right, n_scale, B, N)) return fail(err);
+  // the shared channel through the validation and the transposition of the other irregular setters, without the tables
+  std::vector<double> xt(P * N), zt(P * N), lim(2 * N);
+  if (const char *err = fs::pack_polylines(table, n_pts, max_pts, x, z, limits, N, xt.data(), zt.data(), lim.data(), nullptr)) return fail(err);
+  const std::vector<double> ext = fs::extend_table(table, N);
+  fs::PolyTableLimits how;
+  if (const char *env = std::getenv("FS_POLY_TABLE_MAX_BYTES")) how.max_bytes = (size_t)std::strtoull(env, nullptr, 10);
+  how.force_walk = std::getenv("FS_POLY_WALK") != nullptr;
+  const size_t tstride = (size_t)fs::poly_table_stride(max_pts);
+  const double table_bytes = (double)B * (double)N * (double)tstride * sizeof(double);
+  const bool walk = how.force_walk || table_bytes > (double)how.max_bytes;
+  for (fs::DeviceBuffer *q : {&b->geo_table, &b->poly_x, &b->poly_z, &b->poly_lim, &b->poly_tz, &b->poly_n}) q->reset();
+  b->poly_K = 0; b->poly_P = 0; b->have_geo = false;
+  if (!walk && b->poly_tz.ensure(B * N * tstride * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail("fs_batch_set_geometry_irregular_members: " + std::to_string((size_t)(table_bytes / (1 << 20))) + " MiB of stage tables do not "
+                "fit the device; lower FS_POLY_TABLE_MAX_BYTES to fall back to the edge walk");
+  }
+  HIP_TRY(b->geo_table.ensure(B * fs::FS_GEOX_NROWS * N * sizeof(double)));
+  HIP_TRY(b->poly_x.ensure(B * P * N * sizeof(double)));
+  HIP_TRY(b->poly_z.ensure(B * P * N * sizeof(double)));
+  HIP_TRY(b->poly_lim.ensure(B * 2 * N * sizeof(double)));
+  HIP_TRY(b->poly_n.ensure(B * N * 4));
+  fs::DeviceBuffer *in = b->member_in;
+  if (upload_f64(in[0], xt.data(), xt.size()) || upload_f64(in[1], zt.data(), zt.size()) || upload_f64(in[2], lim.data(), lim.size()) ||
+      upload_f64(in[4], ext.data(), ext.size())) return -1;
+  HIP_TRY(in[3].reserve(N * 4));
+  HIP_TRY(hipMemcpy(in[3].get(), n_pts, N * 4, hipMemcpyHostToDevice));
+  const double *opt[4] = {dz_left, dz_main, dz_right, n_scale};
+  for (int q = 0; q < 4; ++q)
+    if (opt[q] && upload_f64(in[5 + q], opt[q], q < 3 ? B * N : 3 * B)) return -1;
+  auto given = [&](int q) { return opt[q] ? in[5 + q].get<const double>() : nullptr; };
+  fs::MemberGeoArgs a{in[0].get<const double>(), in[1].get<const double>(), in[2].get<const double>(), in[3].get<const int32_t>(),
+                      in[4].get<const double>(), {given(0), given(1), given(2)}, given(3),
+                      b->poly_x.get<double>(), b->poly_z.get<double>(), b->poly_lim.get<double>(), b->poly_n.get<int32_t>(),
+                      b->geo_table.get<double>(), b->poly_tz.get<double>(), (int64_t)B, (int64_t)N, max_pts};
+  {
+    TraceRange range_("flowsim:member_geometry");
+    HIP_TRY(hipEventRecord(b->ev0, b->stream));
+    if (!fs::launch_member_sections(a, b->stream) || (!walk && !fs::launch_member_tables(a, b->stream)))
+      return fail("fs_batch_set_geometry_irregular_members: this build has no geometry kernels");
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(b->ev1, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    b->timed = true; b->launches = walk ? 1 : 2;      // fs_batch_last_step_ms: the two kernels, until the next step
+  }
+  b->poly_K = walk ? 0 : (int)P;
+  b->poly_P = (int)P;
+  b->geo_reach_stride = B > 1 ? (size_t)fs::FS_GEOX_NROWS * N : 0;
+  b->poly_reach_stride = B > 1 ? P * N : 0;
+  b->n_override.reset();      // n_scale[1] takes its place
+  b->have_geo = true;
+  return 0;
 }
 
 // One TrapezoidalSection table per reach: tables[B][FS_GEO_NPARAM][N] on the host -> [B][FS_GEOX_NROWS][N] on the device (a
@@ -1543,6 +1614,40 @@ int32_t fs_kernel_table_entry_tail(int32_t i) { return (i >= 0 && i < kNumEntrie
 int32_t fs_kernel_table_entry_team(int32_t i) { return (i >= 0 && i < kNumEntries) ? kEntries[i].key.team : -2; }
 
 int32_t fs_batch_poly_tables(fs_batch *b) { return (b && b->poly_x) ? (b->poly_K > 0 ? 1 : 0) : -1; }
+
+int fs_batch_get_stage_table(fs_batch *b, int32_t reach, int32_t node, double *out) {
+  if (!b || !out) return fail("fs_batch_get_stage_table: null argument");
+  if (!b->poly_x) return fail("fs_batch_get_stage_table: no polylines set");
+  if (b->poly_K <= 0) return fail("fs_batch_get_stage_table: this batch walks its polylines' edges and holds no stage tables (fs_batch_poly_tables)");
+  if (reach < 0 || reach >= b->d.n_reaches || node < 0 || node >= b->d.n_nodes) return fail("fs_batch_get_stage_table: reach or node out of range");
+  FS_ON_DEVICE(b);
+  const size_t N = b->d.n_nodes, P = b->poly_K, KP = fs::poly_table_bp((int)P), i = node;
+  const double *tz = b->poly_tz.get<const double>() + (b->poly_reach_stride ? (size_t)reach * N * fs::poly_table_stride((int)P) : 0);
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  HIP_TRY(hipMemcpy(out, tz + i * KP, KP * sizeof(double), hipMemcpyDeviceToHost));
+  // the node's 16-byte pairs, N pairs apart in the node-minor layout, in build_stage_table's order
+  HIP_TRY(hipMemcpy2D(out + KP, 2 * sizeof(double), tz + N * KP + 2 * i, N * 2 * sizeof(double), 2 * sizeof(double), P * (fs::FS_PT_BLOCK / 2),
+                      hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int fs_batch_get_bed_levels(fs_batch *b, double *out) {
+  if (!b || !out) return fail("fs_batch_get_bed_levels: null argument");
+  if (!b->geo_table) return fail("fs_batch_get_bed_levels: no TABLE or IRREGULAR geometry set");
+  FS_ON_DEVICE(b);
+  const size_t B = b->d.n_reaches, N = b->d.n_nodes, rows = b->geo_reach_stride ? B : 1, esz = b->esz;
+  // row Z_BED of every table (one shared by the batch, or one per reach, geo_reach_stride elements apart) in the batch's type
+  std::vector<char> raw(rows * N * esz);
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  HIP_TRY(hipMemcpy2D(raw.data(), N * esz, b->geo_table.get<const char>() + (size_t)FS_GEO_Z_BED * N * esz, (rows > 1 ? b->geo_reach_stride : N) * esz, N * esz, rows,
+                      hipMemcpyDeviceToHost));
+  for (size_t r = 0; r < B; ++r)
+    for (size_t i = 0; i < N; ++i) {
+      const size_t q = (rows > 1 ? r : 0) * N + i;
+      out[r * N + i] = esz == sizeof(double) ? reinterpret_cast<const double *>(raw.data())[q] : (double)reinterpret_cast<const float *>(raw.data())[q];
+    }
+  return 0;
+}
 
 int fs_batch_kernel_info(fs_batch *b, int32_t *cells_per_thread, int32_t *waves_per_reach, int32_t *lds_bytes,
                          int32_t *vgprs) {

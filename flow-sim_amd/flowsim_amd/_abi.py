@@ -64,6 +64,9 @@ SIGNATURES = {
     "fs_batch_set_bc": (C.c_int, [_P, C.c_int32, C.c_int32, _D, C.c_int32, C.c_int32, _D]),
     "fs_batch_set_geometry_table_per_reach": (C.c_int, [_P, _D, _D]),
     "fs_batch_set_geometry_irregular_per_reach": (C.c_int, [_P, _D, _I, C.c_int32, _D, _D, _D, _D]),
+    "fs_batch_set_geometry_irregular_members": (C.c_int, [_P, _D, _I, C.c_int32, _D, _D, _D, _D, _D, _D, _D]),
+    "fs_batch_get_stage_table": (C.c_int, [_P, C.c_int32, C.c_int32, _D]),
+    "fs_batch_get_bed_levels": (C.c_int, [_P, _D]),
     "fs_batch_set_reach_nodes": (C.c_int, [_P, _I]),
     "fs_batch_set_reach_scheme": (C.c_int, [_P, _D, _D, _D]),
     "fs_batch_set_reach_tolerance": (C.c_int, [_P, _D, _I]),

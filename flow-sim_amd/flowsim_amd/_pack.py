@@ -1,5 +1,6 @@
 """Python values -> the flat arrays the C ABI receives (include/flowsim_abi.h), without the library: numpy and the constants of _abi
-only, no arithmetic.  Every function returns C-contiguous arrays of the dtype and shape the call takes; batch.py passes them on.
+only, no arithmetic - but for member_sections, the member transform of a geometry ensemble written out in numpy (its definition, and
+the host path the device kernels replace).  Every function returns C-contiguous arrays of the dtype and shape the call takes; batch.py passes them on.
 tests/test_batch_pack.py holds them on the CPU to the arrays the setters built before these functions existed, and to what
 fs::check_bc / fs::check_bc_per_reach accept."""
 import numpy as np
@@ -76,6 +77,62 @@ def irregular_arrays(geo, B, N):
     lim = np.ascontiguousarray(geo["irr_limits"], dtype=np.float64)
     assert cnt.shape == lead + (N,) and x.shape == z.shape and x.shape[:-1] == lead + (N,) and lim.shape == lead + (N, 2)
     return geometry_table(geo, B, N, per_reach), cnt, x, z, lim, per_reach
+
+
+def member_shift(v, B, N):
+    """a dz_* of the member transform: None, or [B] (the same shift at every node) / [B, N] -> [B, N]"""
+    if v is None:
+        return None
+    v = np.asarray(v, dtype=np.float64)
+    if v.shape not in ((B,), (B, N)):
+        raise ValueError("dz_left, dz_main and dz_right must be [B] or [B, N]")
+    return np.ascontiguousarray(np.broadcast_to(v[:, None] if v.ndim == 1 else v, (B, N)))
+
+
+def member_n_scale(v, B):
+    """n_scale of the member transform: None or [3, B] (left, main, right)"""
+    if v is None:
+        return None
+    v = np.ascontiguousarray(v, dtype=np.float64)
+    if v.shape != (3, B):
+        raise ValueError("n_scale must be [3, B]: the factors of n_left, n_main, n_right")
+    return v
+
+
+def member_arrays(geo, B, N, dz_left=None, dz_main=None, dz_right=None, n_scale=None):
+    """(table, n_pts int32, x, z, limits, dz_left, dz_main, dz_right, n_scale) of fs_batch_set_geometry_irregular_members: ONE
+    channel as irregular_arrays packs it, the transforms [B, N] / [3, B] or None"""
+    tab, cnt, x, z, lim, per_reach = irregular_arrays(geo, B, N)
+    if per_reach:
+        raise ValueError("a geometry ensemble takes ONE channel: irr_npts [N], irr_x / irr_z [N, P]")
+    return (tab, cnt, x, z, lim) + tuple(member_shift(v, B, N) for v in (dz_left, dz_main, dz_right)) + (member_n_scale(n_scale, B),)
+
+
+def member_sections(geo, B, dz_left=None, dz_main=None, dz_right=None, n_scale=None):
+    """THE DEFINITION of the member transform (include/flowsim_abi.h: fs_batch_set_geometry_irregular_members), in numpy: the
+    per-reach geo dict set_geometry_irregular accepts (irr_z [B, N, P], z_bed [B, N], n_* [B, N], ...) of the B members of one
+    polyline channel.  Vertex j of node i is in the left strip where x_j < left limit, in the right one where x_j > right limit, in
+    the main channel otherwise; z'_j = z_j + dz_strip(j)[r, i]; n' = n * n_scale[0..2][r]; z_bed' = min_j z'_j; slots beyond a node's
+    count repeat its transformed last vertex.  The device builds the same, bit for bit; this is also the host path it replaces."""
+    cnt = np.asarray(geo["irr_npts"], dtype=np.int32)
+    N = len(cnt)
+    x, z, lim = (np.asarray(geo[k], dtype=np.float64) for k in ("irr_x", "irr_z", "irr_limits"))
+    P = x.shape[1]
+    dzl, dzm, dzr = (np.zeros((B, N)) if v is None else member_shift(v, B, N) for v in (dz_left, dz_main, dz_right))
+    ns = np.ones((3, B)) if n_scale is None else member_n_scale(n_scale, B)
+    slot = np.minimum(np.arange(P)[None, :], cnt[:, None] - 1)               # [N, P]: padding slots read the last vertex
+    xs, zs = np.take_along_axis(x, slot, 1), np.take_along_axis(z, slot, 1)
+    left, right = xs < lim[:, :1], xs > lim[:, 1:]
+    dz = np.where(left[None], dzl[:, :, None], np.where(right[None], dzr[:, :, None], dzm[:, :, None]))
+    out = {k: np.ascontiguousarray(np.broadcast_to(np.asarray(geo[k], dtype=np.float64), (B, N))) for k in A.GEO_ROWS}
+    out["irr_z"] = zs[None] + dz
+    out["irr_x"] = np.ascontiguousarray(np.broadcast_to(xs, (B, N, P)))
+    out["irr_npts"] = np.ascontiguousarray(np.broadcast_to(cnt, (B, N)))
+    out["irr_limits"] = np.ascontiguousarray(np.broadcast_to(lim, (B, N, 2)))
+    out["z_bed"] = out["irr_z"].min(axis=2)
+    for row, k in enumerate(("n_left", "n_main", "n_right")):
+        out[k] = np.asarray(geo[k], dtype=np.float64)[None, :] * ns[row][:, None]
+    return out
 
 
 # -- boundaries -----------------------------------------------------------------------------------

@@ -61,6 +61,7 @@ class PreissmannBatch:
         if not self._h:
             raise A.FlowsimError(A.last_error())
         self.history = history
+        self._max_pts = 0           # stations per polyline row of the geometry on the device (stage_table)
 
     # -- lifetime -------------------------------------------------------------------------
     def close(self):
@@ -132,6 +133,31 @@ class PreissmannBatch:
         ov = P.n_override(n_main_override, self.B)
         fn = self._lib.fs_batch_set_geometry_irregular_per_reach if per_reach else self._lib.fs_batch_set_geometry_irregular
         A.check(fn(self._h, _dptr(tab), _iptr(cnt), x.shape[-1], _dptr(x), _dptr(z), _dptr(lim), _opt(ov)), "set_geometry_irregular")
+        self._max_pts = x.shape[-1]
+
+    def set_geometry_irregular_members(self, geo: dict, dz_left=None, dz_main=None, dz_right=None, n_scale=None):
+        """A geometry ensemble of ONE polyline channel (geo as set_geometry_irregular takes a shared channel, every node a
+        polyline): member r is the channel with its left-strip, main-channel and right-strip vertices of node i lifted by
+        dz_left / dz_main / dz_right [r, i] ([B]: the same shift at every node; None: 0) and its (n_left, n_main, n_right) multiplied
+        by n_scale[0..2, r] ([3, B]; None: 1) - _pack.member_sections is the definition.  The members' polylines, bed levels and
+        stage tables are built on the device; the batch is then where set_geometry_irregular(_pack.member_sections(...)) leaves it."""
+        tab, cnt, x, z, lim, dl, dm, dr, ns = P.member_arrays(geo, self.B, self.N, dz_left, dz_main, dz_right, n_scale)
+        A.check(self._lib.fs_batch_set_geometry_irregular_members(self._h, _dptr(tab), _iptr(cnt), x.shape[-1], _dptr(x), _dptr(z), _dptr(lim),
+                                                                  _opt(dl), _opt(dm), _opt(dr), _opt(ns)), "set_geometry_irregular_members")
+        self._max_pts = x.shape[-1]
+
+    def stage_table(self, reach: int, node: int):
+        """the node's stage table as fs::build_stage_table orders it: breakpoints padded with +inf, then 32 numbers per interval
+        (FlowsimError for a batch that walks its polylines' edges)"""
+        out = np.empty(((self._max_pts + 16) & ~15) + 32 * self._max_pts)
+        A.check(self._lib.fs_batch_get_stage_table(self._h, int(reach), int(node), _dptr(out)), "stage_table")
+        return out
+
+    def bed_levels(self):
+        """[B, N]: every reach's bed levels as the kernels read them (table and polyline batches)"""
+        out = np.empty((self.B, self.N))
+        A.check(self._lib.fs_batch_get_bed_levels(self._h, _dptr(out)), "bed_levels")
+        return out
 
     def set_boundary(self, side: int, spec: BoundarySpec):
         """one kind for the batch, its parameters shared or [B]; BC_HOST_ROW and BC_STORAGE_CURVE follow no hydrograph"""

@@ -115,6 +115,58 @@ def run_scenario_ensemble(solver, pool, inflow_table, inflow_scale=None, inflow_
         return out
 
 
+def run_geometry_ensemble(solver, dz_left=None, dz_main=None, dz_right=None, n_scale=None, tolerance=1e-4, max_iter=100, dtype="f64",
+                          device=0, monitor=True, summaries=False, score=None, bands=None, hydrographs=True):
+    """Geometry ensembles of a surveyed river: members that differ in the bed level of the main channel, the elevation of the left
+    and right floodplain (levees included) and the three roughnesses.  `solver`: a set-up (not yet run) PreissmannSolver whose
+    channel has polyline sections at every node; member r is that channel with the main-channel / left / right vertices of node i
+    lifted by dz_main / dz_left / dz_right [r, i] ([B]: the same at every node; None: 0) and (n_left, n_main, n_right) multiplied by
+    n_scale[0..2, r] ([3, B]; None: 1) - _pack.member_sections is the definition.  The reference builds one Channel per member.
+
+    Everything per member is made on the device: polylines, bed levels and stage tables (PreissmannBatch.
+    set_geometry_irregular_members), the initial state by the channel's own interpolation method on each member's geometry
+    (init_state), and each boundary's bed_level is the member's own (bed_levels() of the end nodes).
+
+    Keywords and return value: as run_manning_ensemble (dtype: polyline batches are fp64)."""
+    ch = solver.channel
+    geo = ch.node_geometry
+    if "irr_npts" not in geo or np.any(np.asarray(geo["irr_npts"]) == 0):
+        raise ValueError("run_geometry_ensemble needs a channel of polyline sections at every node")
+    sizes = {np.shape(v)[-1 if v is n_scale else 0] for v in (dz_left, dz_main, dz_right, n_scale) if v is not None}
+    if len(sizes) > 1:
+        raise ValueError(f"per-member arguments of different lengths: {sorted(sizes)}")
+    B = sizes.pop() if sizes else 1
+    N, nt = solver.number_of_nodes, solver.number_of_time_levels
+    L = max(nt, 2)
+    with PreissmannBatch(B, N, L, dtype=dtype, section_mode="irregular", device=device, monitor=monitor) as b:
+        b.set_scheme(solver.theta, solver.time_step, solver.spatial_step, tolerance, max_iter)
+        b.set_geometry_irregular_members(geo, dz_left, dz_main, dz_right, n_scale)
+        beds = b.bed_levels()
+        for side, boundary, bed in ((A.UPSTREAM, ch.upstream_boundary, beds[:, 0]), (A.DOWNSTREAM, ch.downstream_boundary, beds[:, -1])):
+            spec = boundary_to_spec(boundary, L, solver.time_step)
+            if "bed_level" in spec.params:         # a member's boundary row sees its own bed
+                spec = BoundarySpec(spec.kind, dict(spec.params, bed_level=bed.copy()), spec.target)
+            b.set_boundary(side, spec)
+        method = ch.interpolation_method
+        if method == "steady-state":
+            b.init_state(method, ch.initial_flow_rate, bed_slope=[xs.bed_slope for xs in ch.xs_at_node])
+        else:
+            b.init_state(method, ch.initial_flow_rate, depth_ds=ch.downstream_boundary.initial_depth,
+                         depth_us=ch.upstream_boundary.initial_depth if method == "linear" else None)
+        b.step(nt - 1)
+        out = dict(iterations=b.iterations(0, nt), status=b.status())
+        if hydrographs:
+            out = dict(hydrographs=b.hydrographs(0, nt), **out)
+        if summaries:
+            out["summaries"] = b.summaries(0, nt)
+        if score is not None:
+            out["score"] = b.lookup(A.ROW_Q_IN, A.ROW_H_IN, score["xq"],
+                                    y_offset=score.get("y_offset"), target=score.get("target"), first=0, n=nt)
+        if bands is not None:
+            out["bands"] = b.bands(bands, 0, nt)
+        return out
+
+
 def summary_text(summaries, r, time_step, spatial_step, duration):
     """Member r's result summary in the reference's words (solver.py:188-233; Solver.summary writes the same block from a
     single-channel run) from the numbers PreissmannBatch.summaries computed on the device."""

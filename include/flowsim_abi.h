@@ -229,6 +229,30 @@ int fs_batch_set_geometry_table_per_reach(fs_batch *b, const double *tables, con
 int fs_batch_set_geometry_irregular_per_reach(fs_batch *b, const double *tables, const int32_t *n_pts, int32_t max_pts,
                                               const double *x, const double *z, const double *limits,
                                               const double *n_main_override);
+/* Geometry ensembles of ONE surveyed channel (FS_SEC_IRREGULAR): what the reference does by building one Channel of
+ * IrregularSections per member (cross_section.py:205-246; z_min :231-233; the roughness strips of get_equivalent_n :449-500) is done
+ * on the device from the shared channel - table, n_pts, x, z, limits exactly as fs_batch_set_geometry_irregular takes them, every
+ * node a polyline (n_pts[i] > 0) - and a transform per member r:
+ *   z'_j = z_j + dz_strip(j)[r][i]: vertex j of node i is in the left strip where x_j < limits[i][0], in the right one where
+ *   x_j > limits[i][1], in the main channel otherwise; dz_left / dz_main / dz_right [B][N] each, or NULL (= 0);
+ *   (n_left, n_main, n_right)' = (n_left, n_main, n_right)_i * n_scale[0..2][r]; n_scale [3][B] or NULL (= 1);
+ *   Z_BED'[r][i] = min_j z'_j.  x, the limits and the curvature stay.
+ * The batch is then where fs_batch_set_geometry_irregular_per_reach of the B transformed channels leaves it - polylines, tables and
+ * stage tables (cross_section.py:248-328 summed per interval) bit for bit - without their n_sets * N * poly_table_stride doubles
+ * built, staged and uploaded by the host.  FS_POLY_WALK / FS_POLY_TABLE_MAX_BYTES keep their meaning (fs_batch_poly_tables).  A
+ * main-channel override (n_main_override of the other setters) is cleared: n_scale[1] takes its place.  The call returns when the
+ * members are built; until the next fs_batch_step, fs_batch_last_step_ms reports the HIP-event time of its kernels.
+ *   fs_batch_get_stage_table   node's stage table of reach `reach` (ignored where the batch shares one channel), however it was
+ *                              built: out[max_pts + 16 rounded down to a multiple of 16, + 32 * max_pts]: the breakpoints padded
+ *                              with +inf, then 32 doubles per interval; an error when the batch walks its polylines' edges;
+ *   fs_batch_get_bed_levels    out[B][N]: row Z_BED of every reach's table (FS_SEC_TABLE / FS_SEC_IRREGULAR) - a member's boundary
+ *                              rows take their bed_level from here (boundary.py:24-25). */
+int fs_batch_set_geometry_irregular_members(fs_batch *b, const double *table, const int32_t *n_pts, int32_t max_pts,
+                                            const double *x, const double *z, const double *limits,
+                                            const double *dz_left, const double *dz_main, const double *dz_right,
+                                            const double *n_scale);
+int fs_batch_get_stage_table(fs_batch *b, int32_t reach, int32_t node, double *out);
+int fs_batch_get_bed_levels(fs_batch *b, double *out);
 int fs_batch_set_reach_nodes(fs_batch *b, const int32_t *n_nodes);
 int fs_batch_set_reach_scheme(fs_batch *b, const double *theta, const double *dt, const double *dx);
 int fs_batch_set_reach_tolerance(fs_batch *b, const double *tolerance, const int32_t *max_iter);

@@ -1,0 +1,288 @@
+"""Geometry ensembles of one polyline channel on the CPU: the core functions of flow-sim_amd/csrc/fs_member_geo.hpp - the transform of
+one node, the next breakpoint, one interval's coefficients, the run count: the code the device kernels are made of - built with the
+system compiler under AddressSanitizer / UBSan (tests/member_geo/member_geo_driver.cpp, a program of its own) and held, bit for bit
+on the uint64 view, to two references: flowsim_amd._pack.member_sections (the definition of the member transform, numpy) and
+fs::build_stage_table on its output (the host builder the device tables replace).  Then the validation of the transforms, the
+definition itself against a literal double loop, what the binding hands to the library, and the members the GPU test runs against
+the oracle (tests/member_cases.py)."""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+from flowsim_amd import _abi as A
+from flowsim_amd import _pack
+from oracle import preissmann_oracle as O
+
+import member_cases as MC
+import poly_edges as PE
+
+CSRC = os.path.join(ROOT, "flow-sim_amd", "csrc")
+DRIVER = os.path.join(ROOT, "tests", "member_geo", "member_geo_driver.cpp")
+ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+NSUB, ZLO = 22, 23
+
+
+def kp(P):
+    return (P + 16) & ~15
+
+
+@pytest.fixture(scope="module")
+def driver(tmp_path_factory):
+    if shutil.which("g++") is None:
+        pytest.skip("no system C++ compiler")
+    exe = str(tmp_path_factory.mktemp("member_geo") / "member_geo_driver")
+    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                        "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-I", CSRC, "-o", exe, DRIVER],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return exe
+
+
+def run(exe, *args):
+    r = subprocess.run([exe, *args], capture_output=True, text=True, env=ENV, timeout=600)
+    assert r.returncode == 0 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
+    return r.stdout
+
+
+def hexes(values):
+    return " ".join(float(v).hex() for v in values)
+
+
+def same_bits(got, want, what):
+    got, want = np.ascontiguousarray(got, dtype=np.float64), np.ascontiguousarray(want, dtype=np.float64)
+    assert got.shape == want.shape and np.array_equal(got.view(np.uint64), want.view(np.uint64)), what
+
+
+def members_through_the_header(exe, tmp, geo, B, dzl, dzm, dzr, ns):
+    """the header's core functions node by node on (geo, transforms) against the two references; returns (sections, tables
+    [B, N, stride]) for what a case wants to look at besides"""
+    X, Z, cnt, lim = geo["irr_x"], geo["irr_z"], geo["irr_npts"], geo["irr_limits"]
+    N, P = X.shape
+    sections = _pack.member_sections(geo, B, dzl, dzm, dzr, ns)
+    zero, one = np.zeros((B, N)), np.ones((3, B))
+    dzl, dzm, dzr = (zero if v is None else _pack.member_shift(v, B, N) for v in (dzl, dzm, dzr))
+    ns = one if ns is None else ns
+    lines = [f"{B} {N} {P}"]
+    for i in range(N):
+        c = int(cnt[i])
+        lines += [f"{c} " + hexes([lim[i, 0], lim[i, 1], geo["n_left"][i], geo["n_main"][i], geo["n_right"][i], geo["curvature"][i]]),
+                  hexes(X[i, :c]), hexes(Z[i, :c])]
+    for r in range(B):
+        lines.append(hexes(ns[:, r]))
+        for i in range(N):
+            c = int(cnt[i])
+            lines += [hexes([dzl[r, i], dzm[r, i], dzr[r, i]]),
+                      hexes([sections["n_left"][r, i], sections["n_main"][r, i], sections["n_right"][r, i], sections["z_bed"][r, i]]),
+                      hexes(sections["irr_z"][r, i, :c])]
+    fin, fout = os.path.join(str(tmp), "in.txt"), os.path.join(str(tmp), "out.bin")
+    with open(fin, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    run(exe, "tables", fin, fout)
+    S = kp(P) + 32 * P
+    out = np.fromfile(fout, dtype=np.float64).reshape(B, N, P + 4 + 2 * S)
+    same_bits(out[:, :, :P], sections["irr_z"], "z' against member_sections (padding slots included)")
+    same_bits(out[:, :, P], sections["z_bed"], "z_bed'")
+    for q, k in enumerate(("n_left", "n_main", "n_right")):
+        same_bits(out[:, :, P + 1 + q], sections[k], k)
+    mine, ref = out[:, :, P + 4:P + 4 + S], out[:, :, P + 4 + S:]
+    for r in range(B):
+        for i in range(N):
+            same_bits(mine[r, i], ref[r, i], ("stage table against build_stage_table, +inf padding included", r, i))
+    assert np.all(np.isposinf(ref[:, :, kp(P) - 1])) and not np.any(ref == -1.0)
+    return sections, ref
+
+
+# ---- the census of tests/poly_edges.py under three transforms ------------------------------------------------------------------
+@pytest.mark.parametrize("kind,N,seed", PE.CENSUS, ids=[f"{k}-{n}" for k, n, _ in PE.CENSUS])
+def test_core_functions_give_the_host_builders_tables_bit_for_bit(driver, tmp_path, kind, N, seed):
+    geo = PE.BUILDERS[kind](N, np.random.default_rng(seed)).geo
+    dzl, dzm, dzr, ns = MC.transforms(3, N, 100 + seed)        # member 0: none, 1: main-channel shift only, 2: all three + n_scale
+    assert not np.any(dzm[0]) and np.any(dzm[1]) and not np.any(dzl[1]) and np.any(dzl[2]) and np.any(ns[:, 2] != 1.0)
+    assert max(np.abs(v).max() for v in (dzl, dzm, dzr)) <= 0.3
+    sections, _ = members_through_the_header(driver, tmp_path, geo, 3, dzl, dzm, dzr, ns)
+    same_bits(sections["irr_z"][0], np.take_along_axis(geo["irr_z"], np.minimum(np.arange(geo["irr_z"].shape[1])[None], geo["irr_npts"][:, None] - 1), 1),
+              "the member without a transform is the channel")
+    none = _pack.member_sections(geo, 3)
+    for k in ("irr_z", "z_bed", "n_left", "n_main", "n_right"):
+        same_bits(none[k][2], sections[k][0], ("no transform given at all", k))
+
+
+# ---- what a shift can do to a section ------------------------------------------------------------------------------------------
+def small_channel(x, z, liml, limr, N=2):
+    rough = np.tile([0.05, 0.03, 0.06, liml, limr], (N, 1))
+    return PE.polyline_geo([np.asarray(x, dtype=np.float64)] * N, [np.asarray(z, dtype=np.float64) + 0.25 * i for i in range(N)], rough)
+
+
+def levels_of(table, P):
+    bp = table[:kp(P)]
+    return bp[np.isfinite(bp)]
+
+
+def test_a_shift_that_moves_the_thalweg_to_another_vertex(driver, tmp_path):
+    geo = small_channel([0, 2, 4, 6, 8], [3.0, 1.0, 0.0, 0.5, 3.0], 3.0, 5.0)      # vertex 2 alone is the main channel
+    dzm = np.array([0.0, 0.75])
+    sections, tabs = members_through_the_header(driver, tmp_path, geo, 2, None, dzm, None, None)
+    assert np.array_equal(sections["irr_z"][:, 0].argmin(axis=1), [2, 3])
+    assert np.array_equal(sections["z_bed"][:, 0], [0.0, 0.5]) and np.array_equal(tabs[:, 0, kp(5) + 29], [0.0, 0.5])
+
+
+def test_a_shift_that_makes_two_elevations_equal(driver, tmp_path):
+    geo = small_channel([0, 2, 4, 6, 8], [3.0, 1.0, 0.0, 0.5, 3.5], 3.0, 5.0)
+    sections, tabs = members_through_the_header(driver, tmp_path, geo, 2, None, np.array([0.0, 0.5]), None, None)
+    assert sections["irr_z"][1, 0, 2] == sections["irr_z"][1, 0, 3]
+    assert len(levels_of(tabs[0, 0], 5)) == 5 and len(levels_of(tabs[1, 0], 5)) == 4, "one breakpoint fewer"
+
+
+def test_a_levee_crest_shifted_across_a_main_channel_elevation(driver, tmp_path):
+    # left strip: vertices 0..2 (a channel behind the levee crest at vertex 2); the main channel has a vertex at 1.2
+    geo = small_channel([0, 1, 2, 3, 4, 5, 6], [0.5, 0.4, 1.5, 0.2, 0.0, 1.2, 3.0], 2.5, 7.0)
+    sections, tabs = members_through_the_header(driver, tmp_path, geo, 2, np.array([0.0, -0.4]), None, None, None)
+    assert sections["irr_z"][0, 0, 2] > 1.2 > sections["irr_z"][1, 0, 2], "the crest crosses the elevation 1.2"
+    runs = []
+    for r in range(2):
+        blocks = tabs[r, 0, kp(7):].reshape(7, 32)
+        k = int(np.flatnonzero(blocks[:, ZLO] == 1.2)[0])
+        runs.append(blocks[k, NSUB])
+    assert runs == [2.0, 1.0], "above 1.2: the levee splits the wetted vertices into two runs, the lowered one does not"
+
+
+def test_infinite_limits_make_everything_main(driver, tmp_path):
+    geo = small_channel([0, 2, 4, 6, 8], [3.0, 1.0, 0.0, 0.5, 3.5], -np.inf, np.inf)
+    dz = np.array([0.0, 0.25])
+    sections, _ = members_through_the_header(driver, tmp_path, geo, 2, dz * 100, dz, dz * -100, None)
+    same_bits(sections["irr_z"][1], geo["irr_z"] + 0.25, "only dz_main applies")
+
+
+# ---- validation ------------------------------------------------------------------------------------------------------------------
+def verdict(exe, tmp, n_pts, B, dzl=None, dzm=None, dzr=None, ns=None):
+    N = len(n_pts)
+    arrs = [dzl, dzm, dzr, ns]
+    lines = [f"{B} {N}", " ".join(str(int(c)) for c in n_pts), " ".join(str(int(a is not None)) for a in arrs)]
+    lines += [hexes(np.asarray(a, dtype=np.float64).reshape(-1)) for a in arrs if a is not None]
+    fin = os.path.join(str(tmp), "check.txt")
+    with open(fin, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return run(exe, "check", fin).strip()
+
+
+def test_validation_refuses_and_says_why(driver, tmp_path):
+    B, n_pts = 2, [5, 7, 5]
+    ok, ns = np.full((B, 3), 0.1), np.ones((3, B))
+    assert verdict(driver, tmp_path, n_pts, B) == "ok"
+    assert verdict(driver, tmp_path, n_pts, B, ok, -ok, ok, ns) == "ok"
+    trap = verdict(driver, tmp_path, [5, 0, 5], B, ok, ok, ok, ns)
+    assert trap.startswith("fs_batch_set_geometry_irregular_members: every node must be a polyline (n_pts > 0)")
+    finite = "fs_batch_set_geometry_irregular_members: dz_left, dz_main and dz_right must be finite"
+    for slot in range(3):
+        for bad in (np.nan, np.inf, -np.inf):
+            dz = [ok.copy(), ok.copy(), ok.copy()]
+            dz[slot][1, 2] = bad
+            assert verdict(driver, tmp_path, n_pts, B, *dz, ns) == finite, (slot, bad)
+            only = [None, None, None]
+            only[slot] = dz[slot]
+            assert verdict(driver, tmp_path, n_pts, B, *only) == finite, (slot, bad)
+    for bad in (0.0, -1.0, np.nan, np.inf):
+        s = ns.copy()
+        s[2, 1] = bad
+        assert verdict(driver, tmp_path, n_pts, B, ok, ok, ok, s) == "fs_batch_set_geometry_irregular_members: n_scale must be finite and > 0", bad
+
+
+# ---- the definition against a literal double loop ------------------------------------------------------------------------------
+def test_member_sections_is_the_transform_written_out():
+    rng = np.random.default_rng(7)
+    B, N, P = 2, 3, 5
+    x = [np.array([0.0, 2, 4, 6, 8]), np.array([0.0, 3, 3, 7]), np.array([1.0, 2, 5])]
+    z = [np.array([2.0, 0.5, 0.0, 0.75, 2.5]), np.array([1.5, 0.25, 0.5, 2.0]), np.array([1.0, 0.0, 1.25])]
+    rough = np.array([[0.05, 0.03, 0.06, 2.0, 6.0], [0.05, 0.031, 0.06, 3.0, 3.0], [0.045, 0.03, 0.05, -np.inf, np.inf]])
+    geo = PE.polyline_geo(x, z, rough, curv=[0.0, 1e-3, 0.0])
+    dzl, dzm, dzr = (rng.uniform(-0.3, 0.3, (B, N)) for _ in range(3))
+    ns = rng.uniform(0.8, 1.25, (3, B))
+    got = _pack.member_sections(geo, B, dzl, dzm, dzr, ns)
+    for r in range(B):
+        for i in range(N):
+            c = len(x[i])
+            want = np.empty(P)
+            for j in range(P):
+                jj = min(j, c - 1)
+                xv = x[i][jj]
+                shift = dzl[r, i] if xv < rough[i, 3] else (dzr[r, i] if xv > rough[i, 4] else dzm[r, i])
+                want[j] = z[i][jj] + shift
+            same_bits(got["irr_z"][r, i], want, ("z'", r, i))
+            assert got["z_bed"][r, i] == min(want[:c])
+            assert got["n_left"][r, i] == rough[i, 0] * ns[0, r] and got["n_main"][r, i] == rough[i, 1] * ns[1, r] and got["n_right"][r, i] == rough[i, 2] * ns[2, r]
+            assert got["curvature"][r, i] == geo["curvature"][i] and got["irr_npts"][r, i] == c
+            same_bits(got["irr_x"][r, i, :c], x[i], "x stays")
+            same_bits(got["irr_limits"][r, i], rough[i, 3:], "the limits stay")
+    # a station ON a limit is main-channel: node 1's vertices 1 and 2 (x = 3 = both limits)
+    same_bits(got["irr_z"][0, 1, 1:3], z[1][1:3] + dzm[0, 1], "on the limit: main")
+    # what set_geometry_irregular takes per reach
+    tab, cnt, xx, zz, lim, per_reach = _pack.irregular_arrays(got, B, N)
+    assert per_reach and tab.shape == (B, A.GEO_NPARAM, N) and zz.shape == (B, N, P)
+    # [B] shifts: the same at every node
+    same_bits(_pack.member_sections(geo, B, dz_main=np.array([0.1, -0.2]))["irr_z"],
+              _pack.member_sections(geo, B, dz_main=np.repeat([[0.1], [-0.2]], N, axis=1))["irr_z"], "[B] shift")
+
+
+# ---- the binding -----------------------------------------------------------------------------------------------------------------
+class Recorder:
+    """a library that keeps the arguments of every call and answers 0"""
+    def __init__(self):
+        self.calls = []
+
+    def __getattr__(self, name):
+        def call(*args):
+            self.calls.append((name, args))
+            return 0
+        return call
+
+
+def test_the_binding_packs_one_channel_and_the_transforms():
+    """fails without the feature: PreissmannBatch.set_geometry_irregular_members exists and hands the library ONE channel as
+    set_geometry_irregular packs it, the shifts as [B][N] (a [B] shift spread over the nodes) and n_scale as [3][B], absent ones as NULL"""
+    from flowsim_amd.batch import PreissmannBatch
+    assert "fs_batch_set_geometry_irregular_members" in A.SIGNATURES and "fs_batch_get_stage_table" in A.SIGNATURES and "fs_batch_get_bed_levels" in A.SIGNATURES
+    p = PE.BUILDERS["multi_run"](20, np.random.default_rng(4))
+    B, N, P = 3, 20, p.geo["irr_x"].shape[1]
+    b = PreissmannBatch.__new__(PreissmannBatch)
+    b.B, b.N, b.L, b._h, b._lib, b._max_pts = B, N, 4, 1, Recorder(), 0
+    dzm, dzl = np.linspace(-0.1, 0.1, B * N).reshape(B, N), np.array([0.0, 0.1, -0.1])
+    ns = np.array([[1.0, 1.1, 0.9], [1.0, 1.0, 1.2], [0.8, 1.0, 1.0]])
+    b.set_geometry_irregular_members(p.geo, dz_left=dzl, dz_main=dzm, n_scale=ns)
+    (name, args), = b._lib.calls
+    b._h = None
+    assert name == "fs_batch_set_geometry_irregular_members" and len(args) == len(A.SIGNATURES[name][1]) == 11 and args[3] == P
+    tab, cnt, x, z, lim, *_ = _pack.irregular_arrays(p.geo, B, N)
+    arr = lambda ptr, shape, t=np.float64: np.ctypeslib.as_array(ptr, shape=shape).astype(t)
+    same_bits(arr(args[1], tab.shape), tab, "table")
+    assert np.array_equal(np.ctypeslib.as_array(args[2], shape=(N,)), cnt)
+    for ptr, want in ((args[4], x), (args[5], z), (args[6], lim)):
+        same_bits(arr(ptr, want.shape), want, "polylines")
+    same_bits(arr(args[7], (B, N)), np.repeat(dzl[:, None], N, axis=1), "dz_left [B] -> [B][N]")
+    same_bits(arr(args[8], (B, N)), dzm, "dz_main")
+    assert args[9] is None, "dz_right absent: NULL"
+    same_bits(arr(args[10], (3, B)), ns, "n_scale")
+    with pytest.raises(ValueError):
+        _pack.member_arrays(p.geo, B, N, dz_main=np.zeros((B, N + 1)))
+    with pytest.raises(ValueError):
+        _pack.member_arrays(p.geo, B, N, n_scale=np.ones((2, B)))
+    with pytest.raises(ValueError):
+        _pack.member_arrays(_pack.member_sections(p.geo, B), B, N)
+
+
+# ---- the members the GPU test holds to the oracle ------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind,N,seed", MC.ORACLE_CASES, ids=[c[0] for c in MC.ORACLE_CASES])
+def test_the_oracle_members_converge_away_from_the_tolerance(kind, N, seed):
+    """on the oracle alone: the recorded members are the first draws the search accepts, and each converges with no fragile norm"""
+    import json
+    assert json.load(open(MC.CHOICES))[f"{kind}-{N}-{seed}"] == MC.search_oracle_members(kind, N, seed)
+    p, dzl, dzm, dzr, ns, probs, runs = MC.oracle_members(kind, N, seed)
+    assert len(probs) == 3 and max(np.abs(v).max() for v in (dzl, dzm, dzr)) <= 0.1
+    assert dzl.shape == dzm.shape == dzr.shape == (3, N) and ns.shape == (3, 3)
+    for q, run in zip(probs, runs):
+        assert MC.usable(q, run)
+        assert q.us.bed_level == q.geo["z_bed"][0] == q.geo["irr_z"][0].min() and q.ds.bed_level == q.geo["z_bed"][-1]
+    assert np.array_equal(probs[0].geo["irr_z"], p.geo["irr_z"]) and not np.array_equal(probs[2].geo["irr_z"], p.geo["irr_z"])
