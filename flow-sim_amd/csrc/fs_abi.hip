@@ -23,6 +23,7 @@
 
 #include "fs_buffer.hpp"
 #include "fs_entries.hpp"
+#include "fs_envelope.hpp"
 #include "fs_forcing.hpp"
 #include "fs_host_pack.hpp"
 #include "fs_init_state.hpp"
@@ -45,9 +46,13 @@ struct TraceRange {
 FS_ACTIVE_LIST(FS_DECLARE)
 #else
 // an experiment build is this translation unit alone, with a few step kernels: it has no initial-condition kernels (fs_part_init.hip)
-// no post-processing kernels (fs_part_reduce.hip), no forcing kernels (fs_part_forcing.hip) and no geometry kernels
+// no post-processing kernels (fs_part_reduce.hip, fs_part_envelope.hip), no forcing kernels (fs_part_forcing.hip) and no geometry kernels
 // (fs_part_geometry.hip), and fs_batch_init_state, fs_batch_summarize, fs_batch_set_bc_sampled ... say so
 namespace fs {
+bool launch_envelope(const EnvelopeArgs<double> &, int, hipStream_t) { return false; }
+bool launch_envelope(const EnvelopeArgs<float> &, int, hipStream_t) { return false; }
+bool launch_transpose_rows(const TransposeRows &, int, double *, int, int, hipStream_t) { return false; }
+bool launch_profile_bands(const ProfileBandArgs &, hipStream_t) { return false; }
 bool launch_member_sections(const MemberGeoArgs &, hipStream_t) { return false; }
 bool launch_member_tables(const MemberGeoArgs &, hipStream_t) { return false; }
 bool launch_sample_target(const SampleArgs<double> &, hipStream_t) { return false; }
@@ -248,6 +253,12 @@ struct fs_batch : Timeline {
   fs::DeviceBuffer ic_info;             // int32 [2][B]: what fs_batch_init_state reports per reach (allocated on first use)
   fs::DeviceBuffer red_in[3];           // double: what the caller handed to the last fs_batch_lookup / fs_batch_bands (offsets, abscissae or levels, targets)
   fs::DeviceBuffer red_out[3];          // results of the last fs_batch_summarize / lookup / bands, kept and reused (grown, never shrunk)
+  fs::DeviceBuffer env_out;             // double [env_rows][B][N]: the last fs_batch_envelope - its (quantity, statistic) rows, then its crossings (grown, never shrunk)
+  fs::DeviceBuffer env_levels;          // int32 [B]: the rows of each reach that entered it
+  fs::DeviceBuffer env_thr;             // the threshold it was handed, in the batch's type: [N] or [B][N]
+  fs::DeviceBuffer env_t;               // double [2][N][B]: fs_batch_profile_bands' transposed row and crossing counts
+  int env_quantities = 0;               // FS_ENV_* mask of the envelope the handle holds (0: none)
+  bool env_crossings = false;           // ... and whether it has crossing rows
   fs::DeviceBuffer frc_in[2][6];        // double / int32: what fs_batch_set_bc_sampled was handed per side (times, values, table_of, scale, offset, shift)
   fs::DeviceBuffer frc_dt;              // double [B]: the per-reach time steps as the caller gave them (the forcing kernels compute in fp64), or empty
   fs::DeviceBuffer pool_in[5];          // double: fs_batch_route_pool's curve stages, curve volumes, weirs, initial stages, weir multipliers
@@ -1573,6 +1584,135 @@ int fs_batch_bands(fs_batch *b, int32_t first, int32_t n, const double *q, int32
   if (moments && fetch(b, moments, p.moments, n_mom * sizeof(double))) return -1;
   if (want_q && fetch(b, quantiles, p.quantiles, n_qu * sizeof(double))) return -1;
   if (n_members && fetch(b, n_members, p.n_members, (size_t)n * sizeof(int32_t))) return -1;
+  return 0;
+}
+
+int fs_batch_envelope_device(fs_batch *b, int32_t first, int32_t n, int32_t quantities, const double *threshold,
+                             int32_t threshold_per_reach, int32_t threshold_quantity) {
+  if (!b) return fail("fs_batch_envelope: null handle");
+  if (!b->hist_h) return fail("fs_batch_envelope: batch was created without FS_FLAG_HISTORY");
+  if ((quantities & FS_ENV_ALL) == 0 || (quantities & ~FS_ENV_ALL) != 0)
+    return fail("fs_batch_envelope: quantities must be a mask of FS_ENV_DEPTH .. FS_ENV_TOP_WIDTH with at least one bit set");
+  int cross_q = -1;
+  if (threshold) {
+    for (int q = 0; q < fs::kEnvQuantities; ++q)
+      if (threshold_quantity == (1 << q)) cross_q = q;
+    if (cross_q < 0) return fail("fs_batch_envelope: threshold_quantity must be one of FS_ENV_DEPTH .. FS_ENV_TOP_WIDTH");
+  }
+  if (!b->have_state) return fail("fs_batch_envelope: no state yet");
+  if (first < 0 || n < 1 || (int64_t)first + n > (int64_t)b->level + 1)
+    return fail("fs_batch_envelope: levels [" + std::to_string(first) + ", " + std::to_string((int64_t)first + n) + ") are not inside 0 .. " +
+                std::to_string(b->level) + ", the levels this batch has computed");
+  if (b->restart_level > 0 && first < b->restart_level)
+    return fail("fs_batch_envelope: this batch was restarted at level " + std::to_string(b->restart_level) +
+                "; the history before it was not restored");
+  FS_ON_DEVICE(b);
+  TraceRange range_("flowsim:envelope");
+  const size_t B = b->d.n_reaches, BN = B * b->d.n_nodes;
+  int n_sel = 0;
+  for (int q = 0; q < fs::kEnvQuantities; ++q) n_sel += (quantities >> q) & 1;
+  b->env_quantities = 0; b->env_crossings = false;      // (the handle holds no envelope until this one is launched)
+  HIP_TRY(hipStreamSynchronize(b->stream));             // an earlier call's kernels are through with the threshold
+  if (threshold && upload(b, b->env_thr, threshold, threshold_per_reach ? BN : (size_t)b->d.n_nodes)) return -1;
+  HIP_TRY(b->env_out.reserve(((size_t)n_sel * FS_ENV_NSTAT + (threshold ? FS_ENV_NCROSS : 0)) * BN * sizeof(double)));
+  HIP_TRY(b->env_levels.reserve(B * sizeof(int32_t)));
+  const char *unroll_env = std::getenv("FS_ENVELOPE_UNROLL");      // levels whose loads a thread has in flight: 1, 4, 8 (tools/time_envelope.py compares)
+  const int unroll = unroll_env ? std::atoi(unroll_env) : 0;       // 0: the launcher's choice
+  HIP_TRY(hipEventRecord(b->ev0, b->stream));      // fs_batch_last_step_ms() then reports this kernel
+  const bool launched = with_real(b, [&](auto real) {
+    using R = decltype(real);
+    fs::EnvelopeArgs<R> a{b->d.n_reaches, b->d.n_nodes, first, n, b->d.section_mode, b->hist_h.get<const R>(), b->hist_Q.get<const R>(),
+                          b->geo_uniform.get<const R>(), b->geo_table.get<const R>(), b->poly_x.get<const R>(), b->poly_z.get<const R>(),
+                          b->poly_n.get<const int32_t>(), (int64_t)b->geo_reach_stride, (int64_t)b->poly_reach_stride,
+                          b->reach_nodes.get<const int32_t>(), reduce_args<R>(b, first, n), quantities, cross_q,
+                          threshold ? b->env_thr.get<const R>() : nullptr, threshold_per_reach ? 1 : 0, b->env_out.get<double>(),
+                          threshold ? b->env_out.get<double>() + (size_t)n_sel * FS_ENV_NSTAT * BN : nullptr, b->env_levels.get<int32_t>()};
+    return fs::launch_envelope(a, unroll, b->stream);
+  });
+  if (!launched) return fail(std::string("fs_batch_envelope") + kNoReduceKernels);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(b->ev1, b->stream));
+  b->timed = true; b->launches = 1;
+  b->env_quantities = quantities; b->env_crossings = threshold != nullptr;
+  return 0;
+}
+
+void *fs_batch_envelope_device_ptr(fs_batch *b, int32_t row) {
+  if (!b) { fail("fs_batch_envelope_device_ptr: null handle"); return nullptr; }
+  int n_rows = 0;
+  for (int q = 0; q < fs::kEnvQuantities; ++q) n_rows += ((b->env_quantities >> q) & 1) * FS_ENV_NSTAT;
+  if (b->env_crossings) n_rows += FS_ENV_NCROSS;
+  if (row < 0 || row >= n_rows) { fail("fs_batch_envelope_device_ptr: the envelope this handle holds has no such row"); return nullptr; }
+  return b->env_out.get<double>() + (size_t)row * b->d.n_reaches * b->d.n_nodes;
+}
+
+int fs_batch_envelope(fs_batch *b, int32_t first, int32_t n, int32_t quantities, const double *threshold, int32_t threshold_per_reach,
+                      int32_t threshold_quantity, double *out, double *crossing, int32_t *levels) {
+  if (!b) return fail("fs_batch_envelope: null handle");
+  if (crossing && !threshold) return fail("fs_batch_envelope: crossings need a threshold");
+  if (fs_batch_envelope_device(b, first, n, quantities, threshold, threshold_per_reach, threshold_quantity)) return -1;
+  FS_ON_DEVICE(b);
+  const size_t B = b->d.n_reaches, BN = B * b->d.n_nodes;
+  size_t n_out = 0;
+  for (int q = 0; q < fs::kEnvQuantities; ++q) n_out += (size_t)((quantities >> q) & 1) * FS_ENV_NSTAT * BN;
+  if (out && fetch(b, out, b->env_out.get(), n_out * sizeof(double))) return -1;
+  if (crossing && fetch(b, crossing, b->env_out.get<double>() + n_out, (size_t)FS_ENV_NCROSS * BN * sizeof(double))) return -1;
+  if (levels && fetch(b, levels, b->env_levels.get(), B * sizeof(int32_t))) return -1;
+  return 0;
+}
+
+int fs_batch_profile_bands(fs_batch *b, int32_t quantity, int32_t stat, const double *q, int32_t n_q, double *moments, double *quantiles,
+                           double *exceed, int32_t *n_members) {
+  if (!b) return fail("fs_batch_profile_bands: null handle");
+  if (!moments && !quantiles && !exceed && !n_members)
+    return fail("fs_batch_profile_bands: no output requested (moments, quantiles, exceed and n_members are all NULL)");
+  if (n_q < 0 || n_q > fs::kBandMaxQ) return fail("fs_batch_profile_bands: n_q must be 0 .. " + std::to_string(fs::kBandMaxQ));
+  if (n_q > 0 && !q) return fail("fs_batch_profile_bands: null quantile levels");
+  for (int i = 0; i < n_q; ++i)
+    if (!(q[i] >= 0.0 && q[i] <= 1.0)) return fail("fs_batch_profile_bands: quantile levels must be in [0, 1]");
+  if (b->env_quantities == 0) return fail("fs_batch_profile_bands: this handle holds no envelope (fs_batch_envelope comes first)");
+  int n_sel = 0, row = -1;
+  for (int k = 0; k < fs::kEnvQuantities; ++k) {
+    if (!((b->env_quantities >> k) & 1)) continue;
+    if (quantity == (1 << k) && stat >= 0 && stat < FS_ENV_NSTAT) row = n_sel * FS_ENV_NSTAT + stat;
+    ++n_sel;
+  }
+  if (quantity == FS_ENV_CROSSING && b->env_crossings && stat >= 0 && stat < FS_ENV_NCROSS) row = n_sel * FS_ENV_NSTAT + stat;
+  if (row < 0) return fail("fs_batch_profile_bands: the envelope this handle holds has no such row (quantity " + std::to_string(quantity) +
+                           ", statistic " + std::to_string(stat) + ")");
+  if (exceed && !b->env_crossings) return fail("fs_batch_profile_bands: exceed needs an envelope that was computed with a threshold");
+  FS_ON_DEVICE(b);
+  TraceRange range_("flowsim:reduce");
+  const int B = b->d.n_reaches, N = b->d.n_nodes;
+  const size_t BN = (size_t)B * N;
+  const bool want_q = quantiles && n_q > 0;
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  if (want_q && upload_f64(b->red_in[1], q, (size_t)n_q)) return -1;
+  HIP_TRY(b->env_t.reserve((exceed ? 2 : 1) * BN * sizeof(double)));
+  // moments [N][4], then quantiles [N][n_q], then exceed [N], then n_members [N]
+  const size_t n_mom = (size_t)N * 4, n_qu = want_q ? (size_t)N * n_q : 0;
+  HIP_TRY(b->red_out[2].reserve((n_mom + n_qu + (size_t)N) * sizeof(double) + (size_t)N * sizeof(int32_t)));
+  double *d_mom = b->red_out[2].get<double>();
+  const double *env = b->env_out.get<const double>();
+  fs::TransposeRows rows{{env + (size_t)row * BN, env + ((size_t)n_sel * FS_ENV_NSTAT + FS_ENV_CROSS_COUNT) * BN}};
+  fs::ProfileBandArgs p;
+  p.x = b->env_t.get<const double>(); p.count = exceed ? p.x + BN : nullptr;
+  p.status = b->status.get<const int32_t>(); p.levels = b->env_levels.get<const int32_t>(); p.reach_nodes = b->reach_nodes.get<const int32_t>();
+  p.B = B; p.N = N;
+  p.q = want_q ? b->red_in[1].get<const double>() : nullptr; p.n_q = want_q ? n_q : 0;
+  p.moments = moments ? d_mom : nullptr; p.quantiles = want_q ? d_mom + n_mom : nullptr; p.exceed = exceed ? d_mom + n_mom + n_qu : nullptr;
+  p.n_members = n_members ? (int32_t *)(d_mom + n_mom + n_qu + N) : nullptr;
+  HIP_TRY(hipEventRecord(b->ev0, b->stream));      // fs_batch_last_step_ms(): the transpose and the bands
+  const bool launched = fs::launch_transpose_rows(rows, exceed ? 2 : 1, b->env_t.get<double>(), B, N, b->stream) &&
+                        fs::launch_profile_bands(p, b->stream);
+  if (!launched) return fail(std::string("fs_batch_profile_bands") + kNoReduceKernels);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(b->ev1, b->stream));
+  b->timed = true; b->launches = 2;
+  if (moments && fetch(b, moments, p.moments, n_mom * sizeof(double))) return -1;
+  if (want_q && fetch(b, quantiles, p.quantiles, n_qu * sizeof(double))) return -1;
+  if (exceed && fetch(b, exceed, p.exceed, (size_t)N * sizeof(double))) return -1;
+  if (n_members && fetch(b, n_members, p.n_members, (size_t)N * sizeof(int32_t))) return -1;
   return 0;
 }
 

@@ -37,6 +37,13 @@ SUM_ROWS = ("levels", "q_in", "q_out", "q_net", "peak_q_in", "peak_q_in_level", 
             "peak_h_in", "peak_h_in_level", "peak_h_out", "peak_h_out_level", "median_in_level", "median_out_level")
 ROW_H_IN, ROW_Q_IN, ROW_H_OUT, ROW_Q_OUT = 0, 1, 2, 3      # x_row / y_row of fs_batch_lookup: h[0], Q[0], h[N-1], Q[N-1]
 BANDS_MAX_Q = 16
+# fs_batch_envelope: the quantities in bit order (FS_ENV_DEPTH = 1 .. FS_ENV_TOP_WIDTH = 32), the statistics per quantity (FS_ENV_MAX ..)
+# and the crossing rows (FS_ENV_CROSS_FIRST ..)
+ENV_QUANTITIES = ("depth", "stage", "flow", "velocity", "froude_number", "top_width")
+ENV_ALL = 63
+ENV_CROSSING = 64
+ENV_STATS = ("max", "max_level", "min", "min_level")
+ENV_CROSS_ROWS = ("first", "last", "count")
 ABI_VERSION = 3
 
 
@@ -102,6 +109,10 @@ SIGNATURES = {
     "fs_batch_summarize": (C.c_int, [_P, C.c_int32, C.c_int32, _D]),
     "fs_batch_lookup": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D, _D, C.c_int32, _D, _D, _D, _I]),
     "fs_batch_bands": (C.c_int, [_P, C.c_int32, C.c_int32, _D, C.c_int32, _D, _D, _I]),
+    "fs_batch_envelope": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _D, C.c_int32, C.c_int32, _D, _D, _I]),
+    "fs_batch_envelope_device": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _D, C.c_int32, C.c_int32]),
+    "fs_batch_envelope_device_ptr": (_P, [_P, C.c_int32]),
+    "fs_batch_profile_bands": (C.c_int, [_P, C.c_int32, C.c_int32, _D, C.c_int32, _D, _D, _D, _I]),
     "fs_batch_hydrograph_device_ptr": (_P, [_P]),
     "fs_batch_stream": (_P, [_P]),
     "fs_batch_last_step_ms": (C.c_double, [_P]),

@@ -2,7 +2,7 @@
 only, no arithmetic - but for member_sections, the member transform of a geometry ensemble written out in numpy (its definition, and
 the host path the device kernels replace).  Every function returns C-contiguous arrays of the dtype and shape the call takes; batch.py passes them on.
 tests/test_batch_pack.py holds them on the CPU to the arrays the setters built before these functions existed, and to what
-fs::check_bc / fs::check_bc_per_reach accept."""
+fs::check_bc / fs::check_bc_per_reach accept; tests/test_envelope_pack.py holds the envelope arguments."""
 import numpy as np
 
 from . import _abi as A
@@ -283,3 +283,65 @@ def weir_scale(v, n_w, B):
     if v.shape not in ((n_w,), (n_w, B)):
         raise ValueError("weir_scale must be [n_weirs] or [n_weirs, B]")
     return np.ascontiguousarray(np.broadcast_to(v[:, None] if v.ndim == 1 else v, (n_w, B)))
+
+
+# -- flood envelopes ------------------------------------------------------------------------------
+def envelope_quantity(name):
+    """the FS_ENV_* bit of one quantity name of _abi.ENV_QUANTITIES"""
+    if name not in A.ENV_QUANTITIES:
+        raise ValueError(f"unknown envelope quantity {name!r}: one of {', '.join(A.ENV_QUANTITIES)}")
+    return 1 << A.ENV_QUANTITIES.index(name)
+
+
+def envelope_mask(quantities):
+    """(FS_ENV_* mask, names in bit order - the order of the rows fs_batch_envelope writes); a single name may be given as a str"""
+    names = (quantities,) if isinstance(quantities, str) else tuple(quantities)
+    if not names:
+        raise ValueError("no envelope quantity given")
+    mask = 0
+    for name in names:
+        bit = envelope_quantity(name)
+        if mask & bit:
+            raise ValueError(f"envelope quantity {name!r} given twice")
+        mask |= bit
+    return mask, tuple(n for n in A.ENV_QUANTITIES if mask & envelope_quantity(n))
+
+
+def envelope_threshold(threshold, B, N):
+    """(None | [N] | [B, N] float64, per_reach) of fs_batch_envelope; a scalar is the same level at every node.  NaN entries stay: they
+    mean "not assessed" """
+    if threshold is None:
+        return None, 0
+    t = np.asarray(threshold, dtype=np.float64)
+    if t.ndim == 0:
+        t = np.full(N, float(t))
+    if t.shape not in ((N,), (B, N)):
+        raise ValueError(f"threshold must be a scalar, [N] = [{N}] or [B, N] = [{B}, {N}], not {list(t.shape)}")
+    return np.ascontiguousarray(t), int(t.ndim == 2)
+
+
+def envelope_row(quantity, stat, selected, crossings):
+    """(quantity, stat) of fs_batch_profile_bands for a name pair: quantity one of `selected` (the names the envelope on the handle
+    holds) with stat of _abi.ENV_STATS, or "crossing" with stat of _abi.ENV_CROSS_ROWS"""
+    if quantity == "crossing":
+        if not crossings:
+            raise ValueError("the envelope was computed without a threshold: it has no crossing rows")
+        if stat not in A.ENV_CROSS_ROWS:
+            raise ValueError(f"unknown crossing row {stat!r}: one of {', '.join(A.ENV_CROSS_ROWS)}")
+        return A.ENV_CROSSING, A.ENV_CROSS_ROWS.index(stat)
+    bit = envelope_quantity(quantity)
+    if quantity not in selected:
+        raise ValueError(f"the envelope on this batch does not hold {quantity!r} (it holds: {', '.join(selected) or 'nothing'})")
+    if stat not in A.ENV_STATS:
+        raise ValueError(f"unknown envelope statistic {stat!r}: one of {', '.join(A.ENV_STATS)}")
+    return bit, A.ENV_STATS.index(stat)
+
+
+def quantile_levels(quantiles):
+    """float64 [n_q], 0 <= n_q <= BANDS_MAX_Q, each in [0, 1]"""
+    q = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
+    if len(q) > A.BANDS_MAX_Q:
+        raise ValueError(f"at most {A.BANDS_MAX_Q} quantile levels")
+    if np.any(~((q >= 0.0) & (q <= 1.0))):
+        raise ValueError("quantile levels must be in [0, 1]")
+    return q

@@ -62,6 +62,7 @@ class PreissmannBatch:
             raise A.FlowsimError(A.last_error())
         self.history = history
         self._max_pts = 0           # stations per polyline row of the geometry on the device (stage_table)
+        self._envelope = ((), False)      # what the envelope on the handle holds: quantity names, crossing rows
 
     # -- lifetime -------------------------------------------------------------------------
     def close(self):
@@ -392,6 +393,61 @@ class PreissmannBatch:
         A.check(self._lib.fs_batch_bands(self._h, int(first), int(n), _opt(q if len(q) else None), len(q), _dptr(mom),
                                          _opt(qu if len(q) else None), _iptr(cnt)), "bands")
         return dict(min=mom[:, :, 0], max=mom[:, :, 1], mean=mom[:, :, 2], std=mom[:, :, 3], quantiles=qu, n_members=cnt)
+
+    # -- flood envelopes along the reach (the stored history is reduced where it is) ----------------
+    def envelope(self, quantities=("stage",), threshold=None, threshold_quantity="stage", first=0, n=None):
+        """Per (reach, node) over the levels [first, first + n) of the stored history (needs history=True): dict name -> dict(max,
+        max_level, min, min_level) of [B, N] for the names of _abi.ENV_QUANTITIES given, plus levels [B] (the rows of each reach that
+        entered: a failed reach enters with the rows before its failing level) and crossing = dict(first, last, count) of [B, N] or
+        None.  Levels are relative to `first` and are first indices, as np.argmax / np.argmin.  threshold: scalar, [N] or [B, N],
+        held against `threshold_quantity` (typically stage against the bank or levee crest): the first and last level at or above
+        it (-1: never) and their number; NaN entries are not assessed.  The envelope stays on the device for profile_bands."""
+        n = self._span(first, n)
+        mask, names = P.envelope_mask(quantities)
+        thr, per_reach = P.envelope_threshold(threshold, self.B, self.N)
+        out = np.empty((len(names), len(A.ENV_STATS), self.B, self.N))
+        cross = None if thr is None else np.empty((len(A.ENV_CROSS_ROWS), self.B, self.N))
+        levels = np.empty(self.B, dtype=np.int32)
+        self._envelope = ((), False)
+        A.check(self._lib.fs_batch_envelope(self._h, int(first), int(n), mask, _opt(thr), per_reach, P.envelope_quantity(threshold_quantity),
+                                            _dptr(out), _opt(cross), _iptr(levels)), "envelope")
+        self._envelope = (names, thr is not None)
+        res = {name: dict(zip(A.ENV_STATS, out[i])) for i, name in enumerate(names)}
+        res["levels"] = levels
+        res["crossing"] = None if cross is None else dict(zip(A.ENV_CROSS_ROWS, cross))
+        return res
+
+    def envelope_device(self, quantities=("stage",), threshold=None, threshold_quantity="stage", first=0, n=None):
+        """envelope() with the results left on the device; returns {(name, stat): device pointer to [B, N] float64}, the crossing rows
+        under ("crossing", "first" | "last" | "count")."""
+        n = self._span(first, n)
+        mask, names = P.envelope_mask(quantities)
+        thr, per_reach = P.envelope_threshold(threshold, self.B, self.N)
+        self._envelope = ((), False)
+        A.check(self._lib.fs_batch_envelope_device(self._h, int(first), int(n), mask, _opt(thr), per_reach,
+                                                   P.envelope_quantity(threshold_quantity)), "envelope_device")
+        self._envelope = (names, thr is not None)
+        keys = [(name, stat) for name in names for stat in A.ENV_STATS] + ([("crossing", c) for c in A.ENV_CROSS_ROWS] if thr is not None else [])
+        return {k: self._lib.fs_batch_envelope_device_ptr(self._h, i) for i, k in enumerate(keys)}
+
+    def profile_bands(self, quantity, stat="max", quantiles=(0.05, 0.5, 0.95)):
+        """Across the members, per node, of one row of the envelope this batch holds (envelope() comes first): dict(min, max, mean,
+        std [N], quantiles [N, n_q]: exact order statistics, numpy's default method; exceed [N]: the fraction of the entering members
+        that reached the threshold at the node, or None for an envelope without a threshold; n_members [N]).  quantity: a name the
+        envelope was computed for with stat of _abi.ENV_STATS, or "crossing" with stat "first" | "last" | "count".  Failed members,
+        members without rows and, at a node, members of a ragged batch that do not have it are left out."""
+        names, crossings = self._envelope
+        if not names:
+            raise ValueError("this batch holds no envelope: call envelope() first")
+        qbit, row = P.envelope_row(quantity, stat, names, crossings)
+        q = P.quantile_levels(quantiles)
+        mom = np.empty((self.N, 4))
+        qu = np.empty((self.N, len(q)))
+        exceed = np.empty(self.N) if crossings else None
+        cnt = np.empty(self.N, dtype=np.int32)
+        A.check(self._lib.fs_batch_profile_bands(self._h, qbit, row, _opt(q if len(q) else None), len(q), _dptr(mom),
+                                                 _opt(qu if len(q) else None), _opt(exceed), _iptr(cnt)), "profile_bands")
+        return dict(min=mom[:, 0], max=mom[:, 1], mean=mom[:, 2], std=mom[:, 3], quantiles=qu, exceed=exceed, n_members=cnt)
 
     def last_step_ms(self):
         return self._lib.fs_batch_last_step_ms(self._h)

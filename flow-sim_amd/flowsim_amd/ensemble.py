@@ -8,8 +8,19 @@ from .batch import BoundarySpec, PreissmannBatch
 from .hydromodel.preissmann import boundary_to_spec
 
 
+def _add_envelope(out, b, envelope, nt):
+    """out['envelope'] and out['profile_bands'] of the runners' envelope= keyword"""
+    unknown = set(envelope) - {"quantities", "threshold", "threshold_quantity", "quantiles"}
+    if unknown:
+        raise ValueError(f"envelope: unknown keys {sorted(unknown)}")
+    env = b.envelope(envelope.get("quantities", ("stage",)), envelope.get("threshold"), envelope.get("threshold_quantity", "stage"), 0, nt)
+    out["envelope"] = env
+    out["profile_bands"] = {name: b.profile_bands(name, "max", envelope.get("quantiles", (0.05, 0.5, 0.95)))
+                            for name in env if name not in ("levels", "crossing")}
+
+
 def run_manning_ensemble(solver, n_main_values, tolerance=1e-4, max_iter=100, dtype="f64", device=0, monitor=True, initial="host",
-                         summaries=False, score=None, bands=None, hydrographs=True):
+                         summaries=False, score=None, bands=None, hydrographs=True, envelope=None):
     """`solver`: a set-up (not yet run) PreissmannSolver whose channel provides geometry, boundaries
     and initial conditions; the initial conditions are shared by all members (the reference's
     members start from the same downstream level and the same flow; their GVF profiles differ
@@ -25,6 +36,12 @@ def run_manning_ensemble(solver, n_main_values, tolerance=1e-4, max_iter=100, dt
     bands=(q, ...) adds 'bands' (min, max, mean, std [nt, 4], quantiles [nt, 4, n_q], n_members [nt] across the members);
     hydrographs=False leaves the block on the device - at 32 768 members and 385 levels it is 400 MB.
 
+    Along the reach: envelope=dict(quantities=("stage",), threshold=None, threshold_quantity="stage", quantiles=(0.05, 0.5, 0.95))
+    adds 'envelope' (PreissmannBatch.envelope over all levels: per member and node the extremes, their levels, the crossings of the
+    threshold) and 'profile_bands' (dict name -> PreissmannBatch.profile_bands of that quantity's maxima across the members).  Its
+    cost: the batch is created with history=True, which selects the step kernels compiled with diagnostics and holds the whole
+    history, 2 * levels * B * N values, on the device.  With envelope=None nothing changes.
+
     Returns dict(hydrographs[nt, 4, B], iterations[nt, B], status[B]) and what the keywords above add."""
     if initial not in ("host", "gvf"):
         raise ValueError("initial must be 'host' or 'gvf'")
@@ -32,7 +49,7 @@ def run_manning_ensemble(solver, n_main_values, tolerance=1e-4, max_iter=100, dt
     n_vals = np.ascontiguousarray(n_main_values, dtype=np.float64)
     B, N, nt = len(n_vals), solver.number_of_nodes, solver.number_of_time_levels
     ics = getattr(ch, "member_ics", None)
-    with PreissmannBatch(B, N, max(nt, 2), dtype=dtype, section_mode="table", device=device, monitor=monitor) as b:
+    with PreissmannBatch(B, N, max(nt, 2), dtype=dtype, section_mode="table", device=device, monitor=monitor, history=envelope is not None) as b:
         b.set_scheme(solver.theta, solver.time_step, solver.spatial_step, tolerance, max_iter)
         b.set_geometry_table(ch.node_geometry, n_main_override=n_vals)
         b.set_boundary(A.UPSTREAM, boundary_to_spec(ch.upstream_boundary, max(nt, 2), solver.time_step))
@@ -54,12 +71,14 @@ def run_manning_ensemble(solver, n_main_values, tolerance=1e-4, max_iter=100, dt
                                     y_offset=score.get("y_offset"), target=score.get("target"), first=0, n=nt)
         if bands is not None:
             out["bands"] = b.bands(bands, 0, nt)
+        if envelope is not None:
+            _add_envelope(out, b, envelope, nt)
         return out
 
 
 def run_scenario_ensemble(solver, pool, inflow_table, inflow_scale=None, inflow_shift=None, pool_level=None, weir_scale=None, n_main=None,
                           initial="gvf", tolerance=1e-4, max_iter=100, dtype="f64", device=0, monitor=True, summaries=False, score=None,
-                          bands=None, hydrographs=True):
+                          bands=None, hydrographs=True, envelope=None):
     """Scenario ensembles: members that differ in what the reach is forced with - the inflow into the reservoir upstream of it
     (`inflow_table` [K, 2], time [s] and flow, per member multiplied by inflow_scale and delayed by inflow_shift [s]), the pool
     level the reservoir starts from (pool_level, required; it is also the member's hold level), the outlets in service (weir_scale
@@ -75,7 +94,7 @@ def run_scenario_ensemble(solver, pool, inflow_table, inflow_scale=None, inflow_
     today from the default initial flow (model.py:79-81): it is not rebuilt per member.
 
     A member whose pool leaves the bracket (the reference's ValueError) carries POOL_NO_BRACKET in 'pool' and ends with status NAN.
-    Post-processing keywords and what they add: as run_manning_ensemble.  Returns dict(hydrographs[nt, 4, B], iterations[nt, B],
+    Post-processing keywords and what they add: as run_manning_ensemble (envelope= included, at the same cost: history=True).  Returns dict(hydrographs[nt, 4, B], iterations[nt, B],
     status[B], initial_flow[B], pool=dict(flags[B], level[B])) and what the keywords add."""
     if initial != "gvf":
         raise ValueError("initial must be 'gvf': every member starts from the backwater profile of its own release")
@@ -93,7 +112,7 @@ def run_scenario_ensemble(solver, pool, inflow_table, inflow_scale=None, inflow_
     N, nt = solver.number_of_nodes, solver.number_of_time_levels
     L = max(nt, 2)
     n_vals = None if n_main is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n_main, dtype=np.float64), (B,)))
-    with PreissmannBatch(B, N, L, dtype=dtype, section_mode="table", device=device, monitor=monitor) as b:
+    with PreissmannBatch(B, N, L, dtype=dtype, section_mode="table", device=device, monitor=monitor, history=envelope is not None) as b:
         b.set_scheme(solver.theta, solver.time_step, solver.spatial_step, tolerance, max_iter)
         b.set_geometry_table(ch.node_geometry, n_main_override=n_vals)
         b.set_boundary_sampled(A.UPSTREAM, BoundarySpec(A.BC_FLOW_HYDROGRAPH), table[:, 0], table[:, 1], scale=inflow_scale, shift=inflow_shift)
@@ -112,11 +131,13 @@ def run_scenario_ensemble(solver, pool, inflow_table, inflow_scale=None, inflow_
                                     y_offset=score.get("y_offset"), target=score.get("target"), first=0, n=nt)
         if bands is not None:
             out["bands"] = b.bands(bands, 0, nt)
+        if envelope is not None:
+            _add_envelope(out, b, envelope, nt)
         return out
 
 
 def run_geometry_ensemble(solver, dz_left=None, dz_main=None, dz_right=None, n_scale=None, tolerance=1e-4, max_iter=100, dtype="f64",
-                          device=0, monitor=True, summaries=False, score=None, bands=None, hydrographs=True):
+                          device=0, monitor=True, summaries=False, score=None, bands=None, hydrographs=True, envelope=None):
     """Geometry ensembles of a surveyed river: members that differ in the bed level of the main channel, the elevation of the left
     and right floodplain (levees included) and the three roughnesses.  `solver`: a set-up (not yet run) PreissmannSolver whose
     channel has polyline sections at every node; member r is that channel with the main-channel / left / right vertices of node i
@@ -127,7 +148,7 @@ def run_geometry_ensemble(solver, dz_left=None, dz_main=None, dz_right=None, n_s
     set_geometry_irregular_members), the initial state by the channel's own interpolation method on each member's geometry
     (init_state), and each boundary's bed_level is the member's own (bed_levels() of the end nodes).
 
-    Keywords and return value: as run_manning_ensemble (dtype: polyline batches are fp64)."""
+    Keywords and return value: as run_manning_ensemble (dtype: polyline batches are fp64; envelope= at the same cost: history=True)."""
     ch = solver.channel
     geo = ch.node_geometry
     if "irr_npts" not in geo or np.any(np.asarray(geo["irr_npts"]) == 0):
@@ -138,7 +159,7 @@ def run_geometry_ensemble(solver, dz_left=None, dz_main=None, dz_right=None, n_s
     B = sizes.pop() if sizes else 1
     N, nt = solver.number_of_nodes, solver.number_of_time_levels
     L = max(nt, 2)
-    with PreissmannBatch(B, N, L, dtype=dtype, section_mode="irregular", device=device, monitor=monitor) as b:
+    with PreissmannBatch(B, N, L, dtype=dtype, section_mode="irregular", device=device, monitor=monitor, history=envelope is not None) as b:
         b.set_scheme(solver.theta, solver.time_step, solver.spatial_step, tolerance, max_iter)
         b.set_geometry_irregular_members(geo, dz_left, dz_main, dz_right, n_scale)
         beds = b.bed_levels()
@@ -164,6 +185,8 @@ def run_geometry_ensemble(solver, dz_left=None, dz_main=None, dz_right=None, n_s
                                     y_offset=score.get("y_offset"), target=score.get("target"), first=0, n=nt)
         if bands is not None:
             out["bands"] = b.bands(bands, 0, nt)
+        if envelope is not None:
+            _add_envelope(out, b, envelope, nt)
         return out
 
 

@@ -452,6 +452,47 @@ int fs_batch_lookup(fs_batch *b, int32_t first, int32_t n, int32_t x_row, int32_
 int fs_batch_bands(fs_batch *b, int32_t first, int32_t n, const double *q, int32_t n_q, double *moments, double *quantiles,
                    int32_t *n_members);
 
+/* ---- Flood envelopes along the reach ----
+ * fs_batch_envelope: for the levels [first, first + n) of the stored history (FS_FLAG_HISTORY), for every (reach, node), in one pass
+ * over the levels: the extremes of the quantities of the bit mask `quantities` and the levels at which they occur,
+ * out[n_selected][FS_ENV_NSTAT][B][N] with the selected quantities in bit order.  Each quantity is evaluated as fs_batch_derive
+ * evaluates it (depth, stage = depth + bed, flow, velocity Q/A, Froude number with its clamps, top width), in the batch dtype, and
+ * widened to double on output.  Levels are relative to `first`, as doubles, and are first indices (np.argmax / np.argmin); a NaN sample
+ * behaves as in numpy: the extreme is NaN and its level is the first NaN's.
+ * Crossings (threshold != NULL): crossing[FS_ENV_NCROSS][B][N] = the first level at which the quantity threshold_quantity (one FS_ENV_*
+ * bit, selected or not; typical: stage against a bank or levee crest) is >= the threshold (-1: never), the last such level (-1) and
+ * their number.  threshold[N] is shared, or [B][N] with threshold_per_reach != 0; it is rounded once to the batch dtype, in which the
+ * comparison runs.  A NaN entry means "not assessed": -1, -1, 0.
+ * A reach whose status is a failure enters with the rows before its failing level only (see above); levels[B] (or NULL) receives the
+ * rows that entered.  A reach without rows reports NaN extremes, levels -1 and counts 0; nodes beyond a ragged reach's own count
+ * (fs_batch_set_reach_nodes) report values 0, levels -1 and counts 0.  After fs_batch_restart, ranges that begin before the restart
+ * level are refused.  out, crossing and levels may each be NULL (crossing must be NULL without a threshold).  The results stay on the
+ * handle, in buffers that are kept and reused, for fs_batch_profile_bands; until the next fs_batch_step, fs_batch_last_step_ms reports
+ * the HIP-event time of the kernel. */
+enum { FS_ENV_DEPTH = 1, FS_ENV_STAGE = 2, FS_ENV_FLOW = 4, FS_ENV_VELOCITY = 8, FS_ENV_FROUDE = 16, FS_ENV_TOP_WIDTH = 32,
+       FS_ENV_ALL = 63,
+       FS_ENV_CROSSING = 64 };       /* fs_batch_profile_bands: a crossing row instead of a (quantity, statistic) pair */
+enum { FS_ENV_MAX = 0, FS_ENV_MAX_LEVEL, FS_ENV_MIN, FS_ENV_MIN_LEVEL, FS_ENV_NSTAT };
+enum { FS_ENV_CROSS_FIRST = 0, FS_ENV_CROSS_LAST, FS_ENV_CROSS_COUNT, FS_ENV_NCROSS };
+int fs_batch_envelope(fs_batch *b, int32_t first, int32_t n, int32_t quantities, const double *threshold,
+                      int32_t threshold_per_reach, int32_t threshold_quantity, double *out, double *crossing, int32_t *levels);
+/* The same kernel with everything left on the device (no PCIe traffic but the threshold).  fs_batch_envelope_device_ptr(row) then
+ * points at row `row` of the last envelope, [B][N] doubles: rows 0 .. n_selected * FS_ENV_NSTAT - 1 are out's, the FS_ENV_NCROSS
+ * rows behind them the crossings (where a threshold was given); NULL for any other row.  Valid until the next envelope call. */
+int fs_batch_envelope_device(fs_batch *b, int32_t first, int32_t n, int32_t quantities, const double *threshold,
+                             int32_t threshold_per_reach, int32_t threshold_quantity);
+void *fs_batch_envelope_device_ptr(fs_batch *b, int32_t row);
+/* Across the members, per node, of one row of the envelope the handle holds: quantity = one FS_ENV_* bit that the envelope selected
+ * and stat = FS_ENV_MAX .. FS_ENV_MIN_LEVEL, or quantity = FS_ENV_CROSSING and stat = FS_ENV_CROSS_FIRST .. FS_ENV_CROSS_COUNT.
+ * moments[N][4] = min, max, mean, std (ddof = 0; two passes) or NULL; quantiles[N][n_q] or NULL: exact order statistics at the levels
+ * q[n_q] in [0, 1], 0 <= n_q <= 16, numpy's method "linear" (as fs_batch_bands); exceed[N] or NULL: the fraction of the entering
+ * members whose crossing count is > 0 (needs an envelope computed with a threshold); n_members[N] or NULL.  Left out: failed members,
+ * members without rows and, at a given node, the members of a ragged batch that do not have that node - n_members varies along the
+ * reach.  A node with no member left reports 0 members and NaN.  Fails when the handle holds no envelope or the row was not computed.
+ * At least one output must be given. */
+int fs_batch_profile_bands(fs_batch *b, int32_t quantity, int32_t stat, const double *q, int32_t n_q, double *moments,
+                           double *quantiles, double *exceed, int32_t *n_members);
+
 /* zero-copy access for device-side consumers (RCCL gather of hydrographs): device pointer to the
  * [max_levels][4][B] hydrograph block in the batch dtype, and the handle's hipStream_t */
 void *fs_batch_hydrograph_device_ptr(fs_batch *b);
