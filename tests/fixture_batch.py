@@ -110,17 +110,18 @@ def batch_from_problems(problems, mode="auto", dtype="f64", history=True, n_main
     return b
 
 
-def hetero_batch_from_problems(problems, mode="table", history=True, monitor=None):
+def hetero_batch_from_problems(problems, mode="table", history=True, monitor=None, dtype="f64"):
     """ONE batch from oracle Problems that share nothing: every reach its own channel (node table), node
     count, theta / dt / dx, tolerance / iteration cap, boundary kinds and number of levels (fs_batch_set_geometry_table_per_reach, fs_batch_set_reach_nodes,
-    fs_batch_set_reach_scheme, fs_batch_set_bc_per_reach).  Rows of shorter reaches are padded with their last node."""
+    fs_batch_set_reach_scheme, fs_batch_set_bc_per_reach).  Rows of shorter reaches are padded with their last node.  dtype: the
+    per-reach table setter serves fp32 batches too (the per-reach polyline setters do not: per_reach_polyline_batch has no dtype)."""
     B, N, L = len(problems), max(p.N for p in problems), max(p.nt for p in problems)
     p0 = problems[0]
 
     def pad(a):
         a = np.asarray(a, dtype=np.float64)
         return np.concatenate([a, np.full(N - len(a), a[-1])])
-    b = PreissmannBatch(B, N, L, section_mode=mode, history=history, monitor=history if monitor is None else monitor)
+    b = PreissmannBatch(B, N, L, dtype=dtype, section_mode=mode, history=history, monitor=history if monitor is None else monitor)
     b.set_scheme(p0.theta, p0.dt, p0.dx, p0.tol, p0.max_iter)
     b.set_geometry_table({k: np.stack([pad(p.geo[k]) for p in problems]) for k in A.GEO_ROWS})
     b.set_reach_nodes([p.N for p in problems])

@@ -1,4 +1,5 @@
-"""Geometry-ensemble cases shared by tests/test_member_geometry.py (CPU) and tests/test_gpu_member_geometry.py: seeded member
+"""Geometry-ensemble cases shared by tests/test_member_geometry.py (CPU), tests/test_gpu_member_geometry.py and
+tests/test_gpu_postprocess_geometry.py: seeded member
 transforms of the polyline channels of tests/poly_edges.py, the members as oracle Problems, and the members the oracle comparison
 uses.  flowsim_amd._pack.member_sections is the definition of the transform and the reference throughout."""
 import dataclasses
@@ -9,9 +10,12 @@ import os
 import numpy as np
 
 from conftest import GOLDEN
+from flowsim_amd import _abi as A
 from flowsim_amd import _pack
+from flowsim_amd.batch import BoundarySpec
 from oracle import preissmann_oracle as O
 
+from fixture_batch import boundary_spec
 import poly_edges as PE
 
 log = logging.getLogger("member_cases")
@@ -99,3 +103,42 @@ def oracle_members(kind, N, seed):
         probs = [d[1] for d in draws]
         _built[key] = (p, dzl, dzm, dzr, ns, probs, [O.newton_run(q, trace=True, iterates=True) for q in probs])
     return _built[key]
+
+
+# ---- shared by the GPU tests of the member batches ---------------------------------------------------------------------------------
+def with_member_beds(b, p):
+    """both boundaries of p with bed_level per member, from the batch's own bed levels"""
+    beds = b.bed_levels()
+    for side, bc, bed in ((A.UPSTREAM, p.us, beds[:, 0]), (A.DOWNSTREAM, p.ds, beds[:, -1])):
+        spec = boundary_spec(bc, p.nt)
+        if "bed_level" in spec.params:
+            spec = BoundarySpec(spec.kind, dict(spec.params, bed_level=bed.copy()), spec.target)
+        b.set_boundary(side, spec)
+
+
+SWEEP_CASE = 57        # tests/golden/random_sweep.npz: 9 nodes of 8 .. 15 stations, flow hydrograph in, normal depth out, linear start
+
+
+def mirror_solver(recipe, geo=None):
+    """the mirror's solver of a sweep recipe; with geo (one member of member_sections) on that member's sections: every node an
+    IrregularSection of the transformed polyline, the boundaries on the member's bed, the initial conditions set up again"""
+    from oracle.gen_random_sweep import build_from_recipe
+    from flowsim_amd.hydromodel.cross_section import IrregularSection, section_table
+    solver, _, _ = build_from_recipe(recipe)
+    if geo is None:
+        return solver
+    ch = solver.channel
+    nodes = []
+    for i, xs in enumerate(ch.xs_at_node):
+        c = int(geo["irr_npts"][i])
+        s = IrregularSection(geo["irr_x"][i, :c], geo["irr_z"][i, :c], bed_slope=xs.bed_slope, curvature=xs.curvature)
+        s.n_left, s.n_main, s.n_right = float(geo["n_left"][i]), float(geo["n_main"][i]), float(geo["n_right"][i])
+        s.left_fp_limit, s.right_fp_limit = geo["irr_limits"][i]
+        nodes.append(s)
+    ch.xs_at_node, ch.node_geometry = nodes, section_table(nodes)
+    for bnd, s in ((ch.upstream_boundary, nodes[0]), (ch.downstream_boundary, nodes[-1])):
+        bnd.cross_section, bnd.bed_level = s, s.z_min
+    ch.initial_conditions = np.zeros((len(nodes), 2))
+    {"linear": ch._linear_conditions, "GVF_equation": ch._gvf_conditions, "steady-state": ch._steady_conditions}[ch.interpolation_method](len(nodes), ch.initial_flow_rate)
+    solver.initialize_t0()
+    return solver

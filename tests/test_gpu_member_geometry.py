@@ -12,11 +12,10 @@ import pytest
 
 from flowsim_amd import _abi as A
 from flowsim_amd import _pack
-from flowsim_amd.batch import BoundarySpec, PreissmannBatch
+from flowsim_amd.batch import PreissmannBatch
 from flowsim_amd.ensemble import run_geometry_ensemble
 from oracle import preissmann_oracle as O
 
-from fixture_batch import boundary_spec
 from kernel_harness import TOL, assert_same_bits, rel_err, snapshot
 import member_cases as MC
 import poly_edges as PE
@@ -49,16 +48,6 @@ def test_the_shapes_cross_the_boundaries_they_claim():
     kp = lambda s: (case(s)[0].geo["irr_x"].shape[1] + 16) & ~15
     assert [kp(s) for s in SHAPES] == [16, 16, 16, 16, 256, 32] and case(SHAPES[2])[0].geo["irr_x"].shape[1] == 15
     assert len(set(case(SHAPES[4])[0].geo["irr_npts"])) > 1 and case(SHAPES[4])[0].geo["irr_x"].shape[1] == 245
-
-
-def with_member_beds(b, p):
-    """both boundaries of p with bed_level per member, from the batch's own bed levels"""
-    beds = b.bed_levels()
-    for side, bc, bed in ((A.UPSTREAM, p.us, beds[:, 0]), (A.DOWNSTREAM, p.ds, beds[:, -1])):
-        spec = boundary_spec(bc, p.nt)
-        if "bed_level" in spec.params:
-            spec = BoundarySpec(spec.kind, dict(spec.params, bed_level=bed.copy()), spec.target)
-        b.set_boundary(side, spec)
 
 
 def batch(p, B, history=True):
@@ -117,7 +106,7 @@ def step_both(shape, tables):
         assert dev.poly_tables() == host.poly_tables() == tables
         snaps = []
         for b in (dev, host):
-            with_member_beds(b, p)
+            MC.with_member_beds(b, p)
             b.set_state(np.tile(p.h0, (B, 1)), np.tile(p.Q0, (B, 1)))
             b.step(p.nt - 1)
             snap = snapshot(b, p.nt, fields=("status", "iters", "hyd", "state", "guess"))
@@ -148,7 +137,7 @@ def test_members_against_the_oracle(kind, N, seed):
     assert all(MC.usable(q, ref) for q, ref in zip(probs, refs))
     with batch(p, 3) as b:
         b.set_geometry_irregular_members(p.geo, dzl, dzm, dzr, ns)
-        with_member_beds(b, p)
+        MC.with_member_beds(b, p)
         b.set_state(np.tile(p.h0, (3, 1)), np.tile(p.Q0, (3, 1)))
         b.step(p.nt - 1)
         assert np.all(b.status() == 0), b.status()
@@ -162,39 +151,14 @@ def test_members_against_the_oracle(kind, N, seed):
 
 
 # ---- 4. run_geometry_ensemble ----------------------------------------------------------------------------------------------------
-SWEEP_CASE = 57        # tests/golden/random_sweep.npz: 9 nodes of 8 .. 15 stations, flow hydrograph in, normal depth out, linear start
-
-
-def mirror_solver(recipe, geo=None):
-    """the mirror's solver of a sweep recipe; with geo (one member of member_sections) on that member's sections: every node an
-    IrregularSection of the transformed polyline, the boundaries on the member's bed, the initial conditions set up again"""
-    from oracle.gen_random_sweep import build_from_recipe
-    from flowsim_amd.hydromodel.cross_section import IrregularSection, section_table
-    solver, _, _ = build_from_recipe(recipe)
-    if geo is None:
-        return solver
-    ch = solver.channel
-    nodes = []
-    for i, xs in enumerate(ch.xs_at_node):
-        c = int(geo["irr_npts"][i])
-        s = IrregularSection(geo["irr_x"][i, :c], geo["irr_z"][i, :c], bed_slope=xs.bed_slope, curvature=xs.curvature)
-        s.n_left, s.n_main, s.n_right = float(geo["n_left"][i]), float(geo["n_main"][i]), float(geo["n_right"][i])
-        s.left_fp_limit, s.right_fp_limit = geo["irr_limits"][i]
-        nodes.append(s)
-    ch.xs_at_node, ch.node_geometry = nodes, section_table(nodes)
-    for bnd, s in ((ch.upstream_boundary, nodes[0]), (ch.downstream_boundary, nodes[-1])):
-        bnd.cross_section, bnd.bed_level = s, s.z_min
-    ch.initial_conditions = np.zeros((len(nodes), 2))
-    {"linear": ch._linear_conditions, "GVF_equation": ch._gvf_conditions, "steady-state": ch._steady_conditions}[ch.interpolation_method](len(nodes), ch.initial_flow_rate)
-    solver.initialize_t0()
-    return solver
+SWEEP_CASE = MC.SWEEP_CASE
 
 
 def test_run_geometry_ensemble_against_single_member_runs_of_the_mirror():
     import os
     from conftest import GOLDEN
     _, fx, m = next(c for c in O.sweep_cases(os.path.join(GOLDEN, "random_sweep.npz")) if c[0] == SWEEP_CASE)
-    base = mirror_solver(m["recipe"])
+    base = MC.mirror_solver(m["recipe"])
     geo = base.channel.node_geometry
     N = base.number_of_nodes
     assert np.all(geo["irr_npts"] > 0) and base.channel.downstream_boundary.bed_level == geo["z_bed"][-1]
@@ -208,7 +172,7 @@ def test_run_geometry_ensemble_against_single_member_runs_of_the_mirror():
     assert np.all(out["status"] == 0) and out["hydrographs"].shape == (base.number_of_time_levels, 4, B)
     assert np.array_equal(flat["hydrographs"][:, :, 3], out["hydrographs"][:, :, 3]) and np.array_equal(flat["hydrographs"][:, :, 0], out["hydrographs"][:, :, 0])
     for r in range(B):
-        one = mirror_solver(m["recipe"], None if r == 0 else MC.member_geo(sections, r))      # member 0 has no transform: the untransformed run
+        one = MC.mirror_solver(m["recipe"], None if r == 0 else MC.member_geo(sections, r))      # member 0 has no transform: the untransformed run
         one.run(tolerance=m["tolerance"], verbose=0, max_iter=m["max_iter"])
         want = np.stack([one.depth[:, 0], one.flow[:, 0], one.depth[:, -1], one.flow[:, -1]], axis=1)
         got = out["hydrographs"][:, :, r]
@@ -247,7 +211,7 @@ def test_refusals_leave_the_batch_usable():
             b.set_geometry_irregular_members(tilted, *tr)
         # the geometry of the last good call is still there, and the batch steps
         assert all(same_bits(b.stage_table(r, 5), before[r]) for r in range(B)) and same_bits(b.bed_levels(), sections["z_bed"])
-        with_member_beds(b, p)
+        MC.with_member_beds(b, p)
         b.set_state(np.tile(p.h0, (B, 1)), np.tile(p.Q0, (B, 1)))
         b.step(1)
         assert b.level == 1 and b.status()[0] == 0
