@@ -55,7 +55,9 @@ __device__ __forceinline__ float frsq(float x) {
 
 // x^(-1/3) for x > 0: single-precision log2/exp2 seed y (relative error ~1e-7, so e = 1 - x y^3 ~ 3e-7),
 // then ONE third-order correction y (1 - e)^(-1/3) = y (1 + e/3 + 2 e^2/9 + O(e^3)): the neglected term is
-// ~ (14/81) e^3 < 1e-19, below double rounding (two plain Newton steps cost four more instructions)
+// ~ (14/81) e^3 < 1e-19, below double rounding (two plain Newton steps cost four more instructions).  The double form casts its
+// argument to float for the seed: the argument must lie within the normal float range (1.2e-38 .. 3.4e38), as every hydraulic
+// quantity it is given does.  Measured on the device, with every other helper here: tests/test_gpu_device_helpers.py
 __device__ __forceinline__ double rcbrt_pos(double x) {
   const float xf = (float)x;
   const double y = (double)__builtin_amdgcn_exp2f(__builtin_amdgcn_logf(xf) * (-1.0f / 3.0f));

@@ -2,7 +2,7 @@
 the same operations (tools/micro/pow_model.c: fma() for every device fma, the reciprocal seed's error put in by hand) against powl()
 on a random grid of 4e6 points, x in 1e-4 .. 1e4, b in 0.2 .. 5: no worse than libm's exp(b log x) on the same grid, log(x) to
 4e-16 also next to 1.  (The device function itself runs in every parity test with a power rating curve: c5_512, the instantiation
-and random sweeps.)"""
+and random sweeps; tests/test_gpu_device_helpers.py checks log_pos, exp_short and pow_pos directly, on the device, against long double.)"""
 import os
 import re
 import subprocess
