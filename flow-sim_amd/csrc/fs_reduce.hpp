@@ -125,11 +125,15 @@ template <typename V, typename T> FS_RED_HD double mean_square_series(int n_q, V
 }
 
 // numpy's default quantile (method "linear") between the two order statistics a <= b around the virtual index, gamma in [0, 1)
-// (numpy/lib/_function_base_impl.py: _lerp), kept inside [a, b]
+// (numpy/lib/_function_base_impl.py: _lerp), kept inside [a, b].  A virtual index that is an integer (gamma == 0) and two equal order
+// statistics ARE the order statistic a: nothing is computed, so that an infinite member gives that infinity where numpy's inf - inf
+// and inf * 0 give NaN (finite members: the same bits as the arithmetic, a + d * 0 and a + 0 * gamma).  An interpolation between an
+// infinite and a finite member stays numpy's.
 FS_RED_HD double quantile_lerp(double a, double b, double gamma) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
+  if (gamma == 0.0 || a == b) return a;
   const double d = b - a;
   double v = gamma >= 0.5 ? b - d * (1.0 - gamma) : a + d * gamma;
   if (v < a) v = a;

@@ -1,6 +1,7 @@
-"""ctypes front of tests/device_probe/libfs_probe.so (probe.hip: thin kernels around the __device__ functions of fs_device.hpp; built by
-`make -C flow-sim_amd/csrc probe`, which __graft_entry__.build() runs).  TEST INFRASTRUCTURE: the product never loads it.  Arrays go
-in and come out as numpy arrays of the device type (float64 / float32); a HIP error raises."""
+"""ctypes front of tests/device_probe/libfs_probe.so (probe.hip: thin kernels around the __device__ functions of fs_device.hpp;
+probe_reduce.hip: the launchers of the post-processing kernels of fs_reduce.hpp / fs_envelope.hpp, linked with the library's own
+objects; built by `make -C flow-sim_amd/csrc probe`, which __graft_entry__.build() runs).  TEST INFRASTRUCTURE: the product never
+loads it.  Arrays go in and come out as numpy arrays of the device type (float64 / float32); a HIP error raises."""
 import ctypes
 import os
 
@@ -119,3 +120,77 @@ def bc(form, kind, params, sec, level, dt, h, Q, Qold, Yprev, tgt):
     flag = np.full(len(h), -1, dtype=np.int32)
     _call("fsp_bc", arrays[0], form, kind, p, HR.sec_array(sec, D), level, D(dt), *arrays, out, flag, len(h))
     return dict(res=out[0], dh=out[1], dq=out[2], Ynew=out[3], flag=flag)
+
+
+# ---- probe_reduce.hip: the launchers of the post-processing kernels on arrays of the caller's choice ---------------------------
+def _ptr(a, dtype):
+    if a is None:
+        return None
+    assert isinstance(a, np.ndarray) and a.flags["C_CONTIGUOUS"] and a.dtype == dtype, (a.dtype, dtype)
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _run(name, *args):
+    """args: (array or None, dtype) pairs go as pointers, Python ints as int"""
+    l = lib()
+    fn = getattr(l, name)
+    fn.restype = ctypes.c_int
+    e = fn(*[_ptr(*a) if isinstance(a, tuple) else ctypes.c_int(int(a)) for a in args])
+    if e != 0:
+        raise RuntimeError(f"{name}: HIP error {e}: {l.fsp_error_string(e).decode()}")
+
+
+F64, I32 = np.dtype(np.float64), np.dtype(np.int32)
+
+
+def _block(hydro, status, iters, level, first, n):
+    """hydro[levels][4][B] in the device type, status[B], iters[levels][B]; rows 0 .. level exist, the range is [first, first + n)"""
+    levels, four, B = hydro.shape
+    assert four == 4 and status.shape == (B,) and iters.shape == (levels, B) and 0 <= first and n >= 1 and first + n <= level + 1 <= levels
+    return [(hydro, hydro.dtype), (status, I32), (iters, I32), B, levels, level, first, n]
+
+
+def bands(hydro, status, iters, level, first, n, q):
+    """fs::launch_bands: min, max, mean, std [n][4][4], quantiles [n][4][n_q], n_members [n]"""
+    q = np.ascontiguousarray(q, dtype=np.float64)
+    mom, qu, nm = np.full((n, 4, 4), -7.0), np.full((n, 4, len(q)), -7.0), np.full(n, -7, dtype=np.int32)
+    _run(f"fsp_bands_{_suffix(hydro)}", *_block(hydro, status, iters, level, first, n), (q if len(q) else None, F64), len(q), (mom, F64),
+         (qu if len(q) else None, F64), (nm, I32))
+    return dict(moments=mom, quantiles=qu, n_members=nm)
+
+
+def profile_bands(x, count, status, levels, reach_nodes, q):
+    """fs::launch_profile_bands on x[N][B]: moments [N][4], quantiles [N][n_q], exceed [N], n_members [N]"""
+    N, B = x.shape
+    q = np.ascontiguousarray(q, dtype=np.float64)
+    assert status.shape == (B,) and levels.shape == (B,) and (count is None or count.shape == (N, B)) and (reach_nodes is None or reach_nodes.shape == (B,))
+    mom, qu, ex, nm = np.full((N, 4), -7.0), np.full((N, len(q)), -7.0), np.full(N, -7.0), np.full(N, -7, dtype=np.int32)
+    _run("fsp_profile_bands", (x, F64), (count, F64), (status, I32), (levels, I32), (reach_nodes, I32), B, N, (q if len(q) else None, F64), len(q),
+         (mom, F64), (qu if len(q) else None, F64), (ex if count is not None else None, F64), (nm, I32))
+    return dict(moments=mom, quantiles=qu, exceed=ex if count is not None else None, n_members=nm)
+
+
+def transpose_rows(rows):
+    """fs::launch_transpose_rows: one or two [B][N] rows -> [z][N][B]"""
+    B, N = rows[0].shape
+    assert 1 <= len(rows) <= 2 and all(r.shape == (B, N) for r in rows)
+    out = np.full((len(rows), N, B), -7.0)
+    _run("fsp_transpose_rows", (rows[0], F64), (rows[1] if len(rows) == 2 else None, F64), len(rows), B, N, (out, F64))
+    return out
+
+
+def summarize(hydro, status, iters, level, first, n):
+    """fs::launch_summarize: out[FS_SUM_NROWS][B] (row 0: the rows of the range each reach completed)"""
+    out = np.full((14, hydro.shape[2]), -7.0)
+    _run(f"fsp_summarize_{_suffix(hydro)}", *_block(hydro, status, iters, level, first, n), (out, F64))
+    return out
+
+
+def lookup(hydro, status, iters, level, first, n, x_row, y_row, xq, y_offset=None, target=None):
+    """fs::launch_lookup: values [n_q][B], rmse [B] (with a target), info [B] (bit 0: the abscissae descend somewhere)"""
+    B = hydro.shape[2]
+    xq = np.ascontiguousarray(xq, dtype=np.float64)
+    val, rm, info = np.full((len(xq), B), -7.0), np.full(B, -7.0), np.full(B, -7, dtype=np.int32)
+    _run(f"fsp_lookup_{_suffix(hydro)}", *_block(hydro, status, iters, level, first, n), x_row, y_row, (y_offset, F64), (xq, F64), len(xq),
+         (target, F64), (val, F64), (rm if target is not None else None, F64), (info, I32))
+    return dict(values=val, rmse=rm if target is not None else None, info=info)

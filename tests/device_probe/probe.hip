@@ -11,9 +11,12 @@
 #include <type_traits>
 #include <vector>
 #include "../../flow-sim_amd/csrc/fs_device.hpp"
+#include "probe_call.hpp"
 
 namespace {
 using namespace fs;
+using fsp::Call;
+using fsp::kBadArg;
 
 constexpr int kBlock = 256;
 
@@ -146,39 +149,7 @@ __global__ void k_bc(int form, int kind, const R *params, const R *sec, int leve
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
-// device buffers of one wrapper call; the first failing HIP call is kept and every later step is skipped
-struct Call {
-  hipError_t err = hipSuccess;
-  std::vector<void *> bufs;
-  struct Back { void *host; void *dev; size_t bytes; };
-  std::vector<Back> backs;
-  bool ok() const { return err == hipSuccess; }
-  void check(hipError_t e) { if (err == hipSuccess && e != hipSuccess) err = e; }
-  void *alloc(size_t bytes) {
-    void *d = nullptr;
-    if (ok()) { check(hipMalloc(&d, bytes ? bytes : 1)); if (ok()) bufs.push_back(d); else d = nullptr; }
-    return d;
-  }
-  template <typename T> const T *in(const T *host, size_t count) {
-    void *d = alloc(count * sizeof(T));
-    if (ok() && count) check(hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice));
-    return (const T *)d;
-  }
-  template <typename T> T *out(T *host, size_t count) {
-    void *d = alloc(count * sizeof(T));
-    if (ok()) { check(hipMemset(d, 0, count * sizeof(T))); backs.push_back({host, d, count * sizeof(T)}); }
-    return (T *)d;
-  }
-  int finish() {
-    if (ok()) check(hipGetLastError());
-    if (ok()) check(hipDeviceSynchronize());
-    for (const Back &b : backs) if (ok() && b.bytes) check(hipMemcpy(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost));
-    for (void *d : bufs) check(hipFree(d));
-    return (int)err;
-  }
-};
 inline dim3 grid_for(int n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
-constexpr int kBadArg = (int)hipErrorInvalidValue;
 
 template <typename R> int unary(int op, const R *x, R *y, int n) {
   if (n <= 0 || op < 0 || op >= OP_COUNT || (!std::is_same<R, double>::value && op >= OP_LOG)) return kBadArg;

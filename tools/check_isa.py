@@ -31,6 +31,8 @@ def run(*cmd):
 
 def check_object(obj, tmp):
     bundle, co = os.path.join(tmp, "f.bundle"), os.path.join(tmp, "f.co")
+    if ".hip_fatbin" not in run(f"{LLVM}/llvm-readelf", "-S", "--wide", obj):
+        return 0, []          # host code only (a source that launches other objects' kernels): no code object, nothing to call
     run(f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={bundle}", obj, os.path.join(tmp, "copy.o"))      # (no output name: objcopy rewrites its input)
     run(f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--targets={TARGET}", f"--input={bundle}", f"--output={co}")
     problems = []
