@@ -21,6 +21,7 @@
 #include <thread>
 #include <vector>
 
+#include "fs_balance.hpp"
 #include "fs_buffer.hpp"
 #include "fs_entries.hpp"
 #include "fs_envelope.hpp"
@@ -46,13 +47,18 @@ struct TraceRange {
 FS_ACTIVE_LIST(FS_DECLARE)
 #else
 // an experiment build is this translation unit alone, with a few step kernels: it has no initial-condition kernels (fs_part_init.hip)
-// no post-processing kernels (fs_part_reduce.hip, fs_part_envelope.hip), no forcing kernels (fs_part_forcing.hip) and no geometry kernels
+// no post-processing kernels (fs_part_reduce.hip, fs_part_envelope.hip, fs_part_balance.hip), no forcing kernels (fs_part_forcing.hip) and no geometry kernels
 // (fs_part_geometry.hip), and fs_batch_init_state, fs_batch_summarize, fs_batch_set_bc_sampled ... say so
 namespace fs {
 bool launch_envelope(const EnvelopeArgs<double> &, int, hipStream_t) { return false; }
 bool launch_envelope(const EnvelopeArgs<float> &, int, hipStream_t) { return false; }
 bool launch_transpose_rows(const TransposeRows &, int, double *, int, int, hipStream_t) { return false; }
 bool launch_profile_bands(const ProfileBandArgs &, hipStream_t) { return false; }
+bool launch_reach_integrals(const IntegralArgs<double> &, hipStream_t) { return false; }
+bool launch_reach_integrals(const IntegralArgs<float> &, hipStream_t) { return false; }
+bool launch_balance(const ReduceArgs<double> &, const BalanceArgs &, hipStream_t) { return false; }
+bool launch_balance(const ReduceArgs<float> &, const BalanceArgs &, hipStream_t) { return false; }
+bool launch_clear_integrals(double *, size_t, int32_t *, size_t, hipStream_t) { return false; }
 bool launch_member_sections(const MemberGeoArgs &, hipStream_t) { return false; }
 bool launch_member_tables(const MemberGeoArgs &, hipStream_t) { return false; }
 bool launch_sample_target(const SampleArgs<double> &, hipStream_t) { return false; }
@@ -257,6 +263,11 @@ struct fs_batch : Timeline {
   fs::DeviceBuffer env_levels;          // int32 [B]: the rows of each reach that entered it
   fs::DeviceBuffer env_thr;             // the threshold it was handed, in the batch's type: [N] or [B][N]
   fs::DeviceBuffer env_t;               // double [2][N][B]: fs_batch_profile_bands' transposed row and crossing counts
+  fs::DeviceBuffer integ;               // double [max_levels][FS_INT_NROWS][B]: reach integrals and balance residuals, NaN where never evaluated (allocated on first use)
+  fs::DeviceBuffer integ_mark;          // int32 [max_levels][B]: 1 where a row of integ holds integrals
+  fs::DeviceBuffer integ_thr;           // the threshold fs_batch_reach_integrals was handed, in the batch's type: [N] or [B][N]
+  fs::DeviceBuffer bal_scheme;          // double [3][B]: theta, dt, dx of each reach as the caller gave them in fp64 (rs_host, else the batch's)
+  bool bal_scheme_stale = true;         // the scheme changed since bal_scheme was uploaded
   int env_quantities = 0;               // FS_ENV_* mask of the envelope the handle holds (0: none)
   bool env_crossings = false;           // ... and whether it has crossing rows
   fs::DeviceBuffer frc_in[2][6];        // double / int32: what fs_batch_set_bc_sampled was handed per side (times, values, table_of, scale, offset, shift)
@@ -610,6 +621,10 @@ int begin_at_level0(fs_batch *b) {
   HIP_TRY(hipMemsetAsync(b->Yprev.get(), 0, B * b->esz, b->stream));
   if (b->trace) HIP_TRY(hipMemsetAsync(b->trace.get(), 0, L * FS_TRACE_CAP * B * b->esz, b->stream));
   HIP_TRY(hipMemsetAsync(b->it_done.get(), 0, B * 4, b->stream));
+  if (b->integ) {      // no row holds integrals of the new run
+    fs::launch_clear_integrals(b->integ.get<double>(), L * FS_INT_NROWS * B, b->integ_mark.get<int32_t>(), L * B, b->stream);
+    HIP_TRY(hipGetLastError());
+  }
   b->level = 0; b->iterating = false; b->restart_level = 0;
   b->have_state = true;
   return 0;
@@ -757,7 +772,7 @@ int fs_batch_set_scheme(fs_batch *b, double theta, double dt, double dx, double 
   if (!b) return fail("null handle");
   if (!(dt > 0) || !(dx > 0) || !(tolerance > 0) || max_iter < 1) return fail("fs_batch_set_scheme: dt, dx, tolerance > 0 and max_iter >= 1 required");
   b->theta = theta; b->dt = dt; b->dx = dx; b->tol = tolerance; b->max_iter = max_iter;
-  b->have_scheme = true;
+  b->have_scheme = true; b->bal_scheme_stale = true;
   if (b->reach_scheme) {      // per-reach values stand; the rows the caller left to the batch take the new numbers
     FS_ON_DEVICE(b);
     return rebuild_reach_scheme(b);
@@ -975,6 +990,7 @@ int fs_batch_set_reach_scheme(fs_batch *b, const double *theta, const double *dt
   for (int i = 0; i < 3; ++i) {
     if (src[i]) b->rs_host[i].assign(src[i], src[i] + B); else b->rs_host[i].clear();
   }
+  b->bal_scheme_stale = true;
   return rebuild_reach_scheme(b);
 }
 
@@ -1713,6 +1729,144 @@ int fs_batch_profile_bands(fs_batch *b, int32_t quantity, int32_t stat, const do
   if (want_q && fetch(b, quantiles, p.quantiles, n_qu * sizeof(double))) return -1;
   if (exceed && fetch(b, exceed, p.exceed, (size_t)N * sizeof(double))) return -1;
   if (n_members && fetch(b, n_members, p.n_members, (size_t)N * sizeof(int32_t))) return -1;
+  return 0;
+}
+
+// ---- reach integrals and the water balance (fs_balance.hpp) ----
+
+// the handle's integral block and its marks exist (first use: every row NaN), and the fp64 scheme of every reach is on the device
+static int ready_integrals(fs_batch *b, const char *entry) {
+  const size_t B = b->d.n_reaches, L = b->d.max_levels;
+  if (!b->integ) {
+    HIP_TRY(b->integ.ensure(L * FS_INT_NROWS * B * sizeof(double)));
+    HIP_TRY(b->integ_mark.ensure(L * B * sizeof(int32_t)));
+    if (!fs::launch_clear_integrals(b->integ.get<double>(), L * FS_INT_NROWS * B, b->integ_mark.get<int32_t>(), L * B, b->stream)) {
+      b->integ.reset(); b->integ_mark.reset();
+      return fail(std::string(entry) + kNoReduceKernels);
+    }
+    HIP_TRY(hipGetLastError());
+  }
+  if (b->bal_scheme_stale || !b->bal_scheme) {
+    const double wide[3] = {b->theta, b->dt, b->dx};
+    std::vector<double> v(3 * B);
+    for (int i = 0; i < 3; ++i)
+      for (size_t r = 0; r < B; ++r) v[(size_t)i * B + r] = b->rs_host[i].empty() ? wide[i] : b->rs_host[i][r];
+    HIP_TRY(hipStreamSynchronize(b->stream));      // an earlier call's kernels are through with the values before
+    if (upload_f64(b->bal_scheme, v.data(), v.size())) return -1;
+    b->bal_scheme_stale = false;
+  }
+  return 0;
+}
+
+int fs_batch_reach_integrals(fs_batch *b, int32_t first, int32_t n, const double *threshold, int32_t threshold_per_reach) {
+  if (!b) return fail("fs_batch_reach_integrals: null handle");
+  if (!b->have_scheme || !b->have_geo) return fail("fs_batch_reach_integrals: the scheme (fs_batch_set_scheme: dx) and the geometry must be set first");
+  const bool current = first == -1;
+  if (current) {
+    if (n != 1) return fail("fs_batch_reach_integrals: first = -1 evaluates the current state, one row: n must be 1");
+    if (!b->have_state) return fail("fs_batch_reach_integrals: no state yet");
+    if (b->iterating) return fail("fs_batch_reach_integrals: a level opened with fs_batch_iterate must be closed first");
+  } else {
+    if (!b->hist_h) return fail("fs_batch_reach_integrals: batch was created without FS_FLAG_HISTORY (first = -1 evaluates the current state)");
+    if (check_reduce_range(b, "fs_batch_reach_integrals", first, n)) return -1;
+  }
+  FS_ON_DEVICE(b);
+  TraceRange range_("flowsim:balance");
+  const size_t B = b->d.n_reaches, BN = B * b->d.n_nodes;
+  if (ready_integrals(b, "fs_batch_reach_integrals")) return -1;
+  if (threshold) {
+    HIP_TRY(hipStreamSynchronize(b->stream));             // an earlier call's kernels are through with the threshold
+    if (upload(b, b->integ_thr, threshold, threshold_per_reach ? BN : (size_t)b->d.n_nodes)) return -1;
+  }
+  const int32_t row0 = current ? b->level : first;
+  HIP_TRY(hipEventRecord(b->ev0, b->stream));      // fs_batch_last_step_ms() then reports this kernel
+  const bool launched = with_real(b, [&](auto real) {
+    using R = decltype(real);
+    fs::IntegralArgs<R> a{b->d.n_reaches, b->d.n_nodes, b->d.section_mode,
+                          current ? b->hk.get<const R>() : b->hist_h.get<const R>() + (size_t)first * BN, current ? (int64_t)0 : (int64_t)BN,
+                          b->geo_uniform.get<const R>(), b->geo_table.get<const R>(), b->poly_x.get<const R>(), b->poly_z.get<const R>(),
+                          b->poly_n.get<const int32_t>(), (int64_t)b->geo_reach_stride, (int64_t)b->poly_reach_stride,
+                          b->reach_nodes.get<const int32_t>(), reduce_args<R>(b, row0, n), b->bal_scheme.get<const double>() + 2 * B,
+                          threshold ? b->integ_thr.get<const R>() : nullptr, threshold_per_reach ? 1 : 0, b->integ.get<double>(),
+                          b->integ_mark.get<int32_t>()};
+    return fs::launch_reach_integrals(a, b->stream);
+  });
+  if (!launched) return fail(std::string("fs_batch_reach_integrals") + kNoReduceKernels);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(b->ev1, b->stream));
+  b->timed = true; b->launches = 1;
+  return 0;
+}
+
+int fs_batch_water_balance(fs_batch *b, int32_t first, int32_t n, double *totals) {
+  if (!b) return fail("fs_batch_water_balance: null handle");
+  if (!b->have_scheme) return fail("fs_batch_water_balance: the scheme (fs_batch_set_scheme: theta, dt) must be set first");
+  if (check_reduce_range(b, "fs_batch_water_balance", first, n)) return -1;
+  FS_ON_DEVICE(b);
+  TraceRange range_("flowsim:balance");
+  const size_t B = b->d.n_reaches, bytes = (size_t)FS_BAL_NROWS * B * sizeof(double);
+  if (ready_integrals(b, "fs_batch_water_balance")) return -1;
+  if (totals) HIP_TRY(b->red_out[0].reserve(bytes));
+  fs::BalanceArgs p{b->integ.get<double>(), b->integ_mark.get<const int32_t>(), b->bal_scheme.get<const double>(),
+                    b->bal_scheme.get<const double>() + B, totals ? b->red_out[0].get<double>() : nullptr};
+  HIP_TRY(hipEventRecord(b->ev0, b->stream));
+  const bool launched = with_real(b, [&](auto real) {
+    using R = decltype(real);
+    return fs::launch_balance(reduce_args<R>(b, first, n), p, b->stream);
+  });
+  if (!launched) return fail(std::string("fs_batch_water_balance") + kNoReduceKernels);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(b->ev1, b->stream));
+  b->timed = true; b->launches = 1;
+  return totals ? fetch(b, totals, p.totals, bytes) : 0;
+}
+
+int fs_batch_get_reach_integrals(fs_batch *b, int32_t first, int32_t n, double *out) {
+  if (!b || !out) return fail("fs_batch_get_reach_integrals: null argument");
+  if (check_levels(b, "fs_batch_get_reach_integrals", first, n)) return -1;
+  FS_ON_DEVICE(b);
+  if (ready_integrals(b, "fs_batch_get_reach_integrals")) return -1;
+  const size_t B = b->d.n_reaches;
+  return fetch(b, out, b->integ.get<double>() + (size_t)first * FS_INT_NROWS * B, (size_t)n * FS_INT_NROWS * B * sizeof(double));
+}
+
+void *fs_batch_reach_integrals_device_ptr(fs_batch *b) { return b ? b->integ.get() : nullptr; }
+
+int fs_batch_integral_bands(fs_batch *b, int32_t first, int32_t n, const double *q, int32_t n_q, double *moments, double *quantiles,
+                            int32_t *n_members) {
+  if (!b) return fail("fs_batch_integral_bands: null handle");
+  if (!moments && !quantiles && !n_members) return fail("fs_batch_integral_bands: no output requested (moments, quantiles and n_members are all NULL)");
+  if (n_q < 0 || n_q > fs::kBandMaxQ) return fail("fs_batch_integral_bands: n_q must be 0 .. " + std::to_string(fs::kBandMaxQ));
+  if (n_q > 0 && !q) return fail("fs_batch_integral_bands: null quantile levels");
+  for (int i = 0; i < n_q; ++i)
+    if (!(q[i] >= 0.0 && q[i] <= 1.0)) return fail("fs_batch_integral_bands: quantile levels must be in [0, 1]");
+  if (check_reduce_range(b, "fs_batch_integral_bands", first, n)) return -1;
+  FS_ON_DEVICE(b);
+  TraceRange range_("flowsim:reduce");
+  if (ready_integrals(b, "fs_batch_integral_bands")) return -1;
+  const bool want_q = quantiles && n_q > 0;
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  if (want_q && upload_f64(b->red_in[1], q, (size_t)n_q)) return -1;
+  // moments [n][4][4], then quantiles [n][4][n_q], then n_members [n]
+  static_assert(FS_INT_NROWS == 4, "bands_kernel walks the four rows of a level of the hydrograph block");
+  const size_t n_mom = (size_t)n * 16, n_qu = want_q ? (size_t)n * 4 * n_q : 0;
+  HIP_TRY(b->red_out[2].reserve((n_mom + n_qu) * sizeof(double) + (size_t)n * sizeof(int32_t)));
+  double *d_mom = b->red_out[2].get<double>();
+  fs::BandArgs p;
+  p.q = want_q ? b->red_in[1].get<const double>() : nullptr; p.n_q = want_q ? n_q : 0;
+  p.moments = moments ? d_mom : nullptr; p.quantiles = want_q ? d_mom + n_mom : nullptr;
+  p.n_members = n_members ? (int32_t *)(d_mom + n_mom + n_qu) : nullptr;
+  // the block has the hydrograph block's shape: the shipped bands_kernel on a ReduceArgs<double> that points at it
+  const fs::ReduceArgs<double> a{b->integ.get<const double>(), b->status.get<const int32_t>(), b->iters.get<const int32_t>(), b->d.n_reaches,
+                                 b->level, first, n};
+  HIP_TRY(hipEventRecord(b->ev0, b->stream));
+  if (!fs::launch_bands(a, p, b->stream)) return fail(std::string("fs_batch_integral_bands") + kNoReduceKernels);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(b->ev1, b->stream));
+  b->timed = true; b->launches = 1;
+  if (moments && fetch(b, moments, p.moments, n_mom * sizeof(double))) return -1;
+  if (want_q && fetch(b, quantiles, p.quantiles, n_qu * sizeof(double))) return -1;
+  if (n_members && fetch(b, n_members, p.n_members, (size_t)n * sizeof(int32_t))) return -1;
   return 0;
 }
 

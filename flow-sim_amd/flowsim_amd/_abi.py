@@ -44,6 +44,9 @@ ENV_ALL = 63
 ENV_CROSSING = 64
 ENV_STATS = ("max", "max_level", "min", "min_level")
 ENV_CROSS_ROWS = ("first", "last", "count")
+# fs_batch_reach_integrals: the rows of a level of the integral block (FS_INT_VOLUME ..); fs_batch_water_balance: its totals (FS_BAL_SPANS ..)
+INT_ROWS = ("volume", "surface", "length_over", "balance")
+BAL_ROWS = ("spans", "first_level", "last_level", "storage_change", "net_inflow", "inflow", "residual", "worst", "worst_level", "relative")
 ABI_VERSION = 3
 
 
@@ -113,6 +116,11 @@ SIGNATURES = {
     "fs_batch_envelope_device": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _D, C.c_int32, C.c_int32]),
     "fs_batch_envelope_device_ptr": (_P, [_P, C.c_int32]),
     "fs_batch_profile_bands": (C.c_int, [_P, C.c_int32, C.c_int32, _D, C.c_int32, _D, _D, _D, _I]),
+    "fs_batch_reach_integrals": (C.c_int, [_P, C.c_int32, C.c_int32, _D, C.c_int32]),
+    "fs_batch_water_balance": (C.c_int, [_P, C.c_int32, C.c_int32, _D]),
+    "fs_batch_get_reach_integrals": (C.c_int, [_P, C.c_int32, C.c_int32, _D]),
+    "fs_batch_reach_integrals_device_ptr": (_P, [_P]),
+    "fs_batch_integral_bands": (C.c_int, [_P, C.c_int32, C.c_int32, _D, C.c_int32, _D, _D, _I]),
     "fs_batch_hydrograph_device_ptr": (_P, [_P]),
     "fs_batch_stream": (_P, [_P]),
     "fs_batch_last_step_ms": (C.c_double, [_P]),

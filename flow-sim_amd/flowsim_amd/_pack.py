@@ -345,3 +345,36 @@ def quantile_levels(quantiles):
     if np.any(~((q >= 0.0) & (q <= 1.0))):
         raise ValueError("quantile levels must be in [0, 1]")
     return q
+
+
+# -- reach integrals and the water balance ---------------------------------------------------------
+def integral_range(first, n, level, current):
+    """(first, n) of fs_batch_reach_integrals: the levels [first, first + n) of the history (n None: up to `level`, the batch's
+    current one), or (-1, 1) - the current state into the row of the current level - with current=True, which takes no range"""
+    if current:
+        if first != 0 or n is not None:
+            raise ValueError("current=True evaluates the current state into the row of the current level: it takes no first / n")
+        return -1, 1
+    first = int(first)
+    n = level - first + 1 if n is None else int(n)
+    if first < 0 or n < 1:
+        raise ValueError(f"levels [{first}, {first + n}) are no range of levels")
+    return first, n
+
+
+def balance_options(balance):
+    """(every, threshold, quantiles) of the runners' balance= keyword: dict(every=1, threshold=None, quantiles=(0.05, 0.5, 0.95))"""
+    unknown = set(balance) - {"every", "threshold", "quantiles"}
+    if unknown:
+        raise ValueError(f"balance: unknown keys {sorted(unknown)}")
+    every = balance.get("every", 1)
+    if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or every < 1:
+        raise ValueError(f"balance: every must be an integer >= 1, not {every!r}")
+    return int(every), balance.get("threshold"), quantile_levels(balance.get("quantiles", (0.05, 0.5, 0.95)))
+
+
+def balance_chunks(n_steps, every):
+    """the step counts between two marks of a batch without history: `every` levels each, the last chunk what is left"""
+    if n_steps < 0 or every < 1:
+        raise ValueError("balance_chunks: n_steps >= 0 and every >= 1 required")
+    return [every] * (n_steps // every) + ([n_steps % every] if n_steps % every else [])

@@ -449,6 +449,53 @@ class PreissmannBatch:
                                                  _opt(qu if len(q) else None), _opt(exceed), _iptr(cnt)), "profile_bands")
         return dict(min=mom[:, 0], max=mom[:, 1], mean=mom[:, 2], std=mom[:, 3], quantiles=qu, exceed=exceed, n_members=cnt)
 
+    # -- reach storage and the discrete water balance (reduced along the reach, where the state is) --------
+    def reach_integrals(self, first=0, n=None, threshold=None, current=False):
+        """Per (level, reach): the trapezoid-rule volume [m^3] and water surface [m^2] of the node areas and top widths, and the
+        length [m] of reach whose stage is at or above `threshold` (scalar, [N] or [B, N]; NaN entries are not assessed; None: the
+        row is NaN).  Fills the rows [first, first + n) of the batch's integral block from the stored history (needs history=True)
+        and returns dict name -> [n, B] with the names of _abi.INT_ROWS ('balance' is NaN until water_balance()).  current=True
+        evaluates the current state into the row of the current level instead - no history needed, no wait for the device: a batch
+        without history is marked now and then between two step(..., sync=False) calls - and returns None."""
+        first, n = P.integral_range(first, n, self.level, current)
+        thr, per_reach = P.envelope_threshold(threshold, self.B, self.N)
+        A.check(self._lib.fs_batch_reach_integrals(self._h, first, n, _opt(thr), per_reach), "reach_integrals")
+        return None if current else self.integral_rows(first, n)
+
+    def integral_rows(self, first=0, n=None):
+        """the rows [first, first + n) of the integral block as they stand: dict name -> [n, B]; NaN where never evaluated"""
+        n = self._span(first, n)
+        out = np.empty((n, len(A.INT_ROWS), self.B))
+        A.check(self._lib.fs_batch_get_reach_integrals(self._h, int(first), int(n), _dptr(out)), "get_reach_integrals")
+        return {k: out[:, i] for i, k in enumerate(A.INT_ROWS)}
+
+    def water_balance(self, first=0, n=None):
+        """The discrete water balance over the levels [first, first + n), from each evaluated row of the integral block to the next
+        (a span): storage change minus the net inflow volume of the Preissmann continuity row, which the scheme closes to its Newton
+        tolerance.  Returns (rows, totals): rows as integral_rows() with 'balance' filled at every span's end level (0 at the first
+        evaluated row), totals dict name -> [B] with the names of _abi.BAL_ROWS (levels relative to `first`)."""
+        n = self._span(first, n)
+        tot = np.empty((len(A.BAL_ROWS), self.B))
+        A.check(self._lib.fs_batch_water_balance(self._h, int(first), int(n), _dptr(tot)), "water_balance")
+        return self.integral_rows(first, n), {k: tot[i] for i, k in enumerate(A.BAL_ROWS)}
+
+    def integral_bands(self, quantiles=(0.05, 0.5, 0.95), first=0, n=None):
+        """bands() on the integral block: across the members, per level and row of _abi.INT_ROWS, dict(min, max, mean, std [n, 4],
+        quantiles [n, 4, n_q], n_members [n]).  Failed members are left out; a level that a remaining member has not evaluated
+        is NaN."""
+        n = self._span(first, n)
+        q = P.quantile_levels(quantiles)
+        mom = np.empty((n, 4, 4))
+        qu = np.empty((n, 4, len(q)))
+        cnt = np.empty(n, dtype=np.int32)
+        A.check(self._lib.fs_batch_integral_bands(self._h, int(first), int(n), _opt(q if len(q) else None), len(q), _dptr(mom),
+                                                  _opt(qu if len(q) else None), _iptr(cnt)), "integral_bands")
+        return dict(min=mom[:, :, 0], max=mom[:, :, 1], mean=mom[:, :, 2], std=mom[:, :, 3], quantiles=qu, n_members=cnt)
+
+    def reach_integrals_device_ptr(self):
+        """device pointer to the integral block [max_levels, 4, B] float64 (None before the first evaluation)"""
+        return self._lib.fs_batch_reach_integrals_device_ptr(self._h)
+
     def last_step_ms(self):
         return self._lib.fs_batch_last_step_ms(self._h)
 

@@ -4,6 +4,7 @@ time, cases/gerd_roseires/n_calibrate.py:55-67 -> model.run(n_main=...))."""
 import numpy as np
 
 from . import _abi as A
+from . import _pack as P
 from .batch import BoundarySpec, PreissmannBatch
 from .hydromodel.preissmann import boundary_to_spec
 
@@ -19,8 +20,31 @@ def _add_envelope(out, b, envelope, nt):
                             for name in env if name not in ("levels", "crossing")}
 
 
+def _step(b, n_steps, balance, history):
+    """the runners' time loop: one launch; with balance= on a batch WITHOUT history, chunks of `every` levels with the state marked
+    (PreissmannBatch.reach_integrals(current=True)) before the first and after each - stream-ordered, the host does not wait"""
+    if balance is None or history:
+        b.step(n_steps)
+        return
+    every, threshold, _ = P.balance_options(balance)
+    b.reach_integrals(threshold=threshold, current=True)
+    for chunk in P.balance_chunks(n_steps, every):
+        b.step(chunk, sync=False)
+        b.reach_integrals(threshold=threshold, current=True)
+    b.sync()
+
+
+def _add_balance(out, b, balance, nt, history):
+    """out['balance'] of the runners' balance= keyword: dict(rows, totals, bands)"""
+    _, threshold, quantiles = P.balance_options(balance)
+    if history:
+        b.reach_integrals(0, nt, threshold=threshold)
+    rows, totals = b.water_balance(0, nt)
+    out["balance"] = dict(rows=rows, totals=totals, bands=b.integral_bands(quantiles, 0, nt))
+
+
 def run_manning_ensemble(solver, n_main_values, tolerance=1e-4, max_iter=100, dtype="f64", device=0, monitor=True, initial="host",
-                         summaries=False, score=None, bands=None, hydrographs=True, envelope=None):
+                         summaries=False, score=None, bands=None, hydrographs=True, envelope=None, balance=None):
     """`solver`: a set-up (not yet run) PreissmannSolver whose channel provides geometry, boundaries
     and initial conditions; the initial conditions are shared by all members (the reference's
     members start from the same downstream level and the same flow; their GVF profiles differ
@@ -42,6 +66,13 @@ def run_manning_ensemble(solver, n_main_values, tolerance=1e-4, max_iter=100, dt
     cost: the batch is created with history=True, which selects the step kernels compiled with diagnostics and holds the whole
     history, 2 * levels * B * N values, on the device.  With envelope=None nothing changes.
 
+    Storage and mass balance: balance=dict(every=1, threshold=None, quantiles=(0.05, 0.5, 0.95)) adds 'balance' = dict(rows: per
+    level and member the stored volume, the water surface, the length of reach at or above the stage `threshold` and the residual
+    of the discrete water balance (PreissmannBatch.reach_integrals / water_balance), totals: per member, bands: integral_bands
+    across the members).  With a history (envelope=) the whole range is reduced after the run; without one the run is stepped in
+    chunks of `every` levels and the state is marked after each, so that the balance closes over each chunk and the rows between
+    two marks are NaN.  With balance=None nothing changes.
+
     Returns dict(hydrographs[nt, 4, B], iterations[nt, B], status[B]) and what the keywords above add."""
     if initial not in ("host", "gvf"):
         raise ValueError("initial must be 'host' or 'gvf'")
@@ -60,7 +91,7 @@ def run_manning_ensemble(solver, n_main_values, tolerance=1e-4, max_iter=100, dt
             b.set_state(ch.initial_conditions[:, 0], ch.initial_conditions[:, 1])
         else:
             b.set_state(ics[:, :, 0], ics[:, :, 1])
-        b.step(nt - 1)
+        _step(b, nt - 1, balance, envelope is not None)
         out = dict(iterations=b.iterations(0, nt), status=b.status())
         if hydrographs:
             out = dict(hydrographs=b.hydrographs(0, nt), **out)
@@ -73,12 +104,14 @@ def run_manning_ensemble(solver, n_main_values, tolerance=1e-4, max_iter=100, dt
             out["bands"] = b.bands(bands, 0, nt)
         if envelope is not None:
             _add_envelope(out, b, envelope, nt)
+        if balance is not None:
+            _add_balance(out, b, balance, nt, envelope is not None)
         return out
 
 
 def run_scenario_ensemble(solver, pool, inflow_table, inflow_scale=None, inflow_shift=None, pool_level=None, weir_scale=None, n_main=None,
                           initial="gvf", tolerance=1e-4, max_iter=100, dtype="f64", device=0, monitor=True, summaries=False, score=None,
-                          bands=None, hydrographs=True, envelope=None):
+                          bands=None, hydrographs=True, envelope=None, balance=None):
     """Scenario ensembles: members that differ in what the reach is forced with - the inflow into the reservoir upstream of it
     (`inflow_table` [K, 2], time [s] and flow, per member multiplied by inflow_scale and delayed by inflow_shift [s]), the pool
     level the reservoir starts from (pool_level, required; it is also the member's hold level), the outlets in service (weir_scale
@@ -94,7 +127,7 @@ def run_scenario_ensemble(solver, pool, inflow_table, inflow_scale=None, inflow_
     today from the default initial flow (model.py:79-81): it is not rebuilt per member.
 
     A member whose pool leaves the bracket (the reference's ValueError) carries POOL_NO_BRACKET in 'pool' and ends with status NAN.
-    Post-processing keywords and what they add: as run_manning_ensemble (envelope= included, at the same cost: history=True).  Returns dict(hydrographs[nt, 4, B], iterations[nt, B],
+    Post-processing keywords and what they add: as run_manning_ensemble (envelope= included, at the same cost: history=True; balance=).  Returns dict(hydrographs[nt, 4, B], iterations[nt, B],
     status[B], initial_flow[B], pool=dict(flags[B], level[B])) and what the keywords add."""
     if initial != "gvf":
         raise ValueError("initial must be 'gvf': every member starts from the backwater profile of its own release")
@@ -120,7 +153,7 @@ def run_scenario_ensemble(solver, pool, inflow_table, inflow_scale=None, inflow_
         flow0 = b.bc_target(A.UPSTREAM, 0, 1)[0]
         b.set_boundary(A.DOWNSTREAM, boundary_to_spec(ch.downstream_boundary, L, solver.time_step))
         b.init_state("GVF_equation", flow0, depth_ds=ch.downstream_boundary.initial_depth)
-        b.step(nt - 1)
+        _step(b, nt - 1, balance, envelope is not None)
         out = dict(iterations=b.iterations(0, nt), status=b.status(), initial_flow=flow0, pool=routed)
         if hydrographs:
             out = dict(hydrographs=b.hydrographs(0, nt), **out)
@@ -133,11 +166,13 @@ def run_scenario_ensemble(solver, pool, inflow_table, inflow_scale=None, inflow_
             out["bands"] = b.bands(bands, 0, nt)
         if envelope is not None:
             _add_envelope(out, b, envelope, nt)
+        if balance is not None:
+            _add_balance(out, b, balance, nt, envelope is not None)
         return out
 
 
 def run_geometry_ensemble(solver, dz_left=None, dz_main=None, dz_right=None, n_scale=None, tolerance=1e-4, max_iter=100, dtype="f64",
-                          device=0, monitor=True, summaries=False, score=None, bands=None, hydrographs=True, envelope=None):
+                          device=0, monitor=True, summaries=False, score=None, bands=None, hydrographs=True, envelope=None, balance=None):
     """Geometry ensembles of a surveyed river: members that differ in the bed level of the main channel, the elevation of the left
     and right floodplain (levees included) and the three roughnesses.  `solver`: a set-up (not yet run) PreissmannSolver whose
     channel has polyline sections at every node; member r is that channel with the main-channel / left / right vertices of node i
@@ -148,7 +183,7 @@ def run_geometry_ensemble(solver, dz_left=None, dz_main=None, dz_right=None, n_s
     set_geometry_irregular_members), the initial state by the channel's own interpolation method on each member's geometry
     (init_state), and each boundary's bed_level is the member's own (bed_levels() of the end nodes).
 
-    Keywords and return value: as run_manning_ensemble (dtype: polyline batches are fp64; envelope= at the same cost: history=True)."""
+    Keywords and return value: as run_manning_ensemble (dtype: polyline batches are fp64; envelope= at the same cost: history=True; balance=)."""
     ch = solver.channel
     geo = ch.node_geometry
     if "irr_npts" not in geo or np.any(np.asarray(geo["irr_npts"]) == 0):
@@ -174,7 +209,7 @@ def run_geometry_ensemble(solver, dz_left=None, dz_main=None, dz_right=None, n_s
         else:
             b.init_state(method, ch.initial_flow_rate, depth_ds=ch.downstream_boundary.initial_depth,
                          depth_us=ch.upstream_boundary.initial_depth if method == "linear" else None)
-        b.step(nt - 1)
+        _step(b, nt - 1, balance, envelope is not None)
         out = dict(iterations=b.iterations(0, nt), status=b.status())
         if hydrographs:
             out = dict(hydrographs=b.hydrographs(0, nt), **out)
@@ -187,6 +222,8 @@ def run_geometry_ensemble(solver, dz_left=None, dz_main=None, dz_right=None, n_s
             out["bands"] = b.bands(bands, 0, nt)
         if envelope is not None:
             _add_envelope(out, b, envelope, nt)
+        if balance is not None:
+            _add_balance(out, b, balance, nt, envelope is not None)
         return out
 
 

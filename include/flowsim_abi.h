@@ -493,6 +493,47 @@ void *fs_batch_envelope_device_ptr(fs_batch *b, int32_t row);
 int fs_batch_profile_bands(fs_batch *b, int32_t quantity, int32_t stat, const double *q, int32_t n_q, double *moments,
                            double *quantiles, double *exceed, int32_t *n_members);
 
+/* ---- Reach storage and the discrete water balance ----
+ * The handle owns a block integ[max_levels][FS_INT_NROWS][B] of doubles, member minor as the hydrograph block, allocated by the first
+ * call below.  A row that was never evaluated is NaN; fs_batch_set_state*, fs_batch_init_state and fs_batch_restart reset every row.
+ *
+ * fs_batch_reach_integrals: fills the rows first .. first + n - 1 from the stored depth history (FS_FLAG_HISTORY; the flow history is
+ * not read).  first = -1 (n = 1) evaluates the CURRENT state into the row of the batch's current level instead and needs no history:
+ * a batch that keeps none marks its state now and then, between two fs_batch_step calls.  Per (level, reach), with the trapezoid
+ * weights w_i = 1/2 at node 0 and at the reach's own last node (fs_batch_set_reach_nodes), 1 between:
+ *   FS_INT_VOLUME       dx_r sum_i w_i A_i          m^3 in the channel
+ *   FS_INT_SURFACE      dx_r sum_i w_i T_i          m^2 of water surface
+ *   FS_INT_LENGTH_OVER  dx_r sum_i w_i [h_i + z_i >= threshold_i]   metres of reach at or above a stage threshold; NaN without one
+ *   FS_INT_BALANCE      NaN until fs_batch_water_balance writes it
+ * A_i and T_i are evaluated in the batch dtype as fs_batch_derive evaluates them; products with the weights and sums are fp64 and dx_r
+ * is the caller's double (fs_batch_set_reach_scheme's where given), not its rounding to the batch dtype.  threshold[N] is shared, or
+ * [B][N] with threshold_per_reach != 0, rounded once to the batch dtype; a NaN entry means "not assessed" and adds nothing.  A row's
+ * value depends on the row alone: the same bits whatever B, the reach's place in the batch, the range asked for and the source
+ * (history row or current state).  The rows of a failed reach from its failing level on are NaN.  The call is stream-ordered and does
+ * not wait for the device, except to upload a threshold (or the scheme, after it changed). */
+enum { FS_INT_VOLUME = 0, FS_INT_SURFACE, FS_INT_LENGTH_OVER, FS_INT_BALANCE, FS_INT_NROWS };
+int fs_batch_reach_integrals(fs_batch *b, int32_t first, int32_t n, const double *threshold, int32_t threshold_per_reach);
+/* fs_batch_water_balance: per reach, over the levels [first, first + n), from each evaluated row to the next evaluated row (a span:
+ * one level where every row was evaluated, a chunk of levels for a batch that was marked now and then), FS_INT_BALANCE of the span's
+ * end row = (V_end - V_begin) - sum over the span's levels l of dt_r [theta_r (Q_0 - Q_last)_l + (1 - theta_r) (Q_0 - Q_last)_{l-1}]
+ * with the boundary flows of the hydrograph block and the caller's fp64 theta_r, dt_r; the first evaluated row of the range gets 0.
+ * The Preissmann continuity row is conservative, so a span's residual is dt dx times the summed continuity residuals of its levels:
+ * bounded by the Newton tolerance.  totals[FS_BAL_NROWS][B] or NULL: spans, first and last evaluated level (relative to `first`, -1:
+ * none), storage change, net inflow volume, inflow volume, summed residual, largest |residual| and the level of its span's end,
+ * summed residual over inflow volume.  A failed reach enters with the rows before its failing level. */
+enum { FS_BAL_SPANS = 0, FS_BAL_FIRST_LEVEL, FS_BAL_LAST_LEVEL, FS_BAL_STORAGE_CHANGE, FS_BAL_NET_INFLOW, FS_BAL_INFLOW,
+       FS_BAL_RESIDUAL, FS_BAL_WORST, FS_BAL_WORST_LEVEL, FS_BAL_RELATIVE, FS_BAL_NROWS };
+int fs_batch_water_balance(fs_batch *b, int32_t first, int32_t n, double *totals);
+/* out[n][FS_INT_NROWS][B]: the rows first .. first + n - 1 of the block (any rows of 0 .. max_levels - 1), and the block on the
+ * device, [max_levels][FS_INT_NROWS][B] doubles (NULL before the first evaluation) */
+int fs_batch_get_reach_integrals(fs_batch *b, int32_t first, int32_t n, double *out);
+void *fs_batch_reach_integrals_device_ptr(fs_batch *b);
+/* fs_batch_bands on the integral block instead of the hydrograph block (the same kernel): moments[n][FS_INT_NROWS][4],
+ * quantiles[n][FS_INT_NROWS][n_q], n_members[n].  Failed members are left out; a level that one of the remaining members has not
+ * evaluated reports NaN, as numpy would. */
+int fs_batch_integral_bands(fs_batch *b, int32_t first, int32_t n, const double *q, int32_t n_q, double *moments, double *quantiles,
+                            int32_t *n_members);
+
 /* zero-copy access for device-side consumers (RCCL gather of hydrographs): device pointer to the
  * [max_levels][4][B] hydrograph block in the batch dtype, and the handle's hipStream_t */
 void *fs_batch_hydrograph_device_ptr(fs_batch *b);
