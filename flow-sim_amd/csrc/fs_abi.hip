@@ -3,9 +3,9 @@
 // Holds the device buffers of a batch (SoA, reach-major state [B][N]; per-level tables [level][B]) as fs::DeviceBuffer /
 // fs::PinnedBuffer members (fs_buffer.hpp: freed with the handle), converts caller float64 host arrays to the batch dtype on
 // upload, asks fs::pick (fs_dispatch.hpp) for the kernel instantiation and launches the fused step kernel on the handle's HIP
-// stream.  What needs no device - packing polylines and their stage tables, extending geometry tables, validating boundary
-// arguments - is fs_host_pack.hpp, which the CPU tests build on its own; the batch's arithmetic type is turned into a C++ type in one
-// place (with_real).  No CPU compute path exists here: without a HIP device every entry point that needs one fails and says so.
+// stream.  What needs no device - packing polylines and stage tables, extending geometry tables, validating boundary arguments
+// (fs_host_pack.hpp), the checks and result layouts of post-processing (fs_host_post.hpp) - the CPU tests build on its own; the batch's
+// arithmetic type becomes a C++ type in one place (with_real).  No CPU compute path: without a device every entry point that needs one says so.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,6 +27,7 @@
 #include "fs_envelope.hpp"
 #include "fs_forcing.hpp"
 #include "fs_host_pack.hpp"
+#include "fs_host_post.hpp"
 #include "fs_init_state.hpp"
 #include "fs_member_geo.hpp"
 #include "fs_reduce.hpp"
@@ -659,17 +660,23 @@ int init_batch(fs_batch *b) {
 }
 
 
-// ---- ensemble post-processing (fs_reduce.hpp): what the three entry points share ----
+// ---- post-processing (fs_reduce.hpp, fs_envelope.hpp, fs_balance.hpp): what its entry points share; their checks and layouts are
+// fs_host_post.hpp ----
+
+// a check of fs_host_post.hpp: its text, if it has one, becomes the error
+int refuse(const std::string &text) { return text.empty() ? 0 : fail(text); }
 
 // the range [first, first + n) must hold computed rows only
-int check_reduce_range(const fs_batch *b, const char *entry, int32_t first, int32_t n) {
+int check_reduce_range(const fs_batch *b, const char *entry, int32_t first, int32_t n,
+                       const char *not_restored = "the hydrograph rows before it were not restored") {
   if (!b->have_state) return fail(std::string(entry) + ": no state yet");
-  if (first < 0 || n < 1 || (int64_t)first + n > (int64_t)b->level + 1)
-    return fail(std::string(entry) + ": levels [" + std::to_string(first) + ", " + std::to_string((int64_t)first + n) + ") are not inside 0 .. " +
-                std::to_string(b->level) + ", the levels this batch has computed");
-  if (b->restart_level > 0 && first < b->restart_level)
-    return fail(std::string(entry) + ": this batch was restarted at level " + std::to_string(b->restart_level) + "; the hydrograph rows before it were not restored");
-  return 0;
+  return refuse(fs::check_computed_range(entry, first, n, b->level, b->restart_level, not_restored));
+}
+
+// the batch's section tables as derive, envelope and reach integrals read them
+template <typename R> fs::SectionTables<R> section_tables(const fs_batch *b) {
+  return fs::SectionTables<R>{b->geo_uniform.get<const R>(), b->geo_table.get<const R>(), b->poly_x.get<const R>(), b->poly_z.get<const R>(),
+                              b->poly_n.get<const int32_t>(), (int64_t)b->geo_reach_stride, (int64_t)b->poly_reach_stride};
 }
 
 template <typename R> fs::ReduceArgs<R> reduce_args(const fs_batch *b, int32_t first, int32_t n) {
@@ -690,6 +697,36 @@ int fetch(fs_batch *b, void *dst, const void *dev, size_t bytes) {
 }
 
 const char kNoReduceKernels[] = ": this build has no post-processing kernels";
+
+// One post-processing launch on the handle's stream: launch(real), handed the batch's type as with_real does, says whether this build
+// has the kernel.  launches > 0: the two events are recorded around it, and fs_batch_last_step_ms() / fs_batch_last_launch_count()
+// then report it; 0: they keep what they held.
+template <typename Launch> int post_launch(fs_batch *b, const char *entry, int launches, Launch &&launch) {
+  if (launches > 0) HIP_TRY(hipEventRecord(b->ev0, b->stream));
+  if (!with_real(b, launch)) return fail(std::string(entry) + kNoReduceKernels);
+  HIP_TRY(hipGetLastError());
+  if (launches > 0) {
+    HIP_TRY(hipEventRecord(b->ev1, b->stream));
+    b->timed = true; b->launches = launches;
+  }
+  return 0;
+}
+
+// the outputs of a band call (fs::BandArgs, fs::ProfileBandArgs) that the caller asked for, in the block at blk; q: the levels on the device
+template <typename Args> void point_bands(Args &p, const fs::BandLayout &l, double *blk, const double *q, int32_t n_q, bool moments, bool members) {
+  p.q = l.n_quantiles ? q : nullptr; p.n_q = l.n_quantiles ? n_q : 0;
+  p.moments = moments ? blk + l.moments : nullptr; p.quantiles = l.n_quantiles ? blk + l.quantiles : nullptr;
+  p.n_members = members ? (int32_t *)(blk + l.members) : nullptr;
+}
+
+// ... and back to the caller; extra: the per-series row of the layout, or nullptr
+int fetch_bands(fs_batch *b, const fs::BandLayout &l, const double *blk, double *moments, double *quantiles, double *extra, int32_t *members) {
+  if (moments && fetch(b, moments, blk + l.moments, l.n_moments * sizeof(double))) return -1;
+  if (l.n_quantiles && fetch(b, quantiles, blk + l.quantiles, l.n_quantiles * sizeof(double))) return -1;
+  if (extra && fetch(b, extra, blk + l.extra, l.series * sizeof(double))) return -1;
+  if (members && fetch(b, members, blk + l.members, l.series * sizeof(int32_t))) return -1;
+  return 0;
+}
 
 // ---- forcing on the device (fs_forcing.hpp) ----
 
@@ -1480,21 +1517,15 @@ int fs_batch_derive_device(fs_batch *b, int32_t first, int32_t n, int32_t fields
     dev[f] = b->derived[f].get();
   }
   const size_t per_thread = 16 / b->esz;           // one 16-byte access per thread, level and field
-  HIP_TRY(hipEventRecord(b->ev0, b->stream));      // fs_batch_last_step_ms() then reports this kernel
-  with_real(b, [&](auto real) {
+  return post_launch(b, "fs_batch_derive", 1, [&](auto real) {      // fs_batch_last_step_ms() then reports this kernel
     using R = decltype(real);
     fs::DeriveArgs<R> a{b->d.n_reaches, b->d.n_nodes, first, n, b->d.section_mode, b->hist_h.get<const R>(), b->hist_Q.get<const R>(),
-                        b->geo_uniform.get<const R>(), b->geo_table.get<const R>(), b->poly_x.get<const R>(), b->poly_z.get<const R>(),
-                        b->poly_n.get<const int32_t>(), (int64_t)b->geo_reach_stride, (int64_t)b->poly_reach_stride,
-                        (R *)dev[0], (R *)dev[1], (R *)dev[2], (R *)dev[3], (R *)dev[4], (R *)dev[5], (R *)dev[6], (R *)dev[7],
+                        section_tables<R>(b), (R *)dev[0], (R *)dev[1], (R *)dev[2], (R *)dev[3], (R *)dev[4], (R *)dev[5], (R *)dev[6], (R *)dev[7],
                         b->reach_nodes.get<const int32_t>()};
     hipLaunchKernelGGL((fs::derive_fields_kernel<R, (int)(16 / sizeof(R))>), grid_256((BN + per_thread - 1) / per_thread), dim3(256), 0,
                        b->stream, a);
+    return true;
   });
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(b->ev1, b->stream));
-  b->timed = true; b->launches = 1;
-  return 0;
 }
 
 void *fs_batch_derived_device_ptr(fs_batch *b, int32_t field_index) {
@@ -1523,12 +1554,9 @@ int fs_batch_summarize(fs_batch *b, int32_t first, int32_t n, double *out) {
   TraceRange range_("flowsim:reduce");
   const size_t B = b->d.n_reaches, bytes = (size_t)FS_SUM_NROWS * B * sizeof(double);
   HIP_TRY(b->red_out[0].reserve(bytes));
-  const bool launched = with_real(b, [&](auto real) {
-    using R = decltype(real);
-    return fs::launch_summarize(reduce_args<R>(b, first, n), b->red_out[0].get<double>(), b->stream);
-  });
-  if (!launched) return fail(std::string("fs_batch_summarize") + kNoReduceKernels);
-  HIP_TRY(hipGetLastError());
+  if (post_launch(b, "fs_batch_summarize", 0, [&](auto real) {
+        return fs::launch_summarize(reduce_args<decltype(real)>(b, first, n), b->red_out[0].get<double>(), b->stream);
+      })) return -1;
   return fetch(b, out, b->red_out[0].get(), bytes);
 }
 
@@ -1536,10 +1564,7 @@ int fs_batch_lookup(fs_batch *b, int32_t first, int32_t n, int32_t x_row, int32_
                     const double *xq, int32_t n_q, const double *target, double *values, double *rmse, int32_t *info) {
   if (!b) return fail("fs_batch_lookup: null handle");
   if (!values && !rmse && !info) return fail("fs_batch_lookup: no output requested (values, rmse and info are all NULL)");
-  if (x_row < 0 || x_row > 3 || y_row < 0 || y_row > 3) return fail("fs_batch_lookup: x_row and y_row are 0..3 (h[0], Q[0], h[N-1], Q[N-1])");
-  if (n_q < 1 || n_q > 65535) return fail("fs_batch_lookup: n_q must be 1 .. 65535");
-  if (!xq) return fail("fs_batch_lookup: null query abscissae");
-  if (rmse && !target) return fail("fs_batch_lookup: rmse needs a target");
+  if (refuse(fs::check_lookup_args(x_row, y_row, xq, n_q, target, rmse != nullptr))) return -1;
   if (check_reduce_range(b, "fs_batch_lookup", first, n)) return -1;
   FS_ON_DEVICE(b);
   TraceRange range_("flowsim:reduce");
@@ -1548,58 +1573,19 @@ int fs_batch_lookup(fs_batch *b, int32_t first, int32_t n, int32_t x_row, int32_
   if (y_offset && upload_f64(b->red_in[0], y_offset, B)) return -1;
   if (upload_f64(b->red_in[1], xq, (size_t)n_q)) return -1;
   if (rmse && upload_f64(b->red_in[2], target, (size_t)n_q)) return -1;
-  // values [n_q][B], then rmse [B], then info [B]
-  const size_t n_val = (size_t)n_q * B;
-  HIP_TRY(b->red_out[1].reserve((n_val + B) * sizeof(double) + B * sizeof(int32_t)));
-  double *d_val = b->red_out[1].get<double>();
+  const fs::LookupLayout lay = fs::lookup_layout((size_t)n_q, B);
+  HIP_TRY(b->red_out[1].reserve(lay.bytes));
+  double *blk = b->red_out[1].get<double>();
   fs::LookupArgs l;
   l.x_row = x_row; l.y_row = y_row; l.n_q = n_q;
   l.y_offset = y_offset ? b->red_in[0].get<const double>() : nullptr;
   l.xq = b->red_in[1].get<const double>(); l.target = rmse ? b->red_in[2].get<const double>() : nullptr;
-  l.values = d_val; l.rmse = rmse ? d_val + n_val : nullptr; l.info = info ? (int32_t *)(d_val + n_val + B) : nullptr;
-  const bool launched = with_real(b, [&](auto real) {
-    using R = decltype(real);
-    return fs::launch_lookup(reduce_args<R>(b, first, n), l, b->stream);
-  });
-  if (!launched) return fail(std::string("fs_batch_lookup") + kNoReduceKernels);
-  HIP_TRY(hipGetLastError());
-  if (values && fetch(b, values, l.values, n_val * sizeof(double))) return -1;
+  l.values = blk + lay.values; l.rmse = rmse ? blk + lay.rmse : nullptr; l.info = info ? (int32_t *)(blk + lay.info) : nullptr;
+  if (post_launch(b, "fs_batch_lookup", 0, [&](auto real) { return fs::launch_lookup(reduce_args<decltype(real)>(b, first, n), l, b->stream); }))
+    return -1;
+  if (values && fetch(b, values, l.values, lay.n_values * sizeof(double))) return -1;
   if (rmse && fetch(b, rmse, l.rmse, B * sizeof(double))) return -1;
   if (info && fetch(b, info, l.info, B * sizeof(int32_t))) return -1;
-  return 0;
-}
-
-int fs_batch_bands(fs_batch *b, int32_t first, int32_t n, const double *q, int32_t n_q, double *moments, double *quantiles,
-                   int32_t *n_members) {
-  if (!b) return fail("fs_batch_bands: null handle");
-  if (!moments && !quantiles && !n_members) return fail("fs_batch_bands: no output requested (moments, quantiles and n_members are all NULL)");
-  if (n_q < 0 || n_q > fs::kBandMaxQ) return fail("fs_batch_bands: n_q must be 0 .. " + std::to_string(fs::kBandMaxQ));
-  if (n_q > 0 && !q) return fail("fs_batch_bands: null quantile levels");
-  for (int i = 0; i < n_q; ++i)
-    if (!(q[i] >= 0.0 && q[i] <= 1.0)) return fail("fs_batch_bands: quantile levels must be in [0, 1]");
-  if (check_reduce_range(b, "fs_batch_bands", first, n)) return -1;
-  FS_ON_DEVICE(b);
-  TraceRange range_("flowsim:reduce");
-  const bool want_q = quantiles && n_q > 0;
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  if (want_q && upload_f64(b->red_in[1], q, (size_t)n_q)) return -1;
-  // moments [n][4][4], then quantiles [n][4][n_q], then n_members [n]
-  const size_t n_mom = (size_t)n * 16, n_qu = want_q ? (size_t)n * 4 * n_q : 0;
-  HIP_TRY(b->red_out[2].reserve((n_mom + n_qu) * sizeof(double) + (size_t)n * sizeof(int32_t)));
-  double *d_mom = b->red_out[2].get<double>();
-  fs::BandArgs p;
-  p.q = want_q ? b->red_in[1].get<const double>() : nullptr; p.n_q = want_q ? n_q : 0;
-  p.moments = moments ? d_mom : nullptr; p.quantiles = want_q ? d_mom + n_mom : nullptr;
-  p.n_members = n_members ? (int32_t *)(d_mom + n_mom + n_qu) : nullptr;
-  const bool launched = with_real(b, [&](auto real) {
-    using R = decltype(real);
-    return fs::launch_bands(reduce_args<R>(b, first, n), p, b->stream);
-  });
-  if (!launched) return fail(std::string("fs_batch_bands") + kNoReduceKernels);
-  HIP_TRY(hipGetLastError());
-  if (moments && fetch(b, moments, p.moments, n_mom * sizeof(double))) return -1;
-  if (want_q && fetch(b, quantiles, p.quantiles, n_qu * sizeof(double))) return -1;
-  if (n_members && fetch(b, n_members, p.n_members, (size_t)n * sizeof(int32_t))) return -1;
   return 0;
 }
 
@@ -1609,55 +1595,35 @@ int fs_batch_envelope_device(fs_batch *b, int32_t first, int32_t n, int32_t quan
   if (!b->hist_h) return fail("fs_batch_envelope: batch was created without FS_FLAG_HISTORY");
   if ((quantities & FS_ENV_ALL) == 0 || (quantities & ~FS_ENV_ALL) != 0)
     return fail("fs_batch_envelope: quantities must be a mask of FS_ENV_DEPTH .. FS_ENV_TOP_WIDTH with at least one bit set");
-  int cross_q = -1;
-  if (threshold) {
-    for (int q = 0; q < fs::kEnvQuantities; ++q)
-      if (threshold_quantity == (1 << q)) cross_q = q;
-    if (cross_q < 0) return fail("fs_batch_envelope: threshold_quantity must be one of FS_ENV_DEPTH .. FS_ENV_TOP_WIDTH");
-  }
-  if (!b->have_state) return fail("fs_batch_envelope: no state yet");
-  if (first < 0 || n < 1 || (int64_t)first + n > (int64_t)b->level + 1)
-    return fail("fs_batch_envelope: levels [" + std::to_string(first) + ", " + std::to_string((int64_t)first + n) + ") are not inside 0 .. " +
-                std::to_string(b->level) + ", the levels this batch has computed");
-  if (b->restart_level > 0 && first < b->restart_level)
-    return fail("fs_batch_envelope: this batch was restarted at level " + std::to_string(b->restart_level) +
-                "; the history before it was not restored");
+  const int cross_q = threshold ? fs::EnvRows::quantity_index(threshold_quantity) : -1;
+  if (threshold && cross_q < 0) return fail("fs_batch_envelope: threshold_quantity must be one of FS_ENV_DEPTH .. FS_ENV_TOP_WIDTH");
+  if (check_reduce_range(b, "fs_batch_envelope", first, n, "the history before it was not restored")) return -1;
   FS_ON_DEVICE(b);
   TraceRange range_("flowsim:envelope");
   const size_t B = b->d.n_reaches, BN = B * b->d.n_nodes;
-  int n_sel = 0;
-  for (int q = 0; q < fs::kEnvQuantities; ++q) n_sel += (quantities >> q) & 1;
+  const fs::EnvRows rows(quantities, threshold != nullptr);
   b->env_quantities = 0; b->env_crossings = false;      // (the handle holds no envelope until this one is launched)
   HIP_TRY(hipStreamSynchronize(b->stream));             // an earlier call's kernels are through with the threshold
   if (threshold && upload(b, b->env_thr, threshold, threshold_per_reach ? BN : (size_t)b->d.n_nodes)) return -1;
-  HIP_TRY(b->env_out.reserve(((size_t)n_sel * FS_ENV_NSTAT + (threshold ? FS_ENV_NCROSS : 0)) * BN * sizeof(double)));
+  HIP_TRY(b->env_out.reserve((size_t)rows.n_rows * BN * sizeof(double)));
   HIP_TRY(b->env_levels.reserve(B * sizeof(int32_t)));
   const char *unroll_env = std::getenv("FS_ENVELOPE_UNROLL");      // levels whose loads a thread has in flight: 1, 4, 8 (tools/time_envelope.py compares)
   const int unroll = unroll_env ? std::atoi(unroll_env) : 0;       // 0: the launcher's choice
-  HIP_TRY(hipEventRecord(b->ev0, b->stream));      // fs_batch_last_step_ms() then reports this kernel
-  const bool launched = with_real(b, [&](auto real) {
-    using R = decltype(real);
-    fs::EnvelopeArgs<R> a{b->d.n_reaches, b->d.n_nodes, first, n, b->d.section_mode, b->hist_h.get<const R>(), b->hist_Q.get<const R>(),
-                          b->geo_uniform.get<const R>(), b->geo_table.get<const R>(), b->poly_x.get<const R>(), b->poly_z.get<const R>(),
-                          b->poly_n.get<const int32_t>(), (int64_t)b->geo_reach_stride, (int64_t)b->poly_reach_stride,
-                          b->reach_nodes.get<const int32_t>(), reduce_args<R>(b, first, n), quantities, cross_q,
-                          threshold ? b->env_thr.get<const R>() : nullptr, threshold_per_reach ? 1 : 0, b->env_out.get<double>(),
-                          threshold ? b->env_out.get<double>() + (size_t)n_sel * FS_ENV_NSTAT * BN : nullptr, b->env_levels.get<int32_t>()};
-    return fs::launch_envelope(a, unroll, b->stream);
-  });
-  if (!launched) return fail(std::string("fs_batch_envelope") + kNoReduceKernels);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(b->ev1, b->stream));
-  b->timed = true; b->launches = 1;
+  if (post_launch(b, "fs_batch_envelope", 1, [&](auto real) {      // fs_batch_last_step_ms() then reports this kernel
+        using R = decltype(real);
+        fs::EnvelopeArgs<R> a{b->d.n_reaches, b->d.n_nodes, first, n, b->d.section_mode, b->hist_h.get<const R>(), b->hist_Q.get<const R>(),
+                              section_tables<R>(b), b->reach_nodes.get<const int32_t>(), reduce_args<R>(b, first, n), quantities, cross_q,
+                              threshold ? b->env_thr.get<const R>() : nullptr, threshold_per_reach ? 1 : 0, b->env_out.get<double>(),
+                              threshold ? b->env_out.get<double>() + (size_t)rows.cross_row * BN : nullptr, b->env_levels.get<int32_t>()};
+        return fs::launch_envelope(a, unroll, b->stream);
+      })) return -1;
   b->env_quantities = quantities; b->env_crossings = threshold != nullptr;
   return 0;
 }
 
 void *fs_batch_envelope_device_ptr(fs_batch *b, int32_t row) {
   if (!b) { fail("fs_batch_envelope_device_ptr: null handle"); return nullptr; }
-  int n_rows = 0;
-  for (int q = 0; q < fs::kEnvQuantities; ++q) n_rows += ((b->env_quantities >> q) & 1) * FS_ENV_NSTAT;
-  if (b->env_crossings) n_rows += FS_ENV_NCROSS;
+  const int n_rows = fs::EnvRows(b->env_quantities, b->env_crossings).n_rows;
   if (row < 0 || row >= n_rows) { fail("fs_batch_envelope_device_ptr: the envelope this handle holds has no such row"); return nullptr; }
   return b->env_out.get<double>() + (size_t)row * b->d.n_reaches * b->d.n_nodes;
 }
@@ -1669,8 +1635,7 @@ int fs_batch_envelope(fs_batch *b, int32_t first, int32_t n, int32_t quantities,
   if (fs_batch_envelope_device(b, first, n, quantities, threshold, threshold_per_reach, threshold_quantity)) return -1;
   FS_ON_DEVICE(b);
   const size_t B = b->d.n_reaches, BN = B * b->d.n_nodes;
-  size_t n_out = 0;
-  for (int q = 0; q < fs::kEnvQuantities; ++q) n_out += (size_t)((quantities >> q) & 1) * FS_ENV_NSTAT * BN;
+  const size_t n_out = (size_t)fs::EnvRows(quantities, threshold != nullptr).cross_row * BN;
   if (out && fetch(b, out, b->env_out.get(), n_out * sizeof(double))) return -1;
   if (crossing && fetch(b, crossing, b->env_out.get<double>() + n_out, (size_t)FS_ENV_NCROSS * BN * sizeof(double))) return -1;
   if (levels && fetch(b, levels, b->env_levels.get(), B * sizeof(int32_t))) return -1;
@@ -1682,18 +1647,10 @@ int fs_batch_profile_bands(fs_batch *b, int32_t quantity, int32_t stat, const do
   if (!b) return fail("fs_batch_profile_bands: null handle");
   if (!moments && !quantiles && !exceed && !n_members)
     return fail("fs_batch_profile_bands: no output requested (moments, quantiles, exceed and n_members are all NULL)");
-  if (n_q < 0 || n_q > fs::kBandMaxQ) return fail("fs_batch_profile_bands: n_q must be 0 .. " + std::to_string(fs::kBandMaxQ));
-  if (n_q > 0 && !q) return fail("fs_batch_profile_bands: null quantile levels");
-  for (int i = 0; i < n_q; ++i)
-    if (!(q[i] >= 0.0 && q[i] <= 1.0)) return fail("fs_batch_profile_bands: quantile levels must be in [0, 1]");
+  if (refuse(fs::check_quantile_levels("fs_batch_profile_bands", q, n_q))) return -1;
   if (b->env_quantities == 0) return fail("fs_batch_profile_bands: this handle holds no envelope (fs_batch_envelope comes first)");
-  int n_sel = 0, row = -1;
-  for (int k = 0; k < fs::kEnvQuantities; ++k) {
-    if (!((b->env_quantities >> k) & 1)) continue;
-    if (quantity == (1 << k) && stat >= 0 && stat < FS_ENV_NSTAT) row = n_sel * FS_ENV_NSTAT + stat;
-    ++n_sel;
-  }
-  if (quantity == FS_ENV_CROSSING && b->env_crossings && stat >= 0 && stat < FS_ENV_NCROSS) row = n_sel * FS_ENV_NSTAT + stat;
+  const fs::EnvRows held(b->env_quantities, b->env_crossings);
+  const int row = held.row_of(quantity, stat);
   if (row < 0) return fail("fs_batch_profile_bands: the envelope this handle holds has no such row (quantity " + std::to_string(quantity) +
                            ", statistic " + std::to_string(stat) + ")");
   if (exceed && !b->env_crossings) return fail("fs_batch_profile_bands: exceed needs an envelope that was computed with a threshold");
@@ -1705,31 +1662,21 @@ int fs_batch_profile_bands(fs_batch *b, int32_t quantity, int32_t stat, const do
   HIP_TRY(hipStreamSynchronize(b->stream));
   if (want_q && upload_f64(b->red_in[1], q, (size_t)n_q)) return -1;
   HIP_TRY(b->env_t.reserve((exceed ? 2 : 1) * BN * sizeof(double)));
-  // moments [N][4], then quantiles [N][n_q], then exceed [N], then n_members [N]
-  const size_t n_mom = (size_t)N * 4, n_qu = want_q ? (size_t)N * n_q : 0;
-  HIP_TRY(b->red_out[2].reserve((n_mom + n_qu + (size_t)N) * sizeof(double) + (size_t)N * sizeof(int32_t)));
-  double *d_mom = b->red_out[2].get<double>();
+  const fs::BandLayout lay = fs::band_layout((size_t)N, 1, want_q ? (size_t)n_q : 0, true);      // (the exceed row is always reserved)
+  HIP_TRY(b->red_out[2].reserve(lay.bytes));
+  double *blk = b->red_out[2].get<double>();
   const double *env = b->env_out.get<const double>();
-  fs::TransposeRows rows{{env + (size_t)row * BN, env + ((size_t)n_sel * FS_ENV_NSTAT + FS_ENV_CROSS_COUNT) * BN}};
+  fs::TransposeRows rows{{env + (size_t)row * BN, env + (size_t)(held.cross_row + FS_ENV_CROSS_COUNT) * BN}};
   fs::ProfileBandArgs p;
   p.x = b->env_t.get<const double>(); p.count = exceed ? p.x + BN : nullptr;
   p.status = b->status.get<const int32_t>(); p.levels = b->env_levels.get<const int32_t>(); p.reach_nodes = b->reach_nodes.get<const int32_t>();
   p.B = B; p.N = N;
-  p.q = want_q ? b->red_in[1].get<const double>() : nullptr; p.n_q = want_q ? n_q : 0;
-  p.moments = moments ? d_mom : nullptr; p.quantiles = want_q ? d_mom + n_mom : nullptr; p.exceed = exceed ? d_mom + n_mom + n_qu : nullptr;
-  p.n_members = n_members ? (int32_t *)(d_mom + n_mom + n_qu + N) : nullptr;
-  HIP_TRY(hipEventRecord(b->ev0, b->stream));      // fs_batch_last_step_ms(): the transpose and the bands
-  const bool launched = fs::launch_transpose_rows(rows, exceed ? 2 : 1, b->env_t.get<double>(), B, N, b->stream) &&
-                        fs::launch_profile_bands(p, b->stream);
-  if (!launched) return fail(std::string("fs_batch_profile_bands") + kNoReduceKernels);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(b->ev1, b->stream));
-  b->timed = true; b->launches = 2;
-  if (moments && fetch(b, moments, p.moments, n_mom * sizeof(double))) return -1;
-  if (want_q && fetch(b, quantiles, p.quantiles, n_qu * sizeof(double))) return -1;
-  if (exceed && fetch(b, exceed, p.exceed, (size_t)N * sizeof(double))) return -1;
-  if (n_members && fetch(b, n_members, p.n_members, (size_t)N * sizeof(int32_t))) return -1;
-  return 0;
+  point_bands(p, lay, blk, b->red_in[1].get<const double>(), n_q, moments != nullptr, n_members != nullptr);
+  p.exceed = exceed ? blk + lay.extra : nullptr;
+  if (post_launch(b, "fs_batch_profile_bands", 2, [&](auto) {      // fs_batch_last_step_ms(): the transpose and the bands
+        return fs::launch_transpose_rows(rows, exceed ? 2 : 1, b->env_t.get<double>(), B, N, b->stream) && fs::launch_profile_bands(p, b->stream);
+      })) return -1;
+  return fetch_bands(b, lay, blk, moments, quantiles, exceed, n_members);
 }
 
 // ---- reach integrals and the water balance (fs_balance.hpp) ----
@@ -1779,23 +1726,15 @@ int fs_batch_reach_integrals(fs_batch *b, int32_t first, int32_t n, const double
     if (upload(b, b->integ_thr, threshold, threshold_per_reach ? BN : (size_t)b->d.n_nodes)) return -1;
   }
   const int32_t row0 = current ? b->level : first;
-  HIP_TRY(hipEventRecord(b->ev0, b->stream));      // fs_batch_last_step_ms() then reports this kernel
-  const bool launched = with_real(b, [&](auto real) {
+  return post_launch(b, "fs_batch_reach_integrals", 1, [&](auto real) {      // fs_batch_last_step_ms() then reports this kernel
     using R = decltype(real);
     fs::IntegralArgs<R> a{b->d.n_reaches, b->d.n_nodes, b->d.section_mode,
                           current ? b->hk.get<const R>() : b->hist_h.get<const R>() + (size_t)first * BN, current ? (int64_t)0 : (int64_t)BN,
-                          b->geo_uniform.get<const R>(), b->geo_table.get<const R>(), b->poly_x.get<const R>(), b->poly_z.get<const R>(),
-                          b->poly_n.get<const int32_t>(), (int64_t)b->geo_reach_stride, (int64_t)b->poly_reach_stride,
-                          b->reach_nodes.get<const int32_t>(), reduce_args<R>(b, row0, n), b->bal_scheme.get<const double>() + 2 * B,
-                          threshold ? b->integ_thr.get<const R>() : nullptr, threshold_per_reach ? 1 : 0, b->integ.get<double>(),
-                          b->integ_mark.get<int32_t>()};
+                          section_tables<R>(b), b->reach_nodes.get<const int32_t>(), reduce_args<R>(b, row0, n),
+                          b->bal_scheme.get<const double>() + 2 * B, threshold ? b->integ_thr.get<const R>() : nullptr,
+                          threshold_per_reach ? 1 : 0, b->integ.get<double>(), b->integ_mark.get<int32_t>()};
     return fs::launch_reach_integrals(a, b->stream);
   });
-  if (!launched) return fail(std::string("fs_batch_reach_integrals") + kNoReduceKernels);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(b->ev1, b->stream));
-  b->timed = true; b->launches = 1;
-  return 0;
 }
 
 int fs_batch_water_balance(fs_batch *b, int32_t first, int32_t n, double *totals) {
@@ -1809,15 +1748,8 @@ int fs_batch_water_balance(fs_batch *b, int32_t first, int32_t n, double *totals
   if (totals) HIP_TRY(b->red_out[0].reserve(bytes));
   fs::BalanceArgs p{b->integ.get<double>(), b->integ_mark.get<const int32_t>(), b->bal_scheme.get<const double>(),
                     b->bal_scheme.get<const double>() + B, totals ? b->red_out[0].get<double>() : nullptr};
-  HIP_TRY(hipEventRecord(b->ev0, b->stream));
-  const bool launched = with_real(b, [&](auto real) {
-    using R = decltype(real);
-    return fs::launch_balance(reduce_args<R>(b, first, n), p, b->stream);
-  });
-  if (!launched) return fail(std::string("fs_batch_water_balance") + kNoReduceKernels);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(b->ev1, b->stream));
-  b->timed = true; b->launches = 1;
+  if (post_launch(b, "fs_batch_water_balance", 1, [&](auto real) { return fs::launch_balance(reduce_args<decltype(real)>(b, first, n), p, b->stream); }))
+    return -1;
   return totals ? fetch(b, totals, p.totals, bytes) : 0;
 }
 
@@ -1832,42 +1764,42 @@ int fs_batch_get_reach_integrals(fs_batch *b, int32_t first, int32_t n, double *
 
 void *fs_batch_reach_integrals_device_ptr(fs_batch *b) { return b ? b->integ.get() : nullptr; }
 
-int fs_batch_integral_bands(fs_batch *b, int32_t first, int32_t n, const double *q, int32_t n_q, double *moments, double *quantiles,
-                            int32_t *n_members) {
-  if (!b) return fail("fs_batch_integral_bands: null handle");
-  if (!moments && !quantiles && !n_members) return fail("fs_batch_integral_bands: no output requested (moments, quantiles and n_members are all NULL)");
-  if (n_q < 0 || n_q > fs::kBandMaxQ) return fail("fs_batch_integral_bands: n_q must be 0 .. " + std::to_string(fs::kBandMaxQ));
-  if (n_q > 0 && !q) return fail("fs_batch_integral_bands: null quantile levels");
-  for (int i = 0; i < n_q; ++i)
-    if (!(q[i] >= 0.0 && q[i] <= 1.0)) return fail("fs_batch_integral_bands: quantile levels must be in [0, 1]");
-  if (check_reduce_range(b, "fs_batch_integral_bands", first, n)) return -1;
+// fs_batch_bands and fs_batch_integral_bands: bands_kernel over the four rows of every level of the range - of the hydrograph block, or
+// (integrals; the call is then timed) of the integral block, which has its shape: a ReduceArgs<double> that points at it
+static int band_rows(fs_batch *b, const char *entry, bool integrals, int32_t first, int32_t n, const double *q, int32_t n_q, double *moments,
+                     double *quantiles, int32_t *n_members) {
+  if (!b) return fail(std::string(entry) + ": null handle");
+  if (!moments && !quantiles && !n_members) return fail(std::string(entry) + ": no output requested (moments, quantiles and n_members are all NULL)");
+  if (refuse(fs::check_quantile_levels(entry, q, n_q)) || check_reduce_range(b, entry, first, n)) return -1;
   FS_ON_DEVICE(b);
   TraceRange range_("flowsim:reduce");
-  if (ready_integrals(b, "fs_batch_integral_bands")) return -1;
+  if (integrals && ready_integrals(b, entry)) return -1;
   const bool want_q = quantiles && n_q > 0;
   HIP_TRY(hipStreamSynchronize(b->stream));
   if (want_q && upload_f64(b->red_in[1], q, (size_t)n_q)) return -1;
-  // moments [n][4][4], then quantiles [n][4][n_q], then n_members [n]
   static_assert(FS_INT_NROWS == 4, "bands_kernel walks the four rows of a level of the hydrograph block");
-  const size_t n_mom = (size_t)n * 16, n_qu = want_q ? (size_t)n * 4 * n_q : 0;
-  HIP_TRY(b->red_out[2].reserve((n_mom + n_qu) * sizeof(double) + (size_t)n * sizeof(int32_t)));
-  double *d_mom = b->red_out[2].get<double>();
+  const fs::BandLayout lay = fs::band_layout((size_t)n, 4, want_q ? (size_t)n_q : 0, false);
+  HIP_TRY(b->red_out[2].reserve(lay.bytes));
+  double *blk = b->red_out[2].get<double>();
   fs::BandArgs p;
-  p.q = want_q ? b->red_in[1].get<const double>() : nullptr; p.n_q = want_q ? n_q : 0;
-  p.moments = moments ? d_mom : nullptr; p.quantiles = want_q ? d_mom + n_mom : nullptr;
-  p.n_members = n_members ? (int32_t *)(d_mom + n_mom + n_qu) : nullptr;
-  // the block has the hydrograph block's shape: the shipped bands_kernel on a ReduceArgs<double> that points at it
-  const fs::ReduceArgs<double> a{b->integ.get<const double>(), b->status.get<const int32_t>(), b->iters.get<const int32_t>(), b->d.n_reaches,
-                                 b->level, first, n};
-  HIP_TRY(hipEventRecord(b->ev0, b->stream));
-  if (!fs::launch_bands(a, p, b->stream)) return fail(std::string("fs_batch_integral_bands") + kNoReduceKernels);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(b->ev1, b->stream));
-  b->timed = true; b->launches = 1;
-  if (moments && fetch(b, moments, p.moments, n_mom * sizeof(double))) return -1;
-  if (want_q && fetch(b, quantiles, p.quantiles, n_qu * sizeof(double))) return -1;
-  if (n_members && fetch(b, n_members, p.n_members, (size_t)n * sizeof(int32_t))) return -1;
-  return 0;
+  point_bands(p, lay, blk, b->red_in[1].get<const double>(), n_q, moments != nullptr, n_members != nullptr);
+  if (post_launch(b, entry, integrals ? 1 : 0, [&](auto real) {
+        if (!integrals) return fs::launch_bands(reduce_args<decltype(real)>(b, first, n), p, b->stream);
+        const fs::ReduceArgs<double> a{b->integ.get<const double>(), b->status.get<const int32_t>(), b->iters.get<const int32_t>(), b->d.n_reaches,
+                                       b->level, first, n};
+        return fs::launch_bands(a, p, b->stream);
+      })) return -1;
+  return fetch_bands(b, lay, blk, moments, quantiles, nullptr, n_members);
+}
+
+int fs_batch_bands(fs_batch *b, int32_t first, int32_t n, const double *q, int32_t n_q, double *moments, double *quantiles,
+                   int32_t *n_members) {
+  return band_rows(b, "fs_batch_bands", false, first, n, q, n_q, moments, quantiles, n_members);
+}
+
+int fs_batch_integral_bands(fs_batch *b, int32_t first, int32_t n, const double *q, int32_t n_q, double *moments, double *quantiles,
+                            int32_t *n_members) {
+  return band_rows(b, "fs_batch_integral_bands", true, first, n, q, n_q, moments, quantiles, n_members);
 }
 
 void *fs_batch_hydrograph_device_ptr(fs_batch *b) { return b ? b->hydro.get() : nullptr; }

@@ -108,10 +108,7 @@ template <typename R> struct IntegralArgs {
   int32_t B, N, section_mode;
   const R *src;                   // row (k, r) of the range starts at src + k level_stride + r N
   int64_t level_stride;           // B N: the depth history from the range's first level on; 0: the current state (a range of one row)
-  const R *geo_uniform, *geo_table;
-  const R *poly_x, *poly_z;       // IRREGULAR (see KernelArgs)
-  const int32_t *poly_n;
-  int64_t geo_reach_stride, poly_reach_stride;      // per-reach tables (see KernelArgs), 0: shared
+  SectionTables<R> sec;
   const int32_t *reach_nodes;     // [B] or nullptr (see DeriveArgs)
   ReduceArgs<R> rows;             // status, Newton counts and the range: red_rows says how many rows of a reach enter
   const double *dx;               // [B]: the caller's fp64 node spacing of each reach
@@ -120,6 +117,7 @@ template <typename R> struct IntegralArgs {
   double *integ;                  // [max_levels][FS_INT_NROWS][B]: the handle's block (not the range's part of it)
   int32_t *mark;                  // [max_levels][B]: 1 where a row holds integrals
 };
+FS_ARGS_LAYOUT(IntegralArgs, 176, 32, reach_nodes, 88);
 
 // One wavefront per (level, reach) row, four rows per 256-thread workgroup; consecutive waves take consecutive reaches of a level, so the
 // grid streams the depth history once, in address order.  A lane takes the packs of V consecutive nodes (16 bytes) that lane_packs
@@ -129,8 +127,8 @@ template <typename R> struct IntegralArgs {
 // same instantiation, the same assignment of nodes to lanes).
 // Loads: a row starts at element r N, which for odd N is no 16-byte boundary.  A pack is one 16-byte load only when its own address is
 // aligned and all V nodes exist; every other pack is read element by element.  No address outside [row, row + nodes) is touched.
-// Area and top width are evaluated in the batch's type by the lines of derive_fields_kernel (fs_derive.hpp), repeated here so that its
-// machine code stays what it is; the section parameters are read per row (shared tables: from L1 / L2; per-reach tables: eight values
+// Area and top width are evaluated in the batch's type by the helpers derive_fields_kernel calls (section_at, section_area_top:
+// fs_derive.hpp), inlined here; the section parameters are read per row (shared tables: from L1 / L2; per-reach tables: eight values
 // per node and row from L2 / MALL).  Products with the weights and all sums are fp64.
 // A wave that takes 2 or 4 consecutive rows in turn, their loads in flight together and shared tables read once, was measured and not
 // kept (158 and 256 VGPRs, 3 and 1 waves per SIMD; the C4 history in 2.93 and 5.21 ms against 2.88 ms); two short
@@ -164,38 +162,9 @@ template <typename R, int V> __global__ __launch_bounds__(256) void reach_integr
       const int node = i0 + (e < cnt ? e : 0);
       SecParams<R> se;
       PolyNode<R> pnode;
-      pnode.n = 0;
-      if (a.section_mode == FS_SEC_TABLE || a.section_mode == FS_SEC_IRREGULAR) {
-        auto g = [&](int grow) { return a.geo_table[(size_t)reach * a.geo_reach_stride + (size_t)grow * a.N + node]; };
-        se.z = g(FS_GEO_Z_BED); se.b = g(FS_GEO_B_MAIN); se.m = g(FS_GEO_M_MAIN);
-        se.compound = g(FS_GEO_IS_COMPOUND) > R(0.5);
-        se.hbf = g(FS_GEO_H_BANKFULL); se.bl = g(FS_GEO_B_FP_LEFT); se.br = g(FS_GEO_B_FP_RIGHT); se.mfp = g(FS_GEO_M_FP);
-        if (a.section_mode == FS_SEC_IRREGULAR) {
-          const size_t po = (size_t)reach * a.poly_reach_stride, no = a.poly_reach_stride ? (size_t)reach * a.N : 0;
-          if (a.poly_n[no + node] > 0) {
-            pnode.x = a.poly_x + po + node; pnode.z = a.poly_z + po + node; pnode.stride = a.N; pnode.n = a.poly_n[no + node];
-            pnode.tz = nullptr; pnode.K = 0; pnode.KP = 0;
-          }
-        }
-      } else {
-        const R z_us = a.geo_uniform[(size_t)FS_RU_Z_US * a.B + reach], z_ds = a.geo_uniform[(size_t)FS_RU_Z_DS * a.B + reach];
-        const R w2 = R(node) * (R(1) / R(nodes_r - 1));       // the reach's own node count, as Geometry<R, *_UNIFORM>::bed
-        se.z = z_us * (R(1) - w2) + z_ds * w2;
-        se.b = a.geo_uniform[(size_t)FS_RU_WIDTH * a.B + reach];
-        se.m = a.section_mode == FS_SEC_TRAP_UNIFORM ? a.geo_uniform[(size_t)FS_TU_SIDE_SLOPE * a.B + reach] : R(0);
-        se.compound = false; se.hbf = se.bl = se.br = se.mfp = R(0);
-      }
-      // area and top width: cross_section.py:623-679 (incl. the over-bank convention)
-      const R d = fmax_(R(0), h[e]);
-      R Te = se.b + R(2) * se.m * d;
-      R Ae = (se.b + Te) / R(2) * d;
-      if (se.compound && d > se.hbf) {
-        const R dfp = d - se.hbf, Tb = se.b + R(2) * se.m * se.hbf;
-        Ae = (se.b + Tb) / R(2) * se.hbf + (se.bl + R(0.5) * se.mfp * dfp) * dfp + (se.br + R(0.5) * se.mfp * dfp) * dfp;
-        Te = (se.bl + Tb + se.br) + R(2) * se.mfp * dfp;
-      }
-      if (d <= R(0)) { Ae = R(0); Te = R(0); }
-      if (pnode.n > 0) poly_area_top(pnode, h[e] + se.z, Ae, Te);     // cross_section.py:248-328
+      R Te, Ae;
+      section_at(a.sec, a.section_mode, a.B, a.N, reach, node, nodes_r, se, pnode);
+      section_area_top(se, pnode, h[e], Ae, Te);
       bool over = false;
       if (a.threshold) over = h[e] + se.z >= a.threshold[a.threshold_per_reach ? (size_t)reach * a.N + node : (size_t)node];
       if (e < cnt) {

@@ -82,10 +82,7 @@ namespace fs {
 template <typename R> struct EnvelopeArgs {
   int32_t B, N, first, n, section_mode;
   const R *hist_h, *hist_Q;       // [levels][B][N]
-  const R *geo_uniform, *geo_table;
-  const R *poly_x, *poly_z;       // IRREGULAR (see KernelArgs)
-  const int32_t *poly_n;
-  int64_t geo_reach_stride, poly_reach_stride;      // per-reach tables (see KernelArgs), 0: shared
+  SectionTables<R> sec;
   const int32_t *reach_nodes;     // [B] or nullptr (see DeriveArgs)
   ReduceArgs<R> rows;             // status, Newton counts and the range: red_rows says how many rows of a reach enter
   int32_t quantities;             // FS_ENV_* bit mask: which of the six are written, in bit order
@@ -96,11 +93,12 @@ template <typename R> struct EnvelopeArgs {
   double *crossing;               // [FS_ENV_NCROSS][B][N] or nullptr
   int32_t *levels;                // [B]: rows that entered
 };
+FS_ARGS_LAYOUT(EnvelopeArgs, 192, 40, reach_nodes, 96);
 
 // One thread per V consecutive (reach, node) elements, as derive_fields_kernel: 16-byte history loads, consecutive threads on consecutive
 // elements.  16 B in per element and level and nothing out until the walk is over: the loads of U levels are issued before the first of
-// them is used.  Each quantity is evaluated by the lines of derive_fields_kernel (fs_derive.hpp), repeated here so that its machine code
-// stays what it is; what no selected quantity needs (the area, the divisions, the square root) is skipped, uniformly over the grid -
+// them is used.  The section, its area and its top width come from the helpers derive_fields_kernel calls (section_at, section_area_top:
+// fs_derive.hpp), inlined here; what no selected quantity needs (the area, the divisions, the square root) is skipped, uniformly over the grid -
 // with all six selected the walk is bound by its fp64 divisions, as derive_fields_kernel is, not by HBM.  kNeed: the quantities this
 // instantiation can walk - kEnvPlain (depth, stage, flow: no section, a third of the registers, twice the waves) or FS_ENV_ALL.
 constexpr int kEnvPlain = FS_ENV_DEPTH | FS_ENV_STAGE | FS_ENV_FLOW;
@@ -132,27 +130,7 @@ template <typename R, int V, int U, int kNeed> __global__ __launch_bounds__(256)
     if (node == 0 && e < cnt && a.levels) a.levels[reach] = rows[e];
     most = rows[e] > most ? rows[e] : most;
     thr[e] = a.cross_q >= 0 ? a.threshold[a.threshold_per_reach ? i : (size_t)node] : R(0);
-    pnode[e].n = 0;
-    if (a.section_mode == FS_SEC_TABLE || a.section_mode == FS_SEC_IRREGULAR) {
-      auto g = [&](int row) { return a.geo_table[(size_t)reach * a.geo_reach_stride + (size_t)row * a.N + node]; };
-      s[e].z = g(FS_GEO_Z_BED); s[e].b = g(FS_GEO_B_MAIN); s[e].m = g(FS_GEO_M_MAIN);
-      s[e].compound = g(FS_GEO_IS_COMPOUND) > R(0.5);
-      s[e].hbf = g(FS_GEO_H_BANKFULL); s[e].bl = g(FS_GEO_B_FP_LEFT); s[e].br = g(FS_GEO_B_FP_RIGHT); s[e].mfp = g(FS_GEO_M_FP);
-      if (a.section_mode == FS_SEC_IRREGULAR) {
-        const size_t po = (size_t)reach * a.poly_reach_stride, no = a.poly_reach_stride ? (size_t)reach * a.N : 0;
-        if (a.poly_n[no + node] > 0) {
-          pnode[e].x = a.poly_x + po + node; pnode[e].z = a.poly_z + po + node; pnode[e].stride = a.N; pnode[e].n = a.poly_n[no + node];
-          pnode[e].tz = nullptr; pnode[e].K = 0; pnode[e].KP = 0;
-        }
-      }
-    } else {
-      const R z_us = a.geo_uniform[(size_t)FS_RU_Z_US * a.B + reach], z_ds = a.geo_uniform[(size_t)FS_RU_Z_DS * a.B + reach];
-      const R w2 = R(node) * (R(1) / R(nodes_r - 1));       // the reach's own node count, as Geometry<R, *_UNIFORM>::bed
-      s[e].z = z_us * (R(1) - w2) + z_ds * w2;
-      s[e].b = a.geo_uniform[(size_t)FS_RU_WIDTH * a.B + reach];
-      s[e].m = a.section_mode == FS_SEC_TRAP_UNIFORM ? a.geo_uniform[(size_t)FS_TU_SIDE_SLOPE * a.B + reach] : R(0);
-      s[e].compound = false; s[e].hbf = s[e].bl = s[e].br = s[e].mfp = R(0);
-    }
+    section_at(a.sec, a.section_mode, a.B, a.N, reach, node, nodes_r, s[e], pnode[e]);
     env_begin(crs[e]);
 #pragma unroll
     for (int q = 0; q < kEnvQuantities; ++q) env_begin(ext[e][q]);
@@ -179,21 +157,9 @@ template <typename R, int V, int U, int kNeed> __global__ __launch_bounds__(256)
 #pragma unroll
       for (int e = 0; e < V; ++e) {
         if (beyond[e]) { h[e] = R(1); Q[e] = R(0); }        // (never written by the step kernel)
-        // area and top width: cross_section.py:623-679 (incl. the over-bank convention)
         const SecParams<R> &se = s[e];
         R Ae = R(0), Te = R(0), Ve = R(0), Fre = R(0);
-        if (need_area) {
-          const R d = fmax_(R(0), h[e]);
-          Te = se.b + R(2) * se.m * d;
-          Ae = (se.b + Te) / R(2) * d;
-          if (se.compound && d > se.hbf) {
-            const R dfp = d - se.hbf, Tb = se.b + R(2) * se.m * se.hbf;
-            Ae = (se.b + Tb) / R(2) * se.hbf + (se.bl + R(0.5) * se.mfp * dfp) * dfp + (se.br + R(0.5) * se.mfp * dfp) * dfp;
-            Te = (se.bl + Tb + se.br) + R(2) * se.mfp * dfp;
-          }
-          if (d <= R(0)) { Ae = R(0); Te = R(0); }
-          if (pnode[e].n > 0) poly_area_top(pnode[e], h[e] + se.z, Ae, Te);     // cross_section.py:248-328
-        }
+        if (need_area) section_area_top(se, pnode[e], h[e], Ae, Te);
         if (need & FS_ENV_VELOCITY) Ve = Q[e] / Ae;
         if (need & FS_ENV_FROUDE) {              // hydraulics.py:155-168 with its clamps
           const R Vc = Q[e] / fmax_(Ae, R(1e-6)), D = Ae / fmax_(Te, R(1e-6));

@@ -141,6 +141,8 @@ FS_RED_HD double quantile_lerp(double a, double b, double gamma) {
   return v;
 }
 
+constexpr int kBandMaxQ = 16;                    // quantile levels per call of the band kernels (fs_host_post.hpp checks it)
+
 }  // namespace fs
 
 #if defined(__HIPCC__)
@@ -217,7 +219,6 @@ __global__ __launch_bounds__(256) void lookup_finish_kernel(const ReduceArgs<R> 
 
 // ---- cross-member bands ----
 constexpr int kBandThreads = 256;
-constexpr int kBandMaxQ = 16;                    // quantile levels per call
 constexpr int kBandTargets = 2 * kBandMaxQ;      // order statistics: the two around every virtual index
 
 // the order-preserving integer image of a double (-0.0 has been folded into +0.0 before): negative values reversed below the positive

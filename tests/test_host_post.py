@@ -1,0 +1,211 @@
+"""Host side of the post-processing entry points (fs_batch_summarize ... fs_batch_integral_bands): their range and quantile checks,
+the rows of an envelope and the layouts of their result blocks are plain C++ in flow-sim_amd/csrc/fs_host_post.hpp.
+tests/host_post/host_post_driver.cpp is built here with the system compiler under AddressSanitizer and UBSan and run as a program.
+The texts and the arithmetic it is held to are written out below as the entry points of fs_abi.hip stated them before the header
+existed."""
+import os
+import subprocess
+
+import pytest
+
+from conftest import ROOT
+
+CSRC = os.path.join(ROOT, "flow-sim_amd", "csrc")
+DRIVER = os.path.join(ROOT, "tests", "host_post", "host_post_driver.cpp")
+INT32_MAX = 2 ** 31 - 1
+MAXQ, NSTAT, NCROSS, CROSSING, NQUANT = 16, 4, 3, 64, 6
+HYDRO, HISTORY = "the hydrograph rows before it were not restored", "the history before it was not restored"
+BOUNDS, NULL_Q, OUTSIDE = "entry: n_q must be 0 .. 16", "entry: null quantile levels", "entry: quantile levels must be in [0, 1]"
+
+
+def not_inside(first, end, level):
+    return f"entry: levels [{first}, {end}) are not inside 0 .. {level}, the levels this batch has computed"
+
+
+# request -> the text the entry points gave (level 10 throughout)
+RANGE = {
+    "range -1 1 10 0 0": not_inside(-1, 0, 10),
+    "range 0 0 10 0 0": not_inside(0, 0, 10),
+    "range 3 -2 10 0 0": not_inside(3, 1, 10),
+    "range 0 12 10 0 0": not_inside(0, 12, 10),                                  # first + n = level + 2
+    "range 11 1 10 0 0": not_inside(11, 12, 10),
+    f"range {INT32_MAX} 2 10 0 0": not_inside(INT32_MAX, INT32_MAX + 2, 10),        # the sum does not fit int32
+    "range 0 11 10 0 0": "",                                                     # the exact fit [0, level + 1)
+    "range 10 1 10 0 0": "",
+    "range 2 1 10 3 0": "entry: this batch was restarted at level 3; " + HYDRO,
+    "range 2 1 10 3 1": "entry: this batch was restarted at level 3; " + HISTORY,
+    "range 3 1 10 3 0": "",
+    "range 3 8 10 3 1": "",
+    "range 0 11 10 3 1": "entry: this batch was restarted at level 3; " + HISTORY,
+    "range -1 1 10 3 0": not_inside(-1, 0, 10),                                  # two faults: the range comes first
+}
+LEVELS16 = " ".join(repr(i / 15) for i in range(16))
+QUANT = {
+    "quant -1 null": BOUNDS,
+    "quant -1 0.5": BOUNDS,
+    "quant 0 null": "",
+    "quant 0": "",
+    f"quant {MAXQ} {LEVELS16}": "",
+    f"quant {MAXQ + 1} {LEVELS16} 0.5": BOUNDS,
+    "quant 2 null": NULL_Q,
+    "quant 3 -0.0 0 1": "",
+    f"quant 1 {1.0 + 2.0 ** -52!r}": OUTSIDE,
+    "quant 1 nan": OUTSIDE,
+    f"quant 1 {-(2.0 ** -1074)!r}": OUTSIDE,
+    "quant 3 0.5 0.25 1.5": OUTSIDE,                                             # a bad level after good ones
+    "quant 3 0.5 0.25 nan": OUTSIDE,
+    f"quant {MAXQ + 1} null": BOUNDS,                                            # two faults at once: the first text
+    f"quant {MAXQ + 1} {LEVELS16} 7.0": BOUNDS,
+}
+LOOKUP_ARGS = {
+    "lookupargs 0 3 1 1 1 1": "",
+    "lookupargs 3 0 1 65535 0 0": "",
+    "lookupargs -1 0 1 1 0 0": "fs_batch_lookup: x_row and y_row are 0..3 (h[0], Q[0], h[N-1], Q[N-1])",
+    "lookupargs 0 4 1 1 0 0": "fs_batch_lookup: x_row and y_row are 0..3 (h[0], Q[0], h[N-1], Q[N-1])",
+    "lookupargs 0 0 1 0 0 0": "fs_batch_lookup: n_q must be 1 .. 65535",
+    "lookupargs 0 0 1 65536 0 0": "fs_batch_lookup: n_q must be 1 .. 65535",
+    "lookupargs 0 0 0 1 0 0": "fs_batch_lookup: null query abscissae",
+    "lookupargs 0 0 1 1 0 1": "fs_batch_lookup: rmse needs a target",
+    "lookupargs 4 0 0 0 0 1": "fs_batch_lookup: x_row and y_row are 0..3 (h[0], Q[0], h[N-1], Q[N-1])",      # every fault: the first text
+    "lookupargs 0 0 0 0 0 1": "fs_batch_lookup: n_q must be 1 .. 65535",
+}
+QINDEX = {1: 0, 2: 1, 4: 2, 8: 3, 16: 4, 32: 5, 0: -1, 3: -1, 64: -1, -1: -1, 128: -1}
+
+
+def envelope_rows(mask, crossings):
+    """every row of an envelope in the order fs_batch_envelope lays them out: (quantity bit or CROSSING, statistic)"""
+    rows = [(1 << k, stat) for k in range(NQUANT) if mask >> k & 1 for stat in range(NSTAT)]
+    return rows + ([(CROSSING, stat) for stat in range(NCROSS)] if crossings else [])
+
+
+def row_queries():
+    """(mask, crossings, quantity, stat, row or -1): every row of every mask by enumeration, and what has no row"""
+    out = []
+    for mask in range(1, 64):
+        for crossings in (0, 1):
+            rows = envelope_rows(mask, crossings)
+            where = {key: i for i, key in enumerate(rows)}
+            assert len(where) == len(rows)
+            for k in range(NQUANT):
+                for stat in range(-1, NSTAT + 1):                                   # stat = -1 and FS_ENV_NSTAT: no row
+                    out.append((mask, crossings, 1 << k, stat, where.get((1 << k, stat), -1)))
+            for stat in range(-1, NCROSS + 1):
+                out.append((mask, crossings, CROSSING, stat, where.get((CROSSING, stat), -1)))
+            for quantity in (0, 3, mask | CROSSING, 1 | 32, 128):                   # two bits set, no bit, not a quantity
+                if quantity not in (1, 2, 4, 8, 16, 32, 64):
+                    out.append((mask, crossings, quantity, 0, -1))
+    return out
+
+
+BAND_SHAPES = [(n, n_q) for n in (1, 3) for n_q in (0, 5)]
+PROFILE_SHAPES = [(N, n_q) for N in (1, 5) for n_q in (0, 5)]
+LOOKUP_SHAPES = [(n_q, B) for n_q in (1, 5) for B in (1, 3)]
+
+
+@pytest.fixture(scope="module")
+def answers(tmp_path_factory):
+    tmp = tmp_path_factory.mktemp("host_post")
+    exe = str(tmp / "host_post_driver")
+    cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+           "-fno-omit-frame-pointer", "-I", CSRC, "-o", exe, DRIVER]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    requests = ["consts"] + list(RANGE) + list(QUANT) + list(LOOKUP_ARGS) + [f"qindex {q}" for q in QINDEX]
+    requests += [f"rows {mask} {c}" for mask in range(1, 64) for c in (0, 1)]
+    requests += [f"rowof {m} {c} {q} {s}" for m, c, q, s, _ in row_queries()]
+    requests += [f"band {n} 4 {n_q} 0" for n, n_q in BAND_SHAPES] + [f"band {N} 1 {n_q} 1" for N, n_q in PROFILE_SHAPES]
+    requests += [f"lookup {n_q} {B}" for n_q, B in LOOKUP_SHAPES]
+    path = tmp / "requests.txt"
+    path.write_text("\n".join(requests) + "\n")
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    r = subprocess.run([exe, str(path)], capture_output=True, text=True, env=env, timeout=60)
+    assert r.returncode == 0 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
+    lines = r.stdout.split("\n")[:-1]
+    assert len(lines) == len(requests)
+    return dict(zip(requests, lines))
+
+
+def test_the_constants_are_the_headers(answers):
+    assert answers["consts"].split() == [str(v) for v in (MAXQ, NSTAT, NCROSS, CROSSING, NQUANT)]
+
+
+@pytest.mark.parametrize("request_line", list(RANGE))
+def test_computed_range_check(answers, request_line):
+    assert answers[request_line] == RANGE[request_line]
+
+
+@pytest.mark.parametrize("request_line", list(QUANT))
+def test_quantile_level_check(answers, request_line):
+    assert answers[request_line] == QUANT[request_line]
+
+
+@pytest.mark.parametrize("request_line", list(LOOKUP_ARGS))
+def test_lookup_argument_check(answers, request_line):
+    assert answers[request_line] == LOOKUP_ARGS[request_line]
+
+
+def test_threshold_quantity_index(answers):
+    assert {q: int(answers[f"qindex {q}"]) for q in QINDEX} == QINDEX
+
+
+def test_envelope_row_counts_of_every_mask(answers):
+    for mask in range(1, 64):
+        for c in (0, 1):
+            n_sel = bin(mask).count("1")
+            # fs_batch_envelope_device: n_sel quantities of FS_ENV_NSTAT rows, the crossings behind them
+            assert [int(v) for v in answers[f"rows {mask} {c}"].split()] == [n_sel, n_sel * NSTAT, n_sel * NSTAT + (NCROSS if c else 0)]
+            assert len(envelope_rows(mask, c)) == n_sel * NSTAT + (NCROSS if c else 0)
+
+
+def test_row_of_agrees_with_the_enumeration_and_refuses_the_rest(answers):
+    queries = row_queries()
+    found = refused = 0
+    for m, c, q, s, want in queries:
+        assert int(answers[f"rowof {m} {c} {q} {s}"]) == want, (m, c, q, s)
+        found += want >= 0
+        refused += want < 0
+    assert found == sum(len(envelope_rows(m, c)) for m in range(1, 64) for c in (0, 1)) and refused > found
+    # the kinds of refusal are all among them
+    assert (1, 0, 2, 0, -1) in queries and (1, 0, 1, NSTAT, -1) in queries and (3, 1, 3, 0, -1) in queries
+    assert (63, 0, CROSSING, 0, -1) in queries and (63, 1, CROSSING, NCROSS, -1) in queries and (63, 1, CROSSING, NCROSS - 1, 27 - 1) in queries
+
+
+def check_blocks(blocks, total):
+    """blocks: (byte offset, byte size) in today's order - disjoint, back to back, and the whole of the reserved bytes"""
+    end = 0
+    for off, size in blocks:
+        assert off == end
+        end = off + size
+    assert end == total
+
+
+@pytest.mark.parametrize("n,n_q", BAND_SHAPES)
+def test_band_layout_of_bands_and_integral_bands(answers, n, n_q):
+    series, n_mom, n_qu, moments, quantiles, extra, members, size = (int(v) for v in answers[f"band {n} 4 {n_q} 0"].split())
+    # moments [n][4][4], then quantiles [n][4][n_q], then n_members [n]
+    assert (series, n_mom, n_qu) == (n, n * 16, n * 4 * n_q)
+    assert (moments, quantiles, members) == (0, n * 16, n * 16 + n * 4 * n_q) and extra == members
+    assert size == (n * 16 + n * 4 * n_q) * 8 + n * 4
+    check_blocks([(moments * 8, n_mom * 8), (quantiles * 8, n_qu * 8), (members * 8, n * 4)], size)
+    assert members * 8 % 8 == 0
+
+
+@pytest.mark.parametrize("N,n_q", PROFILE_SHAPES)
+def test_band_layout_of_profile_bands(answers, N, n_q):
+    series, n_mom, n_qu, moments, quantiles, extra, members, size = (int(v) for v in answers[f"band {N} 1 {n_q} 1"].split())
+    # moments [N][4], then quantiles [N][n_q], then exceed [N] (always reserved), then n_members [N]
+    assert (series, n_mom, n_qu) == (N, N * 4, N * n_q)
+    assert (moments, quantiles, extra, members) == (0, N * 4, N * 4 + N * n_q, N * 4 + N * n_q + N)
+    assert size == (N * 4 + N * n_q + N) * 8 + N * 4
+    check_blocks([(moments * 8, n_mom * 8), (quantiles * 8, n_qu * 8), (extra * 8, N * 8), (members * 8, N * 4)], size)
+    assert members * 8 % 8 == 0
+
+
+@pytest.mark.parametrize("n_q,B", LOOKUP_SHAPES)
+def test_lookup_layout(answers, n_q, B):
+    n_val, values, rmse, info, size = (int(v) for v in answers[f"lookup {n_q} {B}"].split())
+    # values [n_q][B], then rmse [B], then info [B]
+    assert (n_val, values, rmse, info) == (n_q * B, 0, n_q * B, n_q * B + B)
+    assert size == (n_q * B + B) * 8 + B * 4
+    check_blocks([(values * 8, n_val * 8), (rmse * 8, B * 8), (info * 8, B * 4)], size)
+    assert info * 8 % 8 == 0
