@@ -122,6 +122,34 @@ def bc(form, kind, params, sec, level, dt, h, Q, Qold, Yprev, tgt):
     return dict(res=out[0], dh=out[1], dq=out[2], Ynew=out[3], flag=flag)
 
 
+STORAGE_OPS = dict(area_at=0, net_vol=1, outflow=2, storage_root=3)
+
+
+def storage_parts(op, params, dt, a, b=None):
+    """one part of the general reservoir row on a shared FS_BC_STORAGE_CURVE parameter block: area_at(a), net_vol(a, b, step),
+    outflow(a) or storage_root(Yold = a, vol_in = b, dt, step); returns (value, flag)"""
+    D = a.dtype.type
+    a = _in(a, D)
+    b = np.zeros_like(a) if b is None else _in(b, D)
+    p = _in(params, D)
+    out = np.empty((2, len(a)), dtype=D)
+    _call("fsp_storage_parts", a, STORAGE_OPS[op], p, len(p), D(dt), a, b, out, len(a))
+    return out[0], out[1].astype(np.int32)
+
+
+def bc_general(kind, params, sec, level, dt, h, Q, Qold, Yprev):
+    """bc_eval<true> for FS_BC_STORAGE_CURVE / FS_BC_HOST_ROW with the parameters in global memory; params 1-d: shared by all
+    elements (stride 0), 2-d [n_params][n]: element i reads column i (stride 1).  Returns res, dh, dq, Ynew, flag"""
+    D = h.dtype.type
+    arrays = [_in(a, D) for a in (h, Q, Qold, Yprev)]
+    p = _in(params, D)
+    assert p.ndim == 1 or p.shape[1] == len(h)
+    out = np.empty((4, len(h)), dtype=D)
+    flag = np.full(len(h), -1, dtype=np.int32)
+    _call("fsp_bc_general", arrays[0], kind, p, p.shape[0], p.ndim - 1, HR.sec_array(sec, D), level, D(dt), *arrays, out, flag, len(h))
+    return dict(res=out[0], dh=out[1], dq=out[2], Ynew=out[3], flag=flag)
+
+
 # ---- probe_reduce.hip: the launchers of the post-processing kernels on arrays of the caller's choice ---------------------------
 def _ptr(a, dtype):
     if a is None:

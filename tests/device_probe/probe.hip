@@ -3,11 +3,17 @@
 // tests/device_probe/libfs_probe.so by its own Makefile target, with the library's flags (-ffp-contract=on: the helpers' arithmetic
 // follows the source, as it does inside the step kernels).
 //
-// Every kernel: one thread per element, a bounds check, no data-dependent loop.  Every host wrapper takes HOST pointers, allocates,
-// copies in, launches, synchronises, copies out, frees, and returns the first HIP error (0 = hipSuccess).  Arrays with several
-// fields per element are field-major: out[f * n + i].
+// Every kernel: one thread per element, a bounds check, no data-dependent loop - except the two kernels of the general reservoir row
+// (k_storage_parts, k_bc_general), whose functions carry their own: the binary search of area_at over the n_curve breakpoints, the
+// trapezoid of net_vol with (int)(|Y2 - Y1| / step) points, and the Brent loop of storage_root, which evaluates the balance at most
+// 102 times (two bracket ends and 100 iterations), each evaluation a trapezoid of at most (Y_max - Y_min) / step points when Yold is
+// inside the bracket.  The recipes (tests/helper_recipes.py) keep that quotient <= 64; the host wrappers refuse a parameter block
+// whose curve does not fit its n_params and a stage that would make a trapezoid of more than kMaxTrapezoid points.
+// Every host wrapper takes HOST pointers, allocates, copies in, launches, synchronises, copies out, frees, and returns the first HIP
+// error (0 = hipSuccess).  Arrays with several fields per element are field-major: out[f * n + i].
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cmath>
 #include <type_traits>
 #include <vector>
 #include "../../flow-sim_amd/csrc/fs_device.hpp"
@@ -148,6 +154,54 @@ __global__ void k_bc(int form, int kind, const R *params, const R *sec, int leve
   flag[i] = fl;
 }
 
+// the smallest gap of the area curve's stages, as bc_storage_curve computes it (1 without a curve)
+template <typename R> __device__ __forceinline__ R storage_step(const StorageCurve<R> &sc) {
+  R step = R(1);
+  for (int j = 0; j + 1 < sc.nc; ++j) {
+    const R d = fabs_(sc.xs(j + 1) - sc.xs(j));
+    step = j == 0 ? d : (d < step ? d : step);
+  }
+  return step;
+}
+
+// the parts of the general reservoir row on one shared parameter block in global memory (stride 0).  out: value, flag
+enum { SOP_AREA = 0, SOP_NET_VOL, SOP_OUTFLOW, SOP_ROOT, SOP_COUNT };
+
+template <typename R> __global__ void k_storage_parts(int op, const R *params, R dt, const R *a, const R *b, R *out, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  BCDesc<R> bc;
+  bc.kind = FS_BC_STORAGE_CURVE; bc.stride = 0; bc.params = params; bc.target = nullptr; bc.tgt = R(0);
+  StorageCurve<R> sc{bc, 0, 1, 0};
+  sc.nc = (int)sc.p(FS_SC_N_CURVE);
+  int fl = FS_OK;
+  R r = R(0);
+  switch (op) {
+    case SOP_AREA: r = sc.area_at(a[i]); break;
+    case SOP_NET_VOL: r = sc.net_vol(a[i], b[i], storage_step(sc)); break;
+    case SOP_OUTFLOW: r = sc.outflow(a[i]); break;
+    default: r = storage_root(sc, a[i], b[i], dt, storage_step(sc), &fl); break;
+  }
+  out[i] = r; out[(size_t)n + i] = R(fl);
+}
+
+// bc_eval<true> for FS_BC_STORAGE_CURVE and FS_BC_HOST_ROW, parameters in global memory as the step kernels of boundary class -1
+// read them: stride 0 (one block, reach 0, B 1) or stride 1 (params[n_params][n], element i reads column i).  out: res, dh, dq, Ynew
+template <typename R>
+__global__ void k_bc_general(int kind, const R *params, int stride, const R *sec, int level, R dt, const R *h, const R *Q,
+                             const R *Qold, const R *Yprev, R *out, int *flag, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  BCDesc<R> bc;
+  bc.kind = kind; bc.stride = stride; bc.params = params; bc.target = nullptr; bc.tgt = R(0);
+  R Ynew = R(0);
+  int fl = FS_OK;
+  const BCRow<R> r = bc_eval<true>(bc, stride ? i : 0, stride ? n : 1, level, section_from(sec), h[i], Q[i], Qold[i], dt, Yprev[i], &Ynew, &fl);
+  const size_t N = (size_t)n;
+  out[i] = r.res; out[N + i] = r.dh; out[2 * N + i] = r.dq; out[3 * N + i] = Ynew;
+  flag[i] = fl;
+}
+
 // ---- host side -----------------------------------------------------------------------------------------------------------
 inline dim3 grid_for(int n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
 
@@ -203,7 +257,8 @@ template <typename R> int blend(int rcp, const R *p, const R *z, R *y, int n) {
 template <typename R>
 int bc_rows(int form, int kind, const R *params, const R *sec, int level, R dt, const R *h, const R *Q, const R *Qold, const R *Yprev,
             const R *tgt, R *out, int *flag, int n) {
-  // the closed-form kinds only: the Brent row and the host row are not probed; bc_eval_rect has no power rating row
+  // the closed-form kinds only, their parameters in LDS: the Brent row and the host row read theirs from global memory and go
+  // through bc_general below; bc_eval_rect has no power rating row
   if (n <= 0 || form < 0 || form > 1 || kind < FS_BC_FLOW_HYDROGRAPH || kind > FS_BC_STORAGE) return kBadArg;
   if (form == 1 && kind == FS_BC_RATING_POWER) return kBadArg;
   Call c;
@@ -211,6 +266,67 @@ int bc_rows(int form, int kind, const R *params, const R *sec, int level, R dt, 
   const R *dh = c.in(h, n), *dQ = c.in(Q, n), *dQo = c.in(Qold, n), *dY = c.in(Yprev, n), *dt_ = c.in(tgt, n);
   R *dout = c.out(out, (size_t)4 * n); int *dflag = c.out(flag, n);
   if (c.ok()) hipLaunchKernelGGL(k_bc<R>, grid_for(n), dim3(kBlock), 0, 0, form, kind, dp, ds, level, dt, dh, dQ, dQo, dY, dt_, dout, dflag, n);
+  return c.finish();
+}
+
+// Host-side guard of the two kernels with data-dependent loops: column `col` of the block holds a curve that fits n_params, with
+// ascending finite stages, and a trapezoid from `y` to either bracket end has at most kMaxTrapezoid points (a NaN stage gives n = 0
+// on the device and passes).
+constexpr int kMaxTrapezoid = 4096;
+template <typename R> bool storage_block_ok(const R *params, int n_params, int stride, int B, int col, const R *ys, int n_y) {
+  auto p = [&](int i) { return stride ? params[(size_t)i * B + col] : params[i]; };
+  if (n_params < FS_SC_NFIXED) return false;
+  const R ncr = p(FS_SC_N_CURVE);
+  if (!(ncr >= R(0) && ncr <= R(1024))) return false;
+  const int nc = (int)ncr;
+  if (FS_SC_NFIXED + 2 * nc > n_params) return false;
+  R step = R(1);
+  for (int j = 0; j + 1 < nc; ++j) {
+    const R d = p(FS_SC_NFIXED + j + 1) - p(FS_SC_NFIXED + j);
+    if (!(d > R(0))) return false;
+    step = j == 0 ? d : (d < step ? d : step);
+  }
+  if (nc == 0) return true;
+  const R lo = p(FS_SC_Y_MIN), hi = p(FS_SC_Y_MAX);
+  if (!(hi - lo >= R(0)) || !((hi - lo) / step <= R(kMaxTrapezoid))) return false;
+  for (int k = 0; k < n_y; ++k) {
+    const R y = ys[k];
+    if (y != y) continue;
+    if (!(std::fabs(y - lo) / step <= R(kMaxTrapezoid)) || !(std::fabs(y - hi) / step <= R(kMaxTrapezoid))) return false;
+  }
+  return true;
+}
+
+template <typename R> int storage_parts(int op, const R *params, int n_params, R dt, const R *a, const R *b, R *out, int n) {
+  if (n <= 0 || op < 0 || op >= SOP_COUNT) return kBadArg;
+  if (!storage_block_ok<R>(params, n_params, 0, 1, 0, a, n)) return kBadArg;
+  if (op == SOP_NET_VOL && !storage_block_ok<R>(params, n_params, 0, 1, 0, b, n)) return kBadArg;
+  Call c;
+  const R *dp = c.in(params, n_params), *da = c.in(a, n), *db = c.in(b, n); R *dout = c.out(out, (size_t)2 * n);
+  if (c.ok()) hipLaunchKernelGGL(k_storage_parts<R>, grid_for(n), dim3(kBlock), 0, 0, op, dp, dt, da, db, dout, n);
+  return c.finish();
+}
+
+// stride 0: params[n_params]; stride 1: params[n_params][n]
+template <typename R>
+int bc_general(int kind, const R *params, int n_params, int stride, const R *sec, int level, R dt, const R *h, const R *Q, const R *Qold,
+               const R *Yprev, R *out, int *flag, int n) {
+  if (n <= 0 || (kind != FS_BC_STORAGE_CURVE && kind != FS_BC_HOST_ROW) || stride < 0 || stride > 1) return kBadArg;
+  if (kind == FS_BC_HOST_ROW && n_params < 3) return kBadArg;
+  if (kind == FS_BC_STORAGE_CURVE) {
+    for (int i = 0; i < n; ++i) {
+      const int col = stride ? i : 0, B = stride ? n : 1;
+      if (!storage_block_ok<R>(params, n_params, stride, B, col, nullptr, 0)) return kBadArg;
+      const R bed = stride ? params[(size_t)FS_SC_BED_LEVEL * B + col] : params[FS_SC_BED_LEVEL];
+      const R yold = level == 1 ? h[i] + bed : Yprev[i];
+      if (!storage_block_ok<R>(params, n_params, stride, B, col, &yold, 1)) return kBadArg;
+    }
+  }
+  Call c;
+  const R *dp = c.in(params, (size_t)n_params * (stride ? n : 1)), *ds = c.in(sec, 12);
+  const R *dh = c.in(h, n), *dQ = c.in(Q, n), *dQo = c.in(Qold, n), *dY = c.in(Yprev, n);
+  R *dout = c.out(out, (size_t)4 * n); int *dflag = c.out(flag, n);
+  if (c.ok()) hipLaunchKernelGGL(k_bc_general<R>, grid_for(n), dim3(kBlock), 0, 0, kind, dp, stride, ds, level, dt, dh, dQ, dQo, dY, dout, dflag, n);
   return c.finish();
 }
 }  // namespace
@@ -230,6 +346,13 @@ const char *fsp_error_string(int e) { return hipGetErrorString((hipError_t)e); }
   int fsp_bc_##S(int form, int kind, const T *params, const T *sec, int level, T dt, const T *h, const T *Q, const T *Qold,     \
                  const T *Yprev, const T *tgt, T *out, int *flag, int n) {                                                      \
     return bc_rows<T>(form, kind, params, sec, level, dt, h, Q, Qold, Yprev, tgt, out, flag, n);                                \
+  }                                                                                                                             \
+  int fsp_storage_parts_##S(int op, const T *params, int n_params, T dt, const T *a, const T *b, T *out, int n) {               \
+    return storage_parts<T>(op, params, n_params, dt, a, b, out, n);                                                            \
+  }                                                                                                                             \
+  int fsp_bc_general_##S(int kind, const T *params, int n_params, int stride, const T *sec, int level, T dt, const T *h,        \
+                         const T *Q, const T *Qold, const T *Yprev, T *out, int *flag, int n) {                                 \
+    return bc_general<T>(kind, params, n_params, stride, sec, level, dt, h, Q, Qold, Yprev, out, flag, n);                      \
   }
 FSP_BOTH(double, f64)
 FSP_BOTH(float, f32)

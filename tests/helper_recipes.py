@@ -12,7 +12,16 @@ Every bar is fixed here, before any device run, from one of four sources:
              that expression in float32 is their restatement: the rounding of b log2 x, up to |b log2 x| 2^-24 ln 2, is part of the
              documented function and of its noise alike;
   1e-12      fp64 composites, the bar of device post-processing in tests/test_gpu_postprocess_geometry.py.
-Values that are exact or shared are compared bit for bit and carry no bar."""
+Values that are exact or shared are compared bit for bit and carry no bar.
+
+The Brent root of the general reservoir row has no value to compare with at such a bar: two valid evaluation paths end up to 2 delta
+apart.  Its criterion (sc_root_brackets) is the root's own: the reference mass balance changes sign between Y - w and Y + w, or is 0
+at Y, with w = FACTOR x (max(delta_D(Y), ulp_D(Y)) + noise_f / A_min): Brent's own half-tolerance (xtol + rtol |Y|) / 2 in the device
+type, not below one ulp of Y (a bracket cannot be narrower), plus the stage error that the rounding noise of f in the device type
+(the set's worst relative noise of the plain restatement, times the magnitudes of f's terms at Y) makes through the smallest slope of f
+in the bracket.  A root point is compared only where the trapezoid of net_vol is at least SWITCH_GAP away from changing its n (f jumps
+there and two valid paths may end on different sides); a flag only where |f| at both bracket ends is FLAG_MARGIN x the noise of f or
+exactly 0.  tests/test_helper_reference.py checks both conditions, and that scipy's brentq roots meet the criterion."""
 import functools
 
 import numpy as np
@@ -252,6 +261,258 @@ def bc_cases(typ):
     return out
 
 
+# ------------------------------------------------------------------------------------------------------------------------------
+# the general reservoir row (FS_BC_STORAGE_CURVE) and the host row
+# ------------------------------------------------------------------------------------------------------------------------------
+DT_SC = 900.0
+Y_LO, Y_HI = 10.0, 20.0                                    # the bracket of every set
+CURVE2 = [[10.0, 1.0e5], [20.0, 9.0e5]]
+# gaps 1, 0.5, 1.5, 3, 4: the step is the second gap; (Y_HI - Y_LO) / step = 20 trapezoid points at the most (the probe's rule: <= 64)
+CURVE6 = [[10.0, 1.0e5], [11.0, 1.5e5], [11.5, 2.2e5], [13.0, 2.4e5], [16.0, 5.0e5], [20.0, 9.0e5]]
+POLY = dict(type="polynomial", a=3.0, b=2.0, c=-300.0, shift=0.0)          # dq/dY = 6 Y + 2 > 0, q > 0 on the bracket
+POWER = dict(type="power", a=2.5, b=1.6, shift=-9.0)                       # x = Y - 9 in 1 .. 11 over the bracket
+LOSSES = dict(reservoir_length=2.0e4, K_q=0.5)
+Z1 = 8.0                                                   # bed of the level-1 sets: Yold = h + bed, so the bed lies below the bracket
+SWITCH_GAP = 1e-3
+MAX_DROPPED = 0.05
+FLAG_MARGIN = 1000.0
+
+
+def sc_sets(D):
+    """(name, params, bed level of the section, level): the section is the compound one of the other rows"""
+    base = dict(Y_min=Y_LO, Y_max=Y_HI, min_stage=10.75, bed=Z)
+    P = lambda **kw: HR.sc_params(D, **dict(base, **kw))
+    return [
+        ("const_area", P(area=2.5e5), Z, 2),                                                   # root Yold + vol / area
+        ("curve2", P(curve=CURVE2, bed=Z1), Z1, 1),
+        ("curve6", P(curve=CURVE6), Z, 2),
+        ("curve6_alpha_beta_poly", P(curve=CURVE6, alpha=0.8, beta=0.25, rc=POLY), Z, 2),
+        ("curve6_power_shift", P(curve=CURVE6, rc=POWER, bed=Z1), Z1, 1),
+        ("curve6_poly_losses_bed_off", P(curve=CURVE6, rc=POLY, losses=LOSSES, bed=Z + 0.3), Z, 2),    # bed_level != sec.z: two depths
+        ("curve6_power_losses_same_bed", P(curve=CURVE6, alpha=1.25, rc=POWER, losses=LOSSES, bed=Z1), Z1, 1),
+    ]
+
+
+def _around(v, D):
+    v = np.asarray(v, dtype=D)
+    return np.concatenate([v, np.nextafter(v, D(-np.inf)), np.nextafter(v, D(np.inf))])
+
+
+def sc_area_points(p, rng):
+    """stages for area_at (and outflow): random ones from below the curve to above it, and Y + beta on every breakpoint, one ulp to
+    either side, below xs(0) and above xs(nc - 1)"""
+    D = p.dtype.type
+    xs, _ = HR.sc_curve(p)
+    beta = p[HR.SC["beta"]]
+    special = np.concatenate([_around(xs, D) - beta, np.array([Y_LO - 1.0, Y_LO - 0.5, Y_HI + 0.5, Y_HI + 3.0], dtype=D)])
+    return np.concatenate([special, rng.uniform(Y_LO - 1.0, Y_HI + 1.0, N_BC - len(special)).astype(D)])
+
+
+def sc_vol_points(p, rng):
+    """(Y1, Y2) for net_vol: |Y2 - Y1| / step at 1.9, 2, 2.99, 3, 3.01 with both signs, the largest n of the set, Y1 == Y2, random"""
+    D = p.dtype.type
+    step = float(HR.sc_step(p))
+    q = np.array([1.9, 2.0, 2.99, 3.0, 3.01])
+    y1 = np.concatenate([np.full(5, 14.0), np.full(5, 14.0), [Y_LO, Y_HI, 13.0, 17.5]])
+    y2 = np.concatenate([14.0 + q * step, 14.0 - q * step, [Y_HI, Y_LO, 13.0, 17.5]])
+    k = N_BC - len(y1)
+    y1 = np.concatenate([y1, rng.uniform(Y_LO, Y_HI, k)]).astype(D)
+    y2 = np.concatenate([y2, rng.uniform(Y_LO, Y_HI, k)]).astype(D)
+    return y1, y2
+
+
+ROOT_SPECIAL = ("largest_n", "floor", "at_min_stage", "f_lo_zero", "f_hi_zero", "both_negative", "both_positive", "nan")
+
+
+def sc_root_points(name, p, rng):
+    """(Yold, vol, tags) for storage_root.  A point is made from the stage Y* it should return: vol = f(Y*) + vol in float64, rounded to
+    the device type.  tags: index -> name of the special points; every other point is random with Y* 0.2 m inside the bracket."""
+    D = p.dtype.type
+    n = N_BC
+    ymin = float(p[HR.SC["min_stage"]])
+    yold = rng.uniform(Y_LO + 0.5, Y_HI - 1.0, n)
+    ystar = rng.uniform(Y_LO + 0.2, Y_HI - 0.2, n)
+    tags = {}
+    yold[0], ystar[0] = Y_LO, Y_HI - 0.2                                  # the largest n of the set
+    tags[0] = "largest_n"
+    ystar[1:9] = rng.uniform(Y_LO + 0.1, ymin - 0.05, 8)                  # a root below min_stage: the row floors it
+    tags.update({i: "floor" for i in range(1, 9)})
+    yold[9], ystar[9] = 12.0, ymin                                        # a root at min_stage
+    tags[9] = "at_min_stage"
+    yold[10:12], ystar[10], ystar[11] = 12.0, Y_LO, Y_HI                  # f(Y_min) == 0, f(Y_max) == 0 (exact with a constant area)
+    tags.update({10: "f_lo_zero", 11: "f_hi_zero"})
+    ystar[12:16] = Y_HI + np.array([1.0, 2.0, 5.0, 30.0])                 # f < 0 at both ends
+    ystar[16:20] = Y_LO - np.array([1.0, 2.0, 5.0, 30.0])                 # f > 0 at both ends
+    tags.update({i: "both_negative" for i in range(12, 16)})
+    tags.update({i: "both_positive" for i in range(16, 20)})
+    yold = yold.astype(D)
+    f0, _ = HR.sc_f(p, yold, np.zeros(n), DT_SC, ystar, np.float64, n=HR.sc_trapezoid_n(p, yold.astype(np.float64), ystar))
+    vol = f0.astype(D)                                                    # f(Y*) with vol = 0 is the volume that puts the root at Y*
+    vol[20] = np.nan
+    tags[20] = "nan"
+    if name != "const_area":                                              # not constructible exactly on a curve: ordinary root points there
+        tags = {i: t for i, t in tags.items() if t not in ("f_lo_zero", "f_hi_zero")}
+        ystar[10], ystar[11] = Y_LO + 0.3, Y_HI - 0.3
+        vol[10:12] = HR.sc_f(p, yold[10:12], np.zeros(2), DT_SC, ystar[10:12], np.float64,
+                             n=HR.sc_trapezoid_n(p, yold[10:12].astype(np.float64), ystar[10:12]))[0].astype(D)
+    return yold, vol, tags
+
+
+def sc_row_points(p, level, yold, vol, rng):
+    """(h, Q, Qold, Yprev) that hand the row the reservoir states of the root points: Yold = Yprev at level 2 and h + bed at level 1
+    (where Yprev holds a stage that must be ignored), vol = (Qold + Q) dt / 2"""
+    D = p.dtype.type
+    n = len(yold)
+    qsum = (2.0 * vol.astype(np.float64) / DT_SC)
+    Qold = (rng.uniform(0.2, 0.8, n) * qsum).astype(D)
+    Q = (qsum - Qold.astype(np.float64)).astype(D)
+    if level == 1:
+        h = (yold - p[HR.SC["bed"]]).astype(D)
+        Yprev = rng.uniform(Y_LO + 1.0, Y_HI - 1.0, n).astype(D)
+    else:
+        h = rng.uniform(0.5, 7.0, n).astype(D)
+        Yprev = yold.copy()
+    return h, Q, Qold, Yprev
+
+
+def _noise_of(fn, D, T, scale_of=lambda r: r[1]):
+    """(reference, scale, relative noise of the plain restatement in D against it)"""
+    ref = fn(T)
+    plain = fn(D)
+    return ref[0], scale_of(ref), HR.noise(plain[0], ref[0], scale_of(ref))
+
+
+@functools.lru_cache(maxsize=None)
+def sc_cases(typ):
+    """list of dicts, one per parameter set: params, sec, level, the points of each op with reference, scale and bar, and for the root:
+    yold, vol, tags, `root_mask` (the points whose returned stage is compared), `flag` (what storage_root must report), noise_f"""
+    D = TYPES[typ]
+    T = HR.reference_type(D)
+    out = []
+    for i, (name, p, z, level) in enumerate(sc_sets(D)):
+        rng = np.random.default_rng(900 + i)
+        c = dict(name=name, params=p, sec=HR.section(D, z=z, **COMPOUND), level=level, dt=D(DT_SC))
+        bar = lambda nz: COMPOSITE_F64 if typ == "f64" else FACTOR * nz
+        ya = sc_area_points(p, rng) if int(p[HR.SC["n_curve"]]) else rng.uniform(Y_LO - 1.0, Y_HI + 1.0, N_BC).astype(D)
+        ref, _, nz = _noise_of(lambda t: (HR.sc_area_at(p, ya, t), None), D, T)
+        c["area"] = dict(Y=ya, ref=ref, bar=bar(nz))
+        ref, sc, nz = _noise_of(lambda t: HR.sc_outflow(p, ya, t), D, T)
+        c["outflow"] = dict(Y=ya, ref=ref, scale=sc, bar=bar(nz))
+        y1, y2 = sc_vol_points(p, rng)
+        ref, sc, nz = _noise_of(lambda t: HR.sc_net_vol(p, y1, y2, t), D, T)
+        c["net_vol"] = dict(Y1=y1, Y2=y2, ref=ref, scale=sc, bar=bar(nz))
+        yold, vol, tags = sc_root_points(name, p, rng)
+        c.update(yold=yold, vol=vol, tags=tags, root=sc_root_expectations(p, yold, vol, tags, D, T))
+        h, Q, Qold, Yprev = c["row_pts"] = sc_row_points(p, level, yold, vol, rng)
+        # the reservoir state the row forms from them, in its own arithmetic, and what its root finder must report on it
+        with np.errstate(all="ignore"):
+            c["row_yold"] = (h + p[HR.SC["bed"]]) if level == 1 else Yprev
+            c["row_vol"] = D(0.5) * (Qold + Q) * D(DT_SC)
+        c["row_root"] = sc_root_expectations(p, c["row_yold"], c["row_vol"], tags, D, T)
+        out.append(c)
+    return out
+
+
+def sc_switch_distance(p, yold, Y):
+    """how far |Y - Yold| / step is from an integer (1 without a curve: the trapezoid never changes its form)"""
+    if int(p[HR.SC["n_curve"]]) == 0:
+        return np.ones(len(yold))
+    q = np.abs(np.asarray(Y, dtype=np.float64) - yold.astype(np.float64)) / float(HR.sc_step(p))
+    return np.abs(q - np.round(q))
+
+
+def sc_root_expectations(p, yold, vol, tags, D, T):
+    """flag: FS_OK / FS_STORAGE_RANGE from the signs of the reference f at the bracket ends (NaN: range); `end`: +-1 where f(end) == 0
+    makes storage_root return that end; noise_f: the relative rounding noise of f in D (scale: the magnitudes of its terms) over the
+    bracket ends; margin: |f| / (noise_f x scale) at each end"""
+    n = len(yold)
+    lo, hi = np.full(n, p[HR.SC["Y_min"]]), np.full(n, p[HR.SC["Y_max"]])
+    finite = np.isfinite(vol)
+    v0 = np.where(finite, vol, D(0))
+    ends = {}
+    nz = 0.0
+    for k, y in (("lo", lo), ("hi", hi)):
+        ref, mag = HR.sc_f(p, yold, v0, DT_SC, y, T)
+        plain, _ = HR.sc_f(p, yold, v0, DT_SC, y, D)
+        nz = max(nz, HR.noise(plain, ref, mag))
+        ends[k] = (ref, mag, plain)
+    zero = {k: (ends[k][2] == 0) & (ends[k][0] == 0) for k in ends}               # exact by construction: zero in D and in T
+    flo, fhi = ends["lo"][0], ends["hi"][0]
+    ok = finite & (zero["lo"] | zero["hi"] | ((flo < 0) != (fhi < 0)))
+    margin = np.minimum(np.abs(flo) / (nz * ends["lo"][1]), np.abs(fhi) / (nz * ends["hi"][1])).astype(np.float64)
+    margin = np.where(zero["lo"] | zero["hi"] | ~finite, np.inf, margin)
+    return dict(flag=np.where(ok, HR.FS_OK, HR.FS_STORAGE_RANGE).astype(np.int32), end=np.where(zero["lo"], -1, np.where(zero["hi"], 1, 0)),
+                noise_f=nz, margin=margin, is_root=ok & ~zero["lo"] & ~zero["hi"])
+
+
+def sc_root_width(c, Y, typ):
+    """w of the root criterion at the returned stages Y: FACTOR x (max(delta_D(Y), ulp_D(Y)) + noise_f / A_min), with noise_f the set's
+    relative noise of f in D times the magnitudes of f's terms at Y"""
+    D = TYPES[typ]
+    p = c["params"]
+    Y = np.asarray(Y, dtype=D)
+    _, mag = HR.sc_f(p, c["yold"], np.where(np.isfinite(c["vol"]), c["vol"], D(0)), DT_SC, Y, np.float64 if typ == "f32" else HR.LD)
+    half = np.maximum(HR.brent_delta(Y).astype(np.float64), np.spacing(np.abs(Y)).astype(np.float64))
+    return FACTOR * (half + c["root"]["noise_f"] * mag.astype(np.float64) / HR.sc_min_slope(p))
+
+
+def sc_root_brackets(c, Y, typ):
+    """the root criterion: the reference f changes sign between Y - w and Y + w, or is 0 at Y (the trapezoid's n is the one of Y).
+    Returns per point the multiple k of w / FACTOR, among 1, 2 and FACTOR, at which it holds (inf: at none): it is met where k <= FACTOR"""
+    D = TYPES[typ]
+    T = HR.reference_type(D)
+    p = c["params"]
+    Y = np.asarray(Y, dtype=D)
+    v = np.where(np.isfinite(c["vol"]), c["vol"], D(0))
+    n = HR.sc_trapezoid_n(p, c["yold"], Y)
+    w = sc_root_width(c, Y, typ) / FACTOR
+    at = HR.sc_f(p, c["yold"], v, DT_SC, Y, T, n=n)[0]
+    need = np.full(len(Y), np.inf)
+    for k in (FACTOR, 2.0, 1.0):
+        a = HR.sc_f(p, c["yold"], v, DT_SC, Y.astype(T) - T(k) * w.astype(T), T, n=n)[0]
+        b = HR.sc_f(p, c["yold"], v, DT_SC, Y.astype(T) + T(k) * w.astype(T), T, n=n)[0]
+        need = np.where((at == 0) | ((a <= 0) != (b <= 0)), k, need)
+    return need
+
+
+def sc_brentq_roots(c):
+    """scipy's brentq on the oracle's float64 mass balance (lumped_storage.py:24-31) at every root point; NaN elsewhere"""
+    from scipy.optimize import brentq
+    from oracle import preissmann_oracle as O
+    st = HR.sc_oracle_st(c["params"])
+    out = np.full(len(c["yold"]), np.nan)
+    for i in np.nonzero(c["root"]["is_root"])[0]:
+        yo, vol = float(c["yold"][i]), float(c["vol"][i])
+
+        def f(Y):
+            q = 0.5 * (O.storage_outflow(st, yo) + O.storage_outflow(st, Y)) if st.get("rc") is not None else 0.0
+            return O.storage_net_vol(st, yo, Y) - (vol - q * DT_SC)
+        out[i] = brentq(f, st["Y_min"], st["Y_max"])
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def sc_reference_roots(typ):
+    """set name -> sc_brentq_roots of the set, computed once"""
+    return {c["name"]: sc_brentq_roots(c) for c in sc_cases(typ)}
+
+
+def sc_compared(c, Y):
+    """the root points whose returned stage Y stays in the comparison: away from a switch of the trapezoid's n"""
+    return c["root"]["is_root"] & (sc_switch_distance(c["params"], c["yold"], Y) >= SWITCH_GAP)
+
+
+HOST_ROW_B = 65
+
+
+def host_rows(D):
+    """params[3][65]: dh, dq, res of 65 reaches as a caller would leave them, a NaN and an inf among them"""
+    rng = np.random.default_rng(77)
+    rows = (HR.log_uniform(rng, 1e-6, 1e6, 3 * HOST_ROW_B, np.float64) * rng.choice([-1.0, 1.0], 3 * HOST_ROW_B)).astype(D).reshape(3, HOST_ROW_B)
+    rows[0, 3], rows[1, 17], rows[2, 40], rows[2, 64], rows[0, 64] = np.nan, np.inf, -np.inf, np.nan, 0.0
+    return rows
+
+
 def all_bars(typ):
     """(label, bar) of every bar of the type"""
     out = [(c["name"], c["bar"]) for c in scalar_cases(typ)]
@@ -259,4 +520,6 @@ def all_bars(typ):
         out += [(f"{c['name']}.{f}", b) for f, b in c["bar"].items()] + [(f"{c['name']}.props.{f}", b) for f, b in c["props"]["bar"].items()]
     for c in bc_cases(typ):
         out += [(f"{c['name']}.{c['form']}.{f}", b) for f, b in c["bar"].items()]
+    for c in sc_cases(typ):
+        out += [(f"storage_curve.{c['name']}.{f}", c[f]["bar"]) for f in ("area", "outflow", "net_vol")]
     return out

@@ -6,8 +6,9 @@ The formulas are the reference's, as oracle/preissmann_oracle.py states them (se
 the curvature terms of node_terms, the boundary rows with their two evaluation depths and the rating derivatives), not the device's
 rearrangements.  `T` is the type the arithmetic runs in: np.longdouble for the fp64 device functions, np.float64 for the fp32 ones,
 and the device's own type for the "plain restatement" whose rounding noise sets the bars.  `D` is the device's type: inputs are
-exactly representable in it, and every branch (d > h_bf, z <= s0, z >= s0 + buf, Y < min_stage, the storage range) is decided in it,
-from the inputs, as the device decides - the two sides of a comparison never sit on different branches.
+exactly representable in it, and every branch (d > h_bf, z <= s0, z >= s0 + buf, Y < min_stage, the storage range; of the general
+reservoir row the interpolation interval and the clamping of the area curve, the trapezoid's n, level == 1, the floor at min_stage and
+capture_losses) is decided in it, from the inputs, as the device decides - the two sides of a comparison never sit on different branches.
 
 Nothing here imports the package or needs a GPU."""
 import numpy as np
@@ -401,4 +402,201 @@ def bc_row(kind, params, sec, level, dt, h, Q, Qold, Yprev, tgt, T):
         out["exact"] += ["dh"]
     else:
         raise KeyError(kind)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the general reservoir row (oracle: storage_area_at, storage_net_vol, storage_outflow, the f of storage_mass_balance and the
+# general-storage branch of boundary_eval) on one FS_BC_STORAGE_CURVE parameter block: the FS_SC_* scalars, stage[n_curve],
+# area[n_curve]
+# ------------------------------------------------------------------------------------------------------------------------------
+KINDS.update(storage_curve=8, host_row=9)
+SC_KEYS = ("min_stage", "Y_min", "Y_max", "bed", "area", "alpha", "beta", "n_curve", "rc_type", "rc_a", "rc_b", "rc_c", "rc_shift",
+           "losses", "length", "K_q")                                                            # the FS_SC_* slots, in order
+SC = {k: i for i, k in enumerate(SC_KEYS)}
+SC_NFIXED = len(SC_KEYS)
+BRENT_XTOL, BRENT_RTOL = 2e-12, 8.881784197001252e-16        # scipy.optimize.brentq's defaults, as storage_root states them
+
+
+def sc_params(D, curve=None, rc=None, losses=None, **kw):
+    """the parameter block in the device type.  curve: [[stage, area], ...]; rc: dict(type="power" | "polynomial", a, b, c, shift);
+    losses: dict(reservoir_length, K_q)"""
+    s = dict.fromkeys(SC_KEYS, 0.0)
+    s.update(alpha=1.0)
+    s.update(kw)
+    curve = np.zeros((0, 2)) if curve is None else np.asarray(curve, dtype=np.float64)
+    s["n_curve"] = len(curve)
+    if rc is not None:
+        s.update(rc_type={"power": 1, "polynomial": 2}[rc["type"]], rc_a=rc["a"], rc_b=rc["b"], rc_c=rc.get("c", 0.0), rc_shift=rc.get("shift", 0.0))
+    if losses is not None:
+        s.update(losses=1.0, length=losses["reservoir_length"], K_q=losses["K_q"])
+    return np.concatenate([[s[k] for k in SC_KEYS], curve[:, 0], curve[:, 1]]).astype(D)
+
+
+def sc_curve(p):
+    nc = int(p[SC["n_curve"]])
+    return p[SC_NFIXED:SC_NFIXED + nc], p[SC_NFIXED + nc:SC_NFIXED + 2 * nc]
+
+
+def sc_oracle_st(p):
+    """the block as the `storage` dict of oracle/preissmann_oracle.py (every value the float of the device-typed parameter)"""
+    f = lambda k: float(p[SC[k]])
+    xs, ys = sc_curve(p)
+    st = dict(area=f("area"), min_stage=f("min_stage"), Y_min=f("Y_min"), Y_max=f("Y_max"), alpha=f("alpha"), beta=f("beta"))
+    if len(xs):
+        st["curve"] = np.stack([xs.astype(np.float64), ys.astype(np.float64)], axis=1)
+    t = int(p[SC["rc_type"]])
+    if t:
+        st["rc"] = dict(type="polynomial" if t == 2 else "power", a=f("rc_a"), b=f("rc_b"), c=f("rc_c"), shift=f("rc_shift"))
+    if f("losses") > 0.5:
+        st["losses"] = dict(reservoir_length=f("length"), K_q=f("K_q"))
+    return st
+
+
+def sc_step(p):
+    """the smallest gap of the curve's stages in the device type, as bc_storage_curve forms it (1 without two breakpoints)"""
+    xs, _ = sc_curve(p)
+    return np.min(np.abs(xs[1:] - xs[:-1])) if len(xs) > 1 else p.dtype.type(1)
+
+
+def sc_area_branch(p, Y):
+    """-1 clamped below, -2 clamped above, else the interpolation interval: decided in the type of Y (the device's for a
+    device-typed stage) from Y + beta as that type rounds it"""
+    xs, _ = sc_curve(p)
+    B = np.asarray(Y).dtype.type
+    x = np.asarray(Y) + B(p[SC["beta"]])
+    xb = xs.astype(B)
+    j = np.clip(np.searchsorted(xb, x, side="right") - 1, 0, max(len(xs) - 2, 0))
+    return np.where(x <= xb[0], -1, np.where(x >= xb[-1], -2, j))
+
+
+def sc_area_at(p, Y, T):
+    """alpha * interp(Y + beta) in T; without a curve the constant area.  Y: stages of the device type, or of T (then the interval is
+    the one the T value lies in)"""
+    Y = np.asarray(Y)
+    xs, ys = sc_curve(p)
+    if len(xs) == 0:
+        return np.full(Y.shape, T(p[SC["area"]]))
+    br = sc_area_branch(p, Y)
+    xs, ys = xs.astype(T), ys.astype(T)
+    x = Y.astype(T) + T(p[SC["beta"]])
+    j = np.maximum(br, 0)
+    if len(xs) > 1:
+        a = (ys[j + 1] - ys[j]) / (xs[j + 1] - xs[j]) * (x - xs[j]) + ys[j]
+    else:
+        a = np.full(Y.shape, ys[0])
+    a = np.where(br == -1, ys[0], np.where(br == -2, ys[-1], a))
+    return T(p[SC["alpha"]]) * a
+
+
+def sc_trapezoid_n(p, Y1, Y2):
+    """(int)(|Y2 - Y1| / step) in the device type (0 where the quotient is no number, as the device's conversion gives)"""
+    with np.errstate(all="ignore"):
+        q = np.abs(np.asarray(Y2) - np.asarray(Y1)) / sc_step(p)
+    return np.where(np.isfinite(q), q, 0).astype(np.int64)
+
+
+def sc_net_vol(p, Y1, Y2, T, n=None):
+    """(volume between Y1 and Y2, sum of the magnitudes of its terms).  n: the trapezoid's point count per element, by default
+    decided in the device type from the device-typed Y1, Y2"""
+    Y1, Y2 = np.asarray(Y1), np.asarray(Y2)
+    if int(p[SC["n_curve"]]) == 0:
+        v = (Y2.astype(T) - Y1.astype(T)) * T(p[SC["area"]])
+        return v, np.abs(v)
+    n = sc_trapezoid_n(p, Y1, Y2) if n is None else np.asarray(n)
+    y1, y2 = Y1.astype(T), Y2.astype(T)
+    a1 = sc_area_at(p, Y1, T)
+    v = T(0.5) * (sc_area_at(p, Y2, T) + a1) * (y2 - y1)
+    mag = np.abs(v)
+    for k in np.unique(n[n > 2]):
+        m = n == k
+        lo, hi = y1[m], y2[m]
+        d = (hi - lo) / T(k - 1)
+        s, sm, y0, a0 = np.zeros_like(lo), np.zeros_like(lo), lo, a1[m]
+        for i in range(1, int(k)):
+            yy = hi if i == k - 1 else lo + T(i) * d
+            aa = sc_area_at(p, yy, T)
+            t = (yy - y0) * (aa + a0) / T(2)
+            s, sm, y0, a0 = s + t, sm + np.abs(t), yy, aa
+        v[m], mag[m] = s, sm
+    return v, mag
+
+
+def sc_outflow(p, Y, T):
+    """(reservoir release at stage Y, sum of the magnitudes of its terms)"""
+    Y = np.asarray(Y)
+    t = int(p[SC["rc_type"]])
+    if t == 0:
+        return np.zeros(Y.shape, dtype=T), np.zeros(Y.shape, dtype=T)
+    a, b, c = (T(p[SC[k]]) for k in ("rc_a", "rc_b", "rc_c"))
+    x = Y.astype(T) + T(p[SC["rc_shift"]])
+    if t == 2:
+        return a * x * x + b * x + c, np.abs(a * x * x) + np.abs(b * x) + abs(c)
+    q = a * (pow_plain_f32 if T is np.float32 else pow_ref)(x, np.full(Y.shape, b))     # (fp32: exp2(b log2 x), as the power row)
+    return q, np.abs(q)
+
+
+def sc_f(p, Yold, vol, dt, Y, T, n=None):
+    """(the mass balance whose root storage_root finds, sum of the magnitudes of its terms).  lumped_storage.py:24-31"""
+    v, mag = sc_net_vol(p, Yold, Y, T, n)
+    vol = np.asarray(vol).astype(T)
+    if int(p[SC["rc_type"]]) != 0:
+        (q0, m0), (q1, m1) = sc_outflow(p, Yold, T), sc_outflow(p, Y, T)
+        qout, mq = T(0.5) * (q0 + q1), T(0.5) * (m0 + m1)
+    else:
+        qout = mq = np.zeros(v.shape, dtype=T)
+    return v - (vol - qout * T(dt)), mag + np.abs(vol) + mq * T(dt)
+
+
+def brent_delta(Y):
+    """Brent's (xtol + rtol |x|) / 2 in the type of Y"""
+    D = np.asarray(Y).dtype.type
+    return (D(BRENT_XTOL) + D(BRENT_RTOL) * np.abs(Y)) / D(2)
+
+
+def sc_min_slope(p):
+    """the smallest dV/dY in the bracket: alpha times the smallest area of the curve (the rating term only adds to it)"""
+    _, ys = sc_curve(p)
+    return float(p[SC["alpha"]]) * float(ys.min()) if len(ys) else float(p[SC["area"]])
+
+
+def sc_row(params, sec, level, dt, h, Q, Qold, Y, T):
+    """The general reservoir row AT the stage Y (device-typed: the stage the root finder returned, after the floor), computed in T.
+    boundary.py:97-133, :152-164, :213-237.  Returns res, dh, dq, their scales, and `exact`: name -> (mask, device-typed values) of what
+    the device must hit bit for bit."""
+    D = np.asarray(h).dtype.type
+    p = params
+    n = len(h)
+    hh, QQ, YY = np.asarray(h).astype(T), np.asarray(Q).astype(T), np.asarray(Y).astype(T)
+    bed, ymin = T(p[SC["bed"]]), D(p[SC["min_stage"]])
+    floored = np.asarray(Y) <= ymin                                         # lumped_storage.py:37-45, decided on the device's own stage
+    with np.errstate(all="ignore"):
+        dY = np.where(floored, T(0), T(1) / sc_area_at(p, Y, T))
+    hl = t1 = t2 = u1 = u2 = dAdh = np.zeros(n, dtype=T)
+    losses = bool(p[SC["losses"]] > D(0.5))
+    if losses:
+        Lr, Kq, gr = T(p[SC["length"]]), T(p[SC["K_q"]]), T(G)
+        aQ = np.abs(QQ)
+        gr_ = general_props(sec, h, T)                                      # residual: hw = z_min + depth
+        hd = (np.asarray(h) + D(p[SC["bed"]])) - D(sec["z"])                # derivatives: hw = depth + bed_level, as the device forms it
+        gd = general_props(sec, hd, T)
+        with np.errstate(all="ignore"):
+            K = gr_["A"] * _p(gr_["Rh"], 2, 3) / gr_["neq"]
+            hl = QQ * aQ / K ** 2 * Lr + Kq * (QQ / gr_["A"]) ** 2 / (T(2) * gr)
+            A, R, ne = gd["A"], gd["Rh"], gd["neq"]
+            K = A * _p(R, 2, 3) / ne
+            dK = (_p(R, 2, 3) + A * T(2) / T(3) * _p(R, -1, 3) * gd["dRdA"]) / ne           # hydraulics.py:28-40
+            V = QQ / A
+            t1 = T(-2) * (QQ * aQ / K ** 2) * (dK / K) * Lr
+            t2 = Kq * T(2) * V * (-QQ / A ** 2) / (T(2) * gr)
+            u1 = T(2) * aQ / K ** 2 * Lr
+            u2 = Kq * T(2) * V * (T(1) / A) / (T(2) * gr)
+            dAdh = gd["T"]
+    half_dt = T(0.5) * T(dt)
+    out = dict(res=hh - (YY + hl - bed), dh=T(1) - (t1 + t2) * dAdh, dq=T(0) - (dY * half_dt + (u1 + u2)),
+               s_res=np.maximum(np.abs(hh), np.abs(YY) + np.abs(hl)), s_dh=T(1) + (np.abs(t1) + np.abs(t2)) * dAdh,
+               s_dq=dY * half_dt + np.abs(u1) + np.abs(u2), floored=floored, exact={})
+    if not losses:
+        out["exact"]["dh"] = (np.ones(n, dtype=bool), np.ones(n, dtype=D))
+        out["exact"]["dq"] = (floored, np.zeros(n, dtype=D))               # dY = 0 at or below min_stage
     return out

@@ -35,6 +35,26 @@ Measured on an MI355X (worst | bar); the composites as the worst of all their pa
   bc_eval<false>       3.40e-15  dh, normal depth 0.3 off   6.58e-07 | 9.95e-07  dh, power rating
   bc_eval_rect         3.69e-15  dh, normal depth same bed  3.47e-07 | 7.76e-07  dh, normal depth S0 < 0
 
+The general reservoir row (FS_BC_STORAGE_CURVE: seven parameter sets, helper_recipes.sc_sets) and the host row:
+
+  area_at              4.08e-16  curve6_alpha_beta_poly     2.38e-07 | 9.51e-07  curve6_alpha_beta_poly
+  outflow              6.04e-16  curve6_power_shift         1.38e-06 | 1.47e-06  curve6_power_shift (exp2(b log2 x), as the power row)
+  net_vol              3.55e-16  curve6_alpha_beta_poly     1.64e-07 | 6.43e-07  curve6
+  bc_eval<true>.res    2.94e-15  curve6_poly_losses_bed_off 6.91e-07 | 4.30e-06  curve6_poly_losses_bed_off
+  bc_eval<true>.dh     1.58e-15  curve6_poly_losses_bed_off 7.13e-07 | 4.81e-06  curve6_poly_losses_bed_off
+  bc_eval<true>.dq     1.98e-15  curve6_poly_losses_bed_off 1.21e-07 | 4.77e-07  curve6
+  storage_root         the wide f changes sign within w = 4 x (max(delta, ulp) + noise_f / A_min) of the returned stage, or is 0 there, at
+                       every root point away from a switch of the trapezoid's n (3 512 of 3 519 points per type; bc_eval<true>'s Ynew: 3 257 / 3 256).
+                       Worst multiple of w / 4 needed on the device, of 1, 2, 4: fp64 1, fp32 1 (bar 4).
+  storage_root, fp64   |Y - brentq's root| <= 0.004 x 2 delta on every set (bar 10 x 2 delta: two valid evaluation paths end at most
+                       2 delta apart, tests/test_gpu_forcing.py)
+
+The row is compared AT the stage the device returned (res, dh, dq do not inherit the root's tolerance).  Bit for bit the same: flag
+(FS_STORAGE_RANGE for f of one sign at both ends and for a NaN volume), the bracket end where f(end) == 0, Ynew == min_stage on the
+floor, dq == 0 there and dh == 1 without entrance losses, area_at on the clamped ends and with a constant area, outflow without a
+rating curve, net_vol(Y, Y) == 0, the shared and the per-reach parameter layout, and dh, dq, res of the host row (NaN, inf included).
+The rows' numbers on flagged points are not promised and not compared.
+
 dq, dh of the stage-type rows, flag, and al outside the blend buffer (both forms, the edge stages included): bit for bit the same.
 Every stated bound held: no comment had to be corrected.  pow_pos: the source's 4.1e-15 stands (4.04e-15 here, the float64 libm
 pair 4.04e-15 on the same points); the 8.0e-15 of profiles/round4/rsq_pow_prec.txt is that benchmark's own grid, where host libm gives 7.95e-15.
@@ -226,4 +246,134 @@ def test_boundary_rows(P, typ):
             t.check(f"{name}.{f}", typ, got[f], ref[f], bar, scale=c["scales"][f], at=at)
         for f in ref["exact"]:
             t.same_bits(f"{name}.{f}", typ, got[f], ref[f])
+    t.done()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the general reservoir row (FS_BC_STORAGE_CURVE): its parts, its Brent root, the row at the device's own stage; the host row
+# ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("typ", TYPS)
+def test_storage_curve_parts(P, typ):
+    """StorageCurve::area_at, outflow and net_vol on every parameter set; bit for bit: the clamped ends, a constant area, no rating
+    curve, net_vol(Y, Y) == 0"""
+    D = RC.TYPES[typ]
+    t = Tally()
+    for c in RC.sc_cases(typ):
+        p, name = c["params"], c["name"]
+        nc = int(p[HR.SC["n_curve"]])
+        a, o, v = c["area"], c["outflow"], c["net_vol"]
+        got, _ = P.storage_parts("area_at", p, c["dt"], a["Y"])
+        t.check(f"area_at [{name}]", typ, got, a["ref"], a["bar"], at=dict(Y=a["Y"]))
+        if nc:
+            _, ys = HR.sc_curve(p)
+            br = HR.sc_area_branch(p, a["Y"])
+            t.same_bits(f"area_at, clamped ends [{name}]", typ, got[br < 0], (p[HR.SC["alpha"]] * np.where(br == -1, ys[0], ys[-1]))[br < 0])
+        else:
+            t.same_bits(f"area_at, n_curve = 0 [{name}]", typ, got, np.full(len(got), p[HR.SC["area"]]))
+        got, _ = P.storage_parts("outflow", p, c["dt"], o["Y"])
+        t.check(f"outflow [{name}]", typ, got, o["ref"], o["bar"], scale=o["scale"], at=dict(Y=o["Y"]))
+        if int(p[HR.SC["rc_type"]]) == 0:
+            t.same_bits(f"outflow, rc_type = 0 [{name}]", typ, got, np.zeros(len(got), dtype=D))
+        got, _ = P.storage_parts("net_vol", p, c["dt"], v["Y1"], v["Y2"])
+        t.check(f"net_vol [{name}]", typ, got, v["ref"], v["bar"], scale=v["scale"], at=dict(Y1=v["Y1"], Y2=v["Y2"]))
+        same = v["Y1"] == v["Y2"]
+        assert same.sum() >= 2
+        t.same_bits(f"net_vol(Y, Y) == 0 [{name}]", typ, got[same], np.zeros(int(same.sum()), dtype=D))
+        if nc == 0:
+            t.same_bits(f"net_vol, n_curve = 0 [{name}]", typ, got, (v["Y2"] - v["Y1"]) * p[HR.SC["area"]])
+    t.done()
+
+
+def _root_checks(t, label, typ, c, Y, keep):
+    """the root criterion on the points `keep`: prints the worst multiple of w / FACTOR that was needed"""
+    D = RC.TYPES[typ]
+    p = c["params"]
+    inside = np.isfinite(Y) & (Y >= p[HR.SC["Y_min"]]) & (Y <= p[HR.SC["Y_max"]])
+    need = RC.sc_root_brackets(c, np.where(keep & inside, Y, D(RC.Y_LO + 1.0)), typ)
+    need = np.where(inside, need, np.inf)[keep]
+    w = float(need.max()) if len(need) else 0.0
+    print(f"HELPER {label} | {typ} | {int(keep.sum())} root points | worst multiple of w / {RC.FACTOR:.0f}: {w:.0f} | bar {RC.FACTOR:.0f}")
+    if not w <= RC.FACTOR:
+        bad = np.nonzero(keep)[0][~(need <= RC.FACTOR)]
+        t.failed.append(f"{label} {typ}: no sign change of f within w at {len(bad)} points, first {bad[:4].tolist()}")
+    return w
+
+
+@pytest.mark.parametrize("typ", TYPS)
+def test_storage_root(P, typ):
+    """storage_root on every parameter set: the flag bit for bit, f(end) == 0 returns that end, and at every root point away from a
+    switch of the trapezoid the wide f changes sign within w of the returned stage; fp64: within 10 x 2 delta of scipy's brentq"""
+    D = RC.TYPES[typ]
+    t = Tally()
+    for c in RC.sc_cases(typ):
+        p, name, r = c["params"], c["name"], c["root"]
+        Y, flag = P.storage_parts("storage_root", p, c["dt"], c["yold"], c["vol"])
+        t.same_bits(f"storage_root.flag [{name}]", typ, flag.astype(D), r["flag"])
+        ends = r["end"] != 0
+        if ends.any():
+            t.same_bits(f"storage_root, f(end) == 0 [{name}]", typ, Y[ends], np.where(r["end"] == -1, p[HR.SC["Y_min"]], p[HR.SC["Y_max"]])[ends])
+        br = RC.sc_reference_roots(typ)[c["name"]]
+        keep = RC.sc_compared(c, br)
+        _root_checks(t, f"storage_root [{name}]", typ, c, Y, keep)
+        if typ == "f64":
+            d = np.abs(Y[keep] - br[keep]) / (2.0 * HR.brent_delta(br[keep]))
+            print(f"HELPER storage_root - brentq [{name}] | {typ} | worst {float(d.max()):.3f} x 2 delta | bar 10")
+            if not d.max() <= 10.0:
+                t.failed.append(f"storage_root [{name}]: {float(d.max())} x 2 delta from brentq's root at {int(np.nonzero(keep)[0][np.argmax(d)])}")
+    t.done()
+
+
+@pytest.mark.parametrize("typ", TYPS)
+def test_general_reservoir_row(P, typ):
+    """bc_eval<true> for FS_BC_STORAGE_CURVE: the flag, the stage it returns (the root of ITS reservoir state: at level 1 Yold is
+    h + bed and Yprev is ignored), and res, dh, dq against the restatement at that stage; shared and per-reach layouts bit for bit"""
+    D = RC.TYPES[typ]
+    T = HR.reference_type(D)
+    t = Tally()
+    for c in RC.sc_cases(typ):
+        p, name, sec, level, rr = c["params"], c["name"], c["sec"], c["level"], c["row_root"]
+        h, Q, Qold, Yprev = c["row_pts"]
+        got = P.bc_general(HR.KINDS["storage_curve"], p, sec, level, c["dt"], h, Q, Qold, Yprev)
+        wide = P.bc_general(HR.KINDS["storage_curve"], np.ascontiguousarray(np.repeat(p[:, None], len(h), axis=1)), sec, level, c["dt"], h, Q, Qold, Yprev)
+        for f in ("res", "dh", "dq", "Ynew"):
+            t.same_bits(f"bc_eval<true>.{f}, per-reach layout [{name}]", typ, wide[f], got[f])
+        t.same_bits(f"bc_eval<true>.flag, per-reach layout [{name}]", typ, wide["flag"].astype(D), got["flag"])
+        sure = rr["margin"] >= RC.FLAG_MARGIN                       # (all but the f(end) == 0 points, exact in the parts' states only)
+        t.same_bits(f"bc_eval<true>.flag [{name}]", typ, got["flag"][sure].astype(D), rr["flag"][sure])
+        ok = sure & (rr["flag"] == HR.FS_OK) & (got["flag"] == HR.FS_OK)
+        ymin = p[HR.SC["min_stage"]]
+        floor = np.array([c["tags"].get(i) == "floor" for i in range(len(h))])
+        t.same_bits(f"bc_eval<true>.Ynew on the floor [{name}]", typ, got["Ynew"][floor], np.full(int(floor.sum()), ymin))
+        # the returned stage is the root of the row's own reservoir state
+        state = dict(c, yold=c["row_yold"], vol=c["row_vol"], root=rr)
+        raw = ok & (got["Ynew"] > ymin)
+        keep = raw & (RC.sc_switch_distance(p, c["row_yold"], got["Ynew"]) >= RC.SWITCH_GAP)
+        assert (raw & ~keep).sum() <= RC.MAX_DROPPED * raw.sum(), name
+        _root_checks(t, f"bc_eval<true>.Ynew [{name}]", typ, state, got["Ynew"], keep)
+        # the row at the device's own stage
+        Y = got["Ynew"][ok]
+        args = (p, sec, level, c["dt"], h[ok], Q[ok], Qold[ok], Y)
+        ref = HR.sc_row(*args, T)
+        plain = HR.sc_row(*args, D)
+        at = dict(h=h[ok], Q=Q[ok], Y=Y)
+        for f in ("res", "dh", "dq"):
+            bar = RC.COMPOSITE_F64 if typ == "f64" else RC.FACTOR * HR.noise(plain[f], ref[f], ref["s_" + f])
+            t.check(f"bc_eval<true>.{f} [{name}]", typ, got[f][ok], ref[f], bar, scale=ref["s_" + f], at=at)
+        for f, (mask, val) in ref["exact"].items():
+            t.same_bits(f"bc_eval<true>.{f} where exact [{name}]", typ, got[f][ok][mask], val[mask])
+        assert ref["floored"].sum() >= 8
+    t.done()
+
+
+@pytest.mark.parametrize("typ", TYPS)
+def test_host_row(P, typ):
+    """FS_BC_HOST_ROW hands back columns 0, 1, 2 of each reach's own rows: dh, dq, res, NaN and inf included"""
+    D = RC.TYPES[typ]
+    rows = RC.host_rows(D)
+    z = np.zeros(rows.shape[1], dtype=D)
+    got = P.bc_general(HR.KINDS["host_row"], rows, RC.bc_section("general", RC.Z, D), 2, RC.DT, z + D(3), z, z, z)
+    t = Tally()
+    for k, f in enumerate(("dh", "dq", "res")):
+        t.same_bits(f"bc_eval<true>.{f} [host row]", typ, got[f], rows[k])
+    assert np.all(got["flag"] == HR.FS_OK)
     t.done()

@@ -4,6 +4,11 @@
     boundary_eval on the recipes' own sections, points and boundary parameter sets, at the bar of tests/test_derived_reference.py;
   * the long double scalar functions agree with mpmath at 50 digits within 4e-19 on 4 096 points each;
   * the bars: every "4 x noise" bar is printed with the restatement noise it comes from (run with -s);
+  * the restatement of the general reservoir row, run in float64, is the oracle's storage_area_at / storage_net_vol / storage_outflow, the mass
+    balance of storage_mass_balance and the general-storage branch of boundary_eval (at the stage brentq found) on every parameter set;
+  * the root criterion accepts scipy's brentq root of the float64 balance on every compared root point; at most 5 % of a set's root points
+    lie within 1e-3 of a switch of the trapezoid's n and no special point does; |f| at the bracket ends of every flag point is 1000 x the noise of
+    f or exactly 0; the part points visit every interval, breakpoint, clamp and form of the trapezoid;
   * the comparison routine fails when ONE point of 2^18 is moved by twice its bar, and passes when it is moved by half, for every bar."""
 import numpy as np
 import pytest
@@ -182,3 +187,132 @@ def test_one_point_of_2_18_moved_by_twice_its_bar_fails(typ, capsys):
     with pytest.raises(AssertionError):
         HR.check("nan", typ, bad, ref, 1.0)
     capsys.readouterr()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the general reservoir row: restatement against the oracle, the root criterion against scipy, the conditions on the points
+# ------------------------------------------------------------------------------------------------------------------------------
+SC_IDS = [c["name"] for c in RC.sc_cases("f64")]
+
+
+def _sc_bc(case):
+    p = case["params"]
+    return O.BC("fixed_depth", bed_level=float(p[HR.SC["bed"]]), storage=HR.sc_oracle_st(p))
+
+
+@pytest.mark.parametrize("case", RC.sc_cases("f64"), ids=SC_IDS)
+def test_float64_restatement_is_the_oracles_storage_functions(case):
+    p, st = case["params"], HR.sc_oracle_st(case["params"])
+    Y = case["area"]["Y"]
+    e = _rel(HR.sc_area_at(p, Y, np.float64), [O.storage_area_at(st, float(y)) for y in Y])
+    assert e <= BAR, ("area_at", e)
+    q, sq = HR.sc_outflow(p, Y, np.float64)
+    e = _rel(q, [O.storage_outflow(st, float(y)) for y in Y], sq)
+    assert e <= BAR, ("outflow", e)
+    y1, y2 = case["net_vol"]["Y1"], case["net_vol"]["Y2"]
+    v, sv = HR.sc_net_vol(p, y1, y2, np.float64)
+    e = _rel(v, [O.storage_net_vol(st, float(a), float(b)) for a, b in zip(y1, y2)], sv)
+    assert e <= BAR, ("net_vol", e)
+    # the mass balance at both bracket ends and at a stage inside, for every reservoir state with a finite volume
+    yold, vol = case["yold"], case["vol"]
+    ok = np.isfinite(vol)
+    rng = np.random.default_rng(11)
+    for Ys in (np.full(len(yold), RC.Y_LO), np.full(len(yold), RC.Y_HI), rng.uniform(RC.Y_LO, RC.Y_HI, len(yold))):
+        f, sf = HR.sc_f(p, yold[ok], vol[ok], RC.DT_SC, Ys[ok], np.float64)
+        want = []
+        for yo, vo, y in zip(yold[ok], vol[ok], Ys[ok]):
+            qo = 0.5 * (O.storage_outflow(st, float(yo)) + O.storage_outflow(st, float(y))) if st.get("rc") is not None else 0.0
+            want.append(O.storage_net_vol(st, float(yo), float(y)) - (float(vo) - qo * RC.DT_SC))
+        e = _rel(f, want, sf)
+        assert e <= BAR, ("f", e)
+
+
+@pytest.mark.parametrize("case", RC.sc_cases("f64"), ids=SC_IDS)
+def test_float64_restatement_is_the_oracles_general_storage_row(case):
+    """boundary_eval finds the stage with storage_mass_balance (brentq); the restatement is evaluated AT that stage"""
+    p, sec, level = case["params"], case["sec"], case["level"]
+    h, Q, Qold, Yprev = case["row_pts"]
+    bc, geo = _sc_bc(case), HR.oracle_geo(sec)
+    want, idx, Ys = [], [], []
+    for i in range(len(h)):
+        store = dict(Y_prev=float(Yprev[i]))
+        try:
+            want.append(O.boundary_eval(bc, geo, float(h[i]), float(Q[i]), level, RC.DT_SC, Q_old=float(Qold[i]), store=store))
+        except O.StorageRange:
+            assert case["row_root"]["flag"][i] == HR.FS_STORAGE_RANGE, i
+            continue
+        assert case["row_root"]["flag"][i] == HR.FS_OK, i
+        idx.append(i)
+        Ys.append(store["Y_eval"])
+    idx, want = np.array(idx), np.array(want)
+    got = HR.sc_row(p, sec, level, RC.DT_SC, h[idx], Q[idx], Qold[idx], np.array(Ys), np.float64)
+    worst = {f: _rel(got[f], want[:, k], got["s_" + f]) for k, f in enumerate(("res", "dh", "dq"))}
+    print(case["name"], worst)
+    assert all(v <= BAR for v in worst.values()), worst
+    for f, (mask, val) in got["exact"].items():
+        assert np.array_equal(got[f][mask], val[mask]), f
+    floored = got["floored"]
+    assert floored.sum() >= 8 and (~floored).sum() >= 400, "the floor is not visited"
+    if level == 1:
+        assert np.all(np.abs(Yprev - case["row_yold"]) > 0), "a level-1 Yprev that equals Yold does not show that it is ignored"
+
+
+@pytest.mark.parametrize("typ", ["f64", "f32"])
+def test_the_root_criterion_accepts_scipys_roots_and_the_points_meet_their_conditions(typ):
+    D = RC.TYPES[typ]
+    n_checked = 0
+    for c in RC.sc_cases(typ):
+        r, tags = c["root"], c["tags"]
+        br = RC.sc_reference_roots(typ)[c["name"]]
+        assert np.all(np.isfinite(br[r["is_root"]]))
+        # root points away from a switch: at most 5 % dropped, no special point among them
+        keep = RC.sc_compared(c, br)
+        dropped = r["is_root"] & ~keep
+        assert dropped.sum() <= RC.MAX_DROPPED * r["is_root"].sum(), (c["name"], int(dropped.sum()))
+        assert not any(dropped[i] for i in tags), (c["name"], [tags[i] for i in tags if dropped[i]])
+        # the criterion holds for brentq's root (rounded to the device type: the width has one ulp in it)
+        need = RC.sc_root_brackets(c, np.where(keep, br, RC.Y_LO + 1.0).astype(D), typ)
+        assert np.all(need[keep] <= RC.FACTOR), (c["name"], np.nonzero(keep & ~(need <= RC.FACTOR))[0][:8])
+        n_checked += int(keep.sum())
+        print(f"ROOT {c['name']} | {typ} | {int(keep.sum())} of {int(r['is_root'].sum())} root points | worst multiple {need[keep].max():.0f} | noise_f {r['noise_f']:.2e}")
+        # flag points away from zero, in the parts' states and in the row's; the f == 0 points are exact in the parts' states only
+        assert r["margin"].min() >= RC.FLAG_MARGIN, (c["name"], r["margin"].min())
+        rr = c["row_root"]
+        exact_only = np.array([tags.get(i, "").endswith("_zero") for i in range(len(br))])
+        assert rr["margin"][~exact_only].min() >= RC.FLAG_MARGIN, (c["name"], rr["margin"][~exact_only].min())
+        assert np.array_equal(rr["flag"][~exact_only], r["flag"][~exact_only])
+        # every special point is there and is what its name says
+        want = set(RC.ROOT_SPECIAL) - (set() if c["name"] == "const_area" else {"f_lo_zero", "f_hi_zero"})
+        assert set(tags.values()) == want
+        for i, t in tags.items():
+            if t in ("both_negative", "both_positive", "nan"):
+                assert r["flag"][i] == HR.FS_STORAGE_RANGE, (c["name"], t)
+            else:
+                assert r["flag"][i] == HR.FS_OK and r["end"][i] == {"f_lo_zero": -1, "f_hi_zero": 1}.get(t, 0), (c["name"], t)
+            if t == "floor":
+                assert br[i] < c["params"][HR.SC["min_stage"]]
+        if int(c["params"][HR.SC["n_curve"]]) > 2:
+            n = HR.sc_trapezoid_n(c["params"], c["yold"], br.astype(D))[r["is_root"]]
+            assert n.max() >= 19 and (n <= 2).any() and (n > 2).any()
+    assert n_checked >= 3400
+
+
+@pytest.mark.parametrize("typ", ["f64", "f32"])
+def test_the_part_points_visit_every_branch(typ):
+    for c in RC.sc_cases(typ):
+        p = c["params"]
+        nc = int(p[HR.SC["n_curve"]])
+        y1, y2 = c["net_vol"]["Y1"], c["net_vol"]["Y2"]
+        if nc:
+            # |Y2 - Y1| / step at 1.9, 2, 2.99, 3, 3.01 with both signs, as the device type rounds it
+            assert HR.sc_trapezoid_n(p, y1, y2)[:10].tolist() == [1, 2, 2, 3, 3] * 2, c["name"]
+            xs, _ = HR.sc_curve(p)
+            Y = c["area"]["Y"]
+            x = Y + p[HR.SC["beta"]]
+            br = HR.sc_area_branch(p, Y)
+            assert set(br.tolist()) == {-1, -2} | set(range(nc - 1)), c["name"]
+            for b in xs:
+                assert (x == b).any() and (x == np.nextafter(b, p.dtype.type(0))).any() and (x == np.nextafter(b, p.dtype.type(99))).any(), (c["name"], b)
+        assert np.all(y1[12:14] == y2[12:14])
+    rows = RC.host_rows(RC.TYPES[typ])
+    assert rows.shape == (3, 65) and np.isnan(rows).sum() == 2 and np.isinf(rows).sum() == 2
