@@ -497,42 +497,28 @@ int launch_steps(fs_batch *b, int n_steps, int iter_budget) {
     return fail("fs_batch_step: FS_BC_STORAGE_CURVE needs section mode FS_SEC_TABLE or FS_SEC_IRREGULAR");
   if (!k) return fail("fs_batch_step: no kernel instantiation for this boundary kind at this size");
   b->kern = k;
-  b->passes = 0;
-  if (k->key.longk) {      // a reach longer than one lane grid: passes of 64 W M rows, level constants in a scratch of the batch's own
-    const size_t chunk = (size_t)64 * k->key.W * k->key.M;
-    b->passes = (int)((b->d.n_nodes + chunk - 1) / chunk);
-    // (uniform sections recompute their level constants, fs_long.hpp: no scratch)
-    const bool recompute = b->d.section_mode == FS_SEC_RECT_UNIFORM || b->d.section_mode == FS_SEC_TRAP_UNIFORM;
-    const size_t need = recompute ? 0 : (size_t)b->d.n_reaches * 4 * b->passes * chunk;
-    HIP_TRY(b->kc_scratch.reserve(need * b->esz));
-  }
-  b->team_size = 0;
-  if (k->key.team) {       // G workgroups per reach: their mailboxes and the ticket counter (which starts every launch at zero)
-    const size_t chunk = (size_t)64 * k->key.W * k->key.M, B = b->d.n_reaches;
-    b->team_size = (int)((b->d.n_nodes + chunk - 1) / chunk);
-    // (16 bytes per word: the tagged form posts (value, tag) pairs; zeroed once - a tag is never 0, launches count from 1)
-    const size_t need = B * 2 * ((size_t)b->team_size * k->key.W + 1) * fs::kTeamWords * 2;
+  const size_t B = b->d.n_reaches, N = b->d.n_nodes;
+  const fs::LaunchPlan plan = fs::plan_launch(k->key, b->d.section_mode, B, N, n_steps, b->any_storage[FS_DOWNSTREAM]);
+  b->passes = plan.passes; b->team_size = plan.team_size;
+  HIP_TRY(b->kc_scratch.reserve(plan.kc_scratch_elems * b->esz));
+  if (plan.team_size) {    // the mailboxes (zeroed once - a tag is never 0, launches count from 1) and the ticket counter (zero at every launch)
     bool grew = false;
-    HIP_TRY(b->team_mail.reserve(need * sizeof(double), &grew));
-    if (grew) HIP_TRY(hipMemsetAsync(b->team_mail.get(), 0, need * sizeof(double), b->stream));
+    HIP_TRY(b->team_mail.reserve(plan.team_mail_bytes, &grew));
+    if (grew) HIP_TRY(hipMemsetAsync(b->team_mail.get(), 0, plan.team_mail_bytes, b->stream));
     ++b->team_epoch;
     HIP_TRY(b->team_sync.ensure(sizeof(unsigned long long)));
     HIP_TRY(hipMemsetAsync(b->team_sync.get(), 0, sizeof(unsigned long long), b->stream));
   }
-  // (a launch of one level writes the state of a reach only when that level is accepted: nothing to keep)
-  const bool keep_entry = k->key.longk && n_steps > 1 &&
-                          (b->d.section_mode == FS_SEC_RECT_UNIFORM || b->d.section_mode == FS_SEC_TRAP_UNIFORM);
-  const size_t state_bytes = (size_t)b->d.n_reaches * b->d.n_nodes * b->esz;
-  if (keep_entry) {
+  if (plan.keep_entry) {
+    const size_t state_bytes = B * N * b->esz;
     HIP_TRY(b->hk_entry.reserve(state_bytes));
     HIP_TRY(b->Qk_entry.reserve(state_bytes));
     HIP_TRY(hipMemcpyAsync(b->hk_entry.get(), b->hk.get(), state_bytes, hipMemcpyDeviceToDevice, b->stream));
     HIP_TRY(hipMemcpyAsync(b->Qk_entry.get(), b->Qk.get(), state_bytes, hipMemcpyDeviceToDevice, b->stream));
   }
-  const bool keep_stage = n_steps > 1 && b->any_storage[FS_DOWNSTREAM];
-  if (keep_stage) {
-    HIP_TRY(b->Yprev_entry.reserve((size_t)b->d.n_reaches * b->esz));
-    HIP_TRY(hipMemcpyAsync(b->Yprev_entry.get(), b->Yprev.get(), (size_t)b->d.n_reaches * b->esz, hipMemcpyDeviceToDevice, b->stream));
+  if (plan.keep_stage) {
+    HIP_TRY(b->Yprev_entry.reserve(B * b->esz));
+    HIP_TRY(hipMemcpyAsync(b->Yprev_entry.get(), b->Yprev.get(), B * b->esz, hipMemcpyDeviceToDevice, b->stream));
   }
   HIP_TRY(hipEventRecord(b->ev0, b->stream));
   with_real(b, [&](auto real) {
@@ -540,14 +526,12 @@ int launch_steps(fs_batch *b, int n_steps, int iter_budget) {
     fs::KernelArgs<R> a; fill_args(b, n_steps, a);
     a.iter_budget = iter_budget;
     b->kern->fn(&a, b->d.n_reaches, b->stream);
-    if (keep_entry) {
-      const size_t B = b->d.n_reaches, N = b->d.n_nodes;
+    if (plan.keep_entry)
       hipLaunchKernelGGL((restore_failed_state<R>), grid_256(B * N), dim3(256), 0, b->stream, b->status.get<const int32_t>(),
                          b->hk_entry.get<const R>(), b->Qk_entry.get<const R>(), b->hk.get<R>(), b->Qk.get<R>(), B, N);
-    }
-    if (keep_stage)
-      hipLaunchKernelGGL((restore_failed_stage<R>), grid_256(b->d.n_reaches), dim3(256), 0, b->stream, b->status.get<const int32_t>(),
-                         b->Yprev_entry.get<const R>(), b->Yprev.get<R>(), (size_t)b->d.n_reaches);
+    if (plan.keep_stage)
+      hipLaunchKernelGGL((restore_failed_stage<R>), grid_256(B), dim3(256), 0, b->stream, b->status.get<const int32_t>(),
+                         b->Yprev_entry.get<const R>(), b->Yprev.get<R>(), B);
   });
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(b->ev1, b->stream));
@@ -594,12 +578,58 @@ int replace_bc_buffers(fs_batch *b, int side, const double *params, size_t n_par
   return 0;
 }
 
+// n int32 of the caller's into device memory that holds at least n
+int upload_i32(int32_t *dst, const int32_t *src, size_t n) {
+  HIP_TRY(hipMemcpy(dst, src, n * sizeof(int32_t), hipMemcpyHostToDevice));
+  return 0;
+}
+
 // one kind into every slot of a side of reach_kinds
 int fill_side_kinds(fs_batch *b, int side, int kind) {
   const size_t B = b->d.n_reaches;
   const std::vector<int32_t> same(B, kind);
-  HIP_TRY(hipMemcpy(b->reach_kinds.get<int32_t>() + (size_t)side * B, same.data(), B * 4, hipMemcpyHostToDevice));
+  return upload_i32(b->reach_kinds.get<int32_t>() + (size_t)side * B, same.data(), B);
+}
+
+// this side now holds one kind for the whole batch (where the other side has per-reach kinds, the kind goes into every slot of this one)
+int set_side_kind(fs_batch *b, int side, int kind, int stride) {
+  b->bc_kind[side] = kind; b->bc_stride[side] = stride;
+  b->have_bc[side] = true;
+  b->kinds_per_reach[side] = false; b->any_storage[side] = fs::bc_is_storage(kind); b->some_host_rows[side] = false;
+  return b->reach_kinds ? fill_side_kinds(b, side, kind) : 0;
+}
+
+// the [2][B] int32 block a kernel reports per reach in: exists, row 0 zeros and row 1 all ones (-1) ...
+int prepare_info(fs_batch *b, fs::DeviceBuffer &block) {
+  const size_t B = b->d.n_reaches;
+  HIP_TRY(block.ensure(2 * B * sizeof(int32_t)));
+  HIP_TRY(hipMemsetAsync(block.get(), 0, B * sizeof(int32_t), b->stream));
+  HIP_TRY(hipMemsetAsync(block.get<int32_t>() + B, 0xff, B * sizeof(int32_t), b->stream));
   return 0;
+}
+
+// ... and back to the caller who asked for it
+int return_info(fs_batch *b, const fs::DeviceBuffer &block, int32_t *info) {
+  if (!info) return 0;
+  HIP_TRY(hipMemcpyAsync(info, block.get(), 2 * (size_t)b->d.n_reaches * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+// the polylines and their tables leave the device (a new irregular geometry follows) ...
+void reset_polylines(fs_batch *b) {
+  for (fs::DeviceBuffer *q : {&b->geo_table, &b->poly_x, &b->poly_z, &b->poly_lim, &b->poly_tz, &b->poly_n}) q->reset();
+  b->poly_K = 0;
+}
+
+// ... and n_sets channels of P stations are on it (1: shared by the batch), with stage tables or for the edge walk
+void commit_polylines(fs_batch *b, size_t n_sets, size_t P, bool walk) {
+  const size_t N = b->d.n_nodes;
+  b->poly_K = walk ? 0 : (int)P;
+  b->poly_P = (int)P;
+  b->geo_reach_stride = n_sets > 1 ? (size_t)fs::FS_GEOX_NROWS * N : 0;
+  b->poly_reach_stride = n_sets > 1 ? P * N : 0;
+  b->have_geo = true;
 }
 
 // the state in hk / Qk becomes the Newton start vector and, where a history is kept, its level 0 (solver.py:61-63)
@@ -759,8 +789,7 @@ fs_batch *fs_batch_create(const fs_batch_desc *desc) {
     fail("fs_batch_create: need n_reaches >= 1, n_nodes >= 2, max_levels >= 2"); return nullptr;
   }
   if (desc->dtype != FS_F64 && desc->dtype != FS_F32) { fail("fs_batch_create: bad dtype"); return nullptr; }
-  if (desc->section_mode != FS_SEC_RECT_UNIFORM && desc->section_mode != FS_SEC_TRAP_UNIFORM &&
-      desc->section_mode != FS_SEC_TABLE && desc->section_mode != FS_SEC_IRREGULAR) {
+  if (!fs::sec_is_uniform(desc->section_mode) && !fs::sec_has_tables(desc->section_mode)) {
     fail("fs_batch_create: bad section_mode"); return nullptr;
   }
   if (desc->section_mode == FS_SEC_IRREGULAR && desc->dtype != FS_F64) {
@@ -853,29 +882,18 @@ static int set_irregular(fs_batch *b, const double *table, const int32_t *n_pts,
   if (max_pts < 2) return fail("fs_batch_set_geometry_irregular: max_pts must be >= 2");
   FS_ON_DEVICE(b);
   const size_t N = b->d.n_nodes, P = max_pts;
-  fs::PolyTableLimits how;
-  if (const char *env = std::getenv("FS_POLY_TABLE_MAX_BYTES")) how.max_bytes = (size_t)std::strtoull(env, nullptr, 10);
-  how.force_walk = std::getenv("FS_POLY_WALK") != nullptr;
   fs::IrregularPlan plan;
-  const std::string err = fs::plan_irregular(table, n_pts, max_pts, x, z, limits, N, n_sets, how, plan);
+  const std::string err = fs::plan_irregular(table, n_pts, max_pts, x, z, limits, N, n_sets, fs::poly_limits_from_environment(), plan);
   if (!err.empty()) return fail(err);
-  for (fs::DeviceBuffer *q : {&b->geo_table, &b->poly_x, &b->poly_z, &b->poly_lim, &b->poly_tz, &b->poly_n}) q->reset();
-  b->poly_K = 0;
-  if (!plan.walk) {
-    if (upload(b, b->poly_tz, plan.tz.data(), plan.tz.size()))
-      return fail("fs_batch_set_geometry_irregular: " + std::to_string(plan.table_mib) + " MiB of stage tables do not fit the "
-                  "device (" + g_err + "); lower FS_POLY_TABLE_MAX_BYTES to fall back to the edge walk");
-    b->poly_K = (int)P;
-  }
-  b->poly_P = (int)P;
+  reset_polylines(b);
+  if (!plan.walk && upload(b, b->poly_tz, plan.tz.data(), plan.tz.size()))
+    return fail("fs_batch_set_geometry_irregular: " + std::to_string(plan.table_mib) + " MiB of stage tables do not fit the "
+                "device (" + g_err + "); lower FS_POLY_TABLE_MAX_BYTES to fall back to the edge walk");
   if (upload(b, b->geo_table, plan.tabs.data(), plan.tabs.size()) || upload(b, b->poly_x, plan.xt.data(), plan.xt.size()) ||
       upload(b, b->poly_z, plan.zt.data(), plan.zt.size()) || upload(b, b->poly_lim, plan.lim.data(), plan.lim.size())) return -1;
-  HIP_TRY(b->poly_n.ensure(n_sets * N * 4));
-  HIP_TRY(hipMemcpy(b->poly_n.get(), n_pts, n_sets * N * 4, hipMemcpyHostToDevice));
-  b->geo_reach_stride = n_sets > 1 ? (size_t)fs::FS_GEOX_NROWS * N : 0;
-  b->poly_reach_stride = n_sets > 1 ? P * N : 0;
-  if (set_n_override(b, n_main_override)) return -1;
-  b->have_geo = true;
+  HIP_TRY(b->poly_n.ensure(n_sets * N * sizeof(int32_t)));
+  if (upload_i32(b->poly_n.get<int32_t>(), n_pts, n_sets * N) || set_n_override(b, n_main_override)) return -1;
+  commit_polylines(b, n_sets, P, plan.walk);
   return 0;
 }
 
@@ -889,7 +907,6 @@ int fs_batch_set_geometry_irregular_per_reach(fs_batch *b, const double *tables,
                                               const double *x, const double *z, const double *limits,
                                               const double *n_main_override) {
   if (!b) return fail("fs_batch_set_geometry_irregular: null argument");
-  if (b->d.n_reaches == 1) return set_irregular(b, tables, n_pts, max_pts, x, z, limits, n_main_override, 1);
   return set_irregular(b, tables, n_pts, max_pts, x, z, limits, n_main_override, (size_t)b->d.n_reaches);
 }
 
@@ -908,29 +925,25 @@ int fs_batch_set_geometry_irregular_members(fs_batch *b, const double *table, co
   std::vector<double> xt(P * N), zt(P * N), lim(2 * N);
   if (const char *err = fs::pack_polylines(table, n_pts, max_pts, x, z, limits, N, xt.data(), zt.data(), lim.data(), nullptr)) return fail(err);
   const std::vector<double> ext = fs::extend_table(table, N);
-  fs::PolyTableLimits how;
-  if (const char *env = std::getenv("FS_POLY_TABLE_MAX_BYTES")) how.max_bytes = (size_t)std::strtoull(env, nullptr, 10);
-  how.force_walk = std::getenv("FS_POLY_WALK") != nullptr;
-  const size_t tstride = (size_t)fs::poly_table_stride(max_pts);
-  const double table_bytes = (double)B * (double)N * (double)tstride * sizeof(double);
-  const bool walk = how.force_walk || table_bytes > (double)how.max_bytes;
-  for (fs::DeviceBuffer *q : {&b->geo_table, &b->poly_x, &b->poly_z, &b->poly_lim, &b->poly_tz, &b->poly_n}) q->reset();
-  b->poly_K = 0; b->poly_P = 0; b->have_geo = false;
-  if (!walk && b->poly_tz.ensure(B * N * tstride * sizeof(double)) != hipSuccess) {
+  size_t table_mib;
+  const bool walk = fs::poly_tables_walk(B, N, max_pts, fs::poly_limits_from_environment(), &table_mib);
+  reset_polylines(b);
+  b->poly_P = 0; b->have_geo = false;
+  if (!walk && b->poly_tz.ensure(B * N * fs::poly_table_stride(max_pts) * sizeof(double)) != hipSuccess) {
     (void)hipGetLastError();
-    return fail("fs_batch_set_geometry_irregular_members: " + std::to_string((size_t)(table_bytes / (1 << 20))) + " MiB of stage tables do not "
+    return fail("fs_batch_set_geometry_irregular_members: " + std::to_string(table_mib) + " MiB of stage tables do not "
                 "fit the device; lower FS_POLY_TABLE_MAX_BYTES to fall back to the edge walk");
   }
   HIP_TRY(b->geo_table.ensure(B * fs::FS_GEOX_NROWS * N * sizeof(double)));
   HIP_TRY(b->poly_x.ensure(B * P * N * sizeof(double)));
   HIP_TRY(b->poly_z.ensure(B * P * N * sizeof(double)));
   HIP_TRY(b->poly_lim.ensure(B * 2 * N * sizeof(double)));
-  HIP_TRY(b->poly_n.ensure(B * N * 4));
+  HIP_TRY(b->poly_n.ensure(B * N * sizeof(int32_t)));
   fs::DeviceBuffer *in = b->member_in;
   if (upload_f64(in[0], xt.data(), xt.size()) || upload_f64(in[1], zt.data(), zt.size()) || upload_f64(in[2], lim.data(), lim.size()) ||
       upload_f64(in[4], ext.data(), ext.size())) return -1;
-  HIP_TRY(in[3].reserve(N * 4));
-  HIP_TRY(hipMemcpy(in[3].get(), n_pts, N * 4, hipMemcpyHostToDevice));
+  HIP_TRY(in[3].reserve(N * sizeof(int32_t)));
+  if (upload_i32(in[3].get<int32_t>(), n_pts, N)) return -1;
   const double *opt[4] = {dz_left, dz_main, dz_right, n_scale};
   for (int q = 0; q < 4; ++q)
     if (opt[q] && upload_f64(in[5 + q], opt[q], q < 3 ? B * N : 3 * B)) return -1;
@@ -949,12 +962,8 @@ int fs_batch_set_geometry_irregular_members(fs_batch *b, const double *table, co
     HIP_TRY(hipStreamSynchronize(b->stream));
     b->timed = true; b->launches = walk ? 1 : 2;      // fs_batch_last_step_ms: the two kernels, until the next step
   }
-  b->poly_K = walk ? 0 : (int)P;
-  b->poly_P = (int)P;
-  b->geo_reach_stride = B > 1 ? (size_t)fs::FS_GEOX_NROWS * N : 0;
-  b->poly_reach_stride = B > 1 ? P * N : 0;
   b->n_override.reset();      // n_scale[1] takes its place
-  b->have_geo = true;
+  commit_polylines(b, B, P, walk);
   return 0;
 }
 
@@ -1001,8 +1010,8 @@ int fs_batch_set_reach_nodes(fs_batch *b, const int32_t *n_nodes) {
   }
   for (size_t r = 0; r < B; ++r)
     if (n_nodes[r] < 2 || n_nodes[r] > b->d.n_nodes) return fail("fs_batch_set_reach_nodes: every reach needs 2 <= nodes <= n_nodes of the batch");
-  HIP_TRY(b->reach_nodes.ensure(B * 4));
-  HIP_TRY(hipMemcpy(b->reach_nodes.get(), n_nodes, B * 4, hipMemcpyHostToDevice));
+  HIP_TRY(b->reach_nodes.ensure(B * sizeof(int32_t)));
+  if (upload_i32(b->reach_nodes.get<int32_t>(), n_nodes, B)) return -1;
   b->reach_nodes_host.assign(n_nodes, n_nodes + B);
   return refresh_row0();
 }
@@ -1054,15 +1063,15 @@ int fs_batch_set_bc_per_reach_wide(fs_batch *b, int32_t side, const int32_t *kin
   if (n_params < FS_BC_MAX_PARAMS) return fail("fs_batch_set_bc_per_reach: at least FS_BC_MAX_PARAMS parameter rows");
   FS_ON_DEVICE(b);
   const size_t B = b->d.n_reaches;
-  const bool tables = b->d.section_mode == FS_SEC_TABLE || b->d.section_mode == FS_SEC_IRREGULAR;
   fs::SideKinds sk;
-  if (const char *err = fs::check_bc_per_reach(side, kinds, params, n_params, target != nullptr, B, tables, sk)) return fail(err);
+  if (const char *err = fs::check_bc_per_reach(side, kinds, params, n_params, target != nullptr, B, fs::sec_has_tables(b->d.section_mode), sk))
+    return fail(err);
   if (replace_bc_buffers(b, side, params, (size_t)n_params * B, target)) return -1;
   if (!b->reach_kinds) {
     HIP_TRY(b->reach_kinds.ensure(2 * B * 4));
     HIP_TRY(hipMemset(b->reach_kinds.get(), 0, 2 * B * 4));
   }
-  HIP_TRY(hipMemcpy(b->reach_kinds.get<int32_t>() + (size_t)side * B, kinds, B * 4, hipMemcpyHostToDevice));
+  if (upload_i32(b->reach_kinds.get<int32_t>() + (size_t)side * B, kinds, B)) return -1;
   // the other side, if it was set for the whole batch, keeps its one kind in every slot
   const int other = 1 - side;
   if (b->have_bc[other] && !b->kinds_per_reach[other] && fill_side_kinds(b, other, b->bc_kind[other])) return -1;
@@ -1078,17 +1087,12 @@ int fs_batch_set_bc(fs_batch *b, int32_t side, int32_t kind, const double *param
   if (check_side("fs_batch_set_bc", side)) return -1;
   FS_ON_DEVICE(b);
   const size_t B = b->d.n_reaches;
-  const bool tables = b->d.section_mode == FS_SEC_TABLE || b->d.section_mode == FS_SEC_IRREGULAR;
-  if (const char *err = fs::check_bc(side, kind, params, n_params, per_reach, target != nullptr, B, tables)) return fail(err);
+  if (const char *err = fs::check_bc(side, kind, params, n_params, per_reach, target != nullptr, B, fs::sec_has_tables(b->d.section_mode)))
+    return fail(err);
   if (kind == FS_BC_HOST_ROW) {      // params[3][B], or NULL: zeros until fs_batch_set_host_rows
     if (replace_bc_buffers(b, side, params, 3 * B, nullptr)) return -1;
   } else if (replace_bc_buffers(b, side, params, per_reach ? n_params * B : (size_t)n_params, target)) return -1;
-  b->bc_kind[side] = kind; b->bc_stride[side] = (kind == FS_BC_HOST_ROW || per_reach) ? 1 : 0;
-  b->have_bc[side] = true;
-  b->kinds_per_reach[side] = false; b->any_storage[side] = fs::bc_is_storage(kind); b->some_host_rows[side] = false;
-  // the other side has per-reach kinds: this side's one kind goes into every slot
-  if (b->reach_kinds && fill_side_kinds(b, side, kind)) return -1;
-  return 0;
+  return set_side_kind(b, side, kind, (kind == FS_BC_HOST_ROW || per_reach) ? 1 : 0);
 }
 
 int fs_batch_set_state(fs_batch *b, const double *h, const double *Q) {
@@ -1135,10 +1139,9 @@ int fs_batch_init_state(fs_batch *b, int32_t method, const double *flow, const d
                 " must be set first");
   if (method != FS_IC_STEADY && !depth_ds) return fail("fs_batch_init_state: depth_ds is needed by FS_IC_LINEAR and FS_IC_GVF");
   if (method == FS_IC_LINEAR && !depth_us) return fail("fs_batch_init_state: depth_us is needed by FS_IC_LINEAR");
-  const bool uniform = b->d.section_mode == FS_SEC_RECT_UNIFORM || b->d.section_mode == FS_SEC_TRAP_UNIFORM;
   const size_t B = b->d.n_reaches, N = b->d.n_nodes;
   if (method == FS_IC_STEADY) {
-    if (!bed_slope && !uniform) return fail("fs_batch_init_state: FS_IC_STEADY needs bed_slope in section modes FS_SEC_TABLE and FS_SEC_IRREGULAR");
+    if (!bed_slope && !fs::sec_is_uniform(b->d.section_mode)) return fail("fs_batch_init_state: FS_IC_STEADY needs bed_slope in section modes FS_SEC_TABLE and FS_SEC_IRREGULAR");
     if (bed_slope)        // the reference's None (channel.py:299-300), at a reach's own nodes
       for (size_t r = 0; r < (bed_slope_per_reach ? B : 1); ++r) {
         size_t n_r = N;
@@ -1158,9 +1161,7 @@ int fs_batch_init_state(fs_batch *b, int32_t method, const double *flow, const d
   if (method == FS_IC_LINEAR && upload(b, d_us, depth_us, B)) return -1;
   if (method != FS_IC_STEADY && upload(b, d_ds, depth_ds, B)) return -1;
   if (method == FS_IC_STEADY && bed_slope && upload(b, d_slope, bed_slope, bed_slope_per_reach ? B * N : N)) return -1;
-  HIP_TRY(b->ic_info.ensure(2 * B * sizeof(int32_t)));
-  HIP_TRY(hipMemsetAsync(b->ic_info.get(), 0, B * sizeof(int32_t), b->stream));
-  HIP_TRY(hipMemsetAsync(b->ic_info.get<int32_t>() + B, 0xff, B * sizeof(int32_t), b->stream));
+  if (prepare_info(b, b->ic_info)) return -1;
   {
     TraceRange range_("flowsim:init_state");
     const bool launched = with_real(b, [&](auto real) {
@@ -1181,11 +1182,7 @@ int fs_batch_init_state(fs_batch *b, int32_t method, const double *flow, const d
     HIP_TRY(hipGetLastError());
   }
   if (spread_level0(b) || begin_at_level0(b)) return -1;
-  if (info) {
-    HIP_TRY(hipMemcpyAsync(info, b->ic_info.get(), 2 * B * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-  }
-  return 0;
+  return return_info(b, b->ic_info, info);
 }
 
 int fs_batch_set_bc_sampled(fs_batch *b, int32_t side, int32_t kind, const double *params, int32_t n_params, const double *times,
@@ -1197,8 +1194,7 @@ int fs_batch_set_bc_sampled(fs_batch *b, int32_t side, int32_t kind, const doubl
     return fail("fs_batch_set_bc_sampled: kind must be FS_BC_FLOW_HYDROGRAPH or FS_BC_STAGE_HYDROGRAPH");
   if (!b->have_scheme) return fail("fs_batch_set_bc_sampled: the scheme (fs_batch_set_scheme: dt) must be set first");
   const size_t B = b->d.n_reaches, L = b->d.max_levels;
-  const bool tables = b->d.section_mode == FS_SEC_TABLE || b->d.section_mode == FS_SEC_IRREGULAR;
-  if (const char *err = fs::check_bc(side, kind, params, n_params, 0, true, B, tables)) return fail(err);
+  if (const char *err = fs::check_bc(side, kind, params, n_params, 0, true, B, fs::sec_has_tables(b->d.section_mode))) return fail(err);
   if (const char *err = fs::check_sampled_tables(times, values, n_pts, n_tables, table_of, B)) return fail(err);
   FS_ON_DEVICE(b);
   HIP_TRY(hipStreamSynchronize(b->stream));      // an earlier call's kernels are through with the inputs
@@ -1209,7 +1205,7 @@ int fs_batch_set_bc_sampled(fs_batch *b, int32_t side, int32_t kind, const doubl
   if (upload_f64(in[0], times, (size_t)n_pts) || upload_f64(in[1], values, (size_t)n_tables * n_pts)) return -1;
   if (table_of) {
     HIP_TRY(in[2].reserve(B * sizeof(int32_t)));
-    HIP_TRY(hipMemcpy(in[2].get(), table_of, B * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (upload_i32(in[2].get<int32_t>(), table_of, B)) return -1;
   }
   const double *per[3] = {scale, offset, shift};
   for (int i = 0; i < 3; ++i)
@@ -1232,11 +1228,7 @@ int fs_batch_set_bc_sampled(fs_batch *b, int32_t side, int32_t kind, const doubl
     if (!launched) return fail("fs_batch_set_bc_sampled: this build has no forcing kernels");
     HIP_TRY(hipGetLastError());
   }
-  b->bc_kind[side] = kind; b->bc_stride[side] = 0;
-  b->have_bc[side] = true;
-  b->kinds_per_reach[side] = false; b->any_storage[side] = false; b->some_host_rows[side] = false;
-  if (b->reach_kinds && fill_side_kinds(b, side, kind)) return -1;
-  return 0;
+  return set_side_kind(b, side, kind, 0);
 }
 
 int fs_batch_route_pool(fs_batch *b, int32_t side, const double *curve_stage, const double *curve_volume, int32_t n_curve,
@@ -1262,9 +1254,7 @@ int fs_batch_route_pool(fs_batch *b, int32_t side, const double *curve_stage, co
   const double *reach_dt;
   if (forcing_reach_dt(b, &reach_dt)) return -1;
   HIP_TRY(b->pool_stage.ensure(L * B * sizeof(double)));
-  HIP_TRY(b->pool_info.ensure(2 * B * sizeof(int32_t)));
-  HIP_TRY(hipMemsetAsync(b->pool_info.get(), 0, B * sizeof(int32_t), b->stream));
-  HIP_TRY(hipMemsetAsync(b->pool_info.get<int32_t>() + B, 0xff, B * sizeof(int32_t), b->stream));
+  if (prepare_info(b, b->pool_info)) return -1;
   {
     TraceRange range_("flowsim:forcing");
     const bool launched = with_real(b, [&](auto real) {
@@ -1282,11 +1272,7 @@ int fs_batch_route_pool(fs_batch *b, int32_t side, const double *curve_stage, co
     if (!launched) return fail("fs_batch_route_pool: this build has no forcing kernels");
     HIP_TRY(hipGetLastError());
   }
-  if (info) {
-    HIP_TRY(hipMemcpyAsync(info, b->pool_info.get(), 2 * B * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-  }
-  return 0;
+  return return_info(b, b->pool_info, info);
 }
 
 int fs_batch_get_bc_target(fs_batch *b, int32_t side, int32_t first, int32_t n, double *out) {
@@ -1327,7 +1313,7 @@ int fs_batch_iterate(fs_batch *b, int32_t *n_open) {
   if (!b) return fail("null handle");
   if (check_ready(b, "fs_batch_iterate")) return -1;
   if (b->level + 1 >= b->d.max_levels) return fail("fs_batch_iterate: would run past max_levels");
-  if (b->d.section_mode != FS_SEC_TABLE && b->d.section_mode != FS_SEC_IRREGULAR)
+  if (!fs::sec_has_tables(b->d.section_mode))
     return fail("fs_batch_iterate: section mode FS_SEC_TABLE or FS_SEC_IRREGULAR required");
   FS_ON_DEVICE(b);
   if (launch_steps(b, 1, 1)) return -1;
@@ -1452,17 +1438,13 @@ int fs_batch_get_iterations(fs_batch *b, int32_t first, int32_t n, int32_t *out)
   FS_ON_DEVICE(b);
   if (check_levels(b, "fs_batch_get_iterations", first, n)) return -1;
   const size_t B = b->d.n_reaches;
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  HIP_TRY(hipMemcpy(out, b->iters.get<int32_t>() + (size_t)first * B, (size_t)n * B * 4, hipMemcpyDeviceToHost));
-  return 0;
+  return fetch(b, out, b->iters.get<int32_t>() + (size_t)first * B, (size_t)n * B * 4);
 }
 
 int fs_batch_get_status(fs_batch *b, int32_t *out) {
   if (!b || !out) return fail("fs_batch_get_status: null argument");
   FS_ON_DEVICE(b);
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  HIP_TRY(hipMemcpy(out, b->status.get(), (size_t)b->d.n_reaches * 4, hipMemcpyDeviceToHost));
-  return 0;
+  return fetch(b, out, b->status.get(), (size_t)b->d.n_reaches * 4);
 }
 
 int fs_batch_get_history(fs_batch *b, int32_t first, int32_t n, double *h, double *Q) {
@@ -1695,9 +1677,7 @@ static int ready_integrals(fs_batch *b, const char *entry) {
   }
   if (b->bal_scheme_stale || !b->bal_scheme) {
     const double wide[3] = {b->theta, b->dt, b->dx};
-    std::vector<double> v(3 * B);
-    for (int i = 0; i < 3; ++i)
-      for (size_t r = 0; r < B; ++r) v[(size_t)i * B + r] = b->rs_host[i].empty() ? wide[i] : b->rs_host[i][r];
+    const std::vector<double> v = fs::reach_scheme_rows(b->rs_host, wide, 3, B, true);
     HIP_TRY(hipStreamSynchronize(b->stream));      // an earlier call's kernels are through with the values before
     if (upload_f64(b->bal_scheme, v.data(), v.size())) return -1;
     b->bal_scheme_stale = false;
@@ -1819,9 +1799,7 @@ int32_t fs_batch_last_launch_count(fs_batch *b) { return b ? b->launches : 0; }
 // diagnostic builds only: out[B][16][12] cycle sums (waves beyond W are zero)
 int fs_debug_stamps(fs_batch *b, unsigned long long *out) {
   if (!b || !out || !b->dbg) return fail("fs_debug_stamps: not available");
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  HIP_TRY(hipMemcpy(out, b->dbg.get(), (size_t)b->d.n_reaches * 16 * 12 * 8, hipMemcpyDeviceToHost));
-  return 0;
+  return fetch(b, out, b->dbg.get(), (size_t)b->d.n_reaches * 16 * 12 * 8);
 }
 #endif
 

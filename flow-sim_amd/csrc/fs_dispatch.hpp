@@ -1,7 +1,8 @@
 // fs_dispatch.hpp - which kernel instantiation a batch gets: the key that describes an instantiation, the query a batch asks with,
-// the environment's overrides, and fits() / pick() over a table of keys.  Plain C++17 apart from the __host__ __device__ mark of
-// bc_is_light under hipcc (the kernels use it too): tests/dispatch/ builds the key table from the very lists of the library
-// (fs_entry_list.hpp) with the system compiler and checks every choice against tests/golden/dispatch/choices.npz.
+// the environment's overrides, and fits() / pick() over a table of keys; and what a launch of the chosen one needs beside the batch's
+// own arrays (plan_launch).  Plain C++17 apart from the __host__ __device__ marks of bc_is_light and team_mailbox_bytes under hipcc
+// (the kernels use them too): tests/dispatch/ builds the key table from the very lists of the library (fs_entry_list.hpp) with the
+// system compiler, checks every choice against tests/golden/dispatch/choices.npz and every plan against the kernels' layouts.
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -11,6 +12,7 @@
 
 #include "../../include/flowsim_abi.h"
 #include "fs_entry_list.hpp"      // FS_KIND_*: what FS_KEY reads a row's kind with
+#include "fs_host_pack.hpp"       // sec_is_uniform
 
 #ifndef FS_ST_HD
 #ifdef __HIPCC__
@@ -131,6 +133,33 @@ int pick(const Row *table, int n, const Query &q, const Overrides &o, std::strin
   if (best < 0 && why) *why = "no kernel instantiation for N=" + std::to_string(q.N) + " (supported: 2..32768 nodes for the uniform section "
                               "modes, 2..16384 for tables and polylines)";
   return best;
+}
+
+// ---- what one launch of an instantiation needs beside the batch's own arrays (fs_abi.hip: launch_steps makes the HIP calls) ----
+constexpr int kTeamWords = 12;   // per mailbox slot: the segment (8), the wave's residual sum (1), two ints (monitor word, boundary flag), pad
+// bytes of one reach's mailbox of one iteration parity: a slot per (member, wave) and one for the upstream row, kTeamWords 16-byte (value,
+// tag) words each.  The host allocates [B][2] of them; the team kernel (fs_kernel.hpp) strides them by this very number
+FS_ST_HD constexpr size_t team_mailbox_bytes(int G, int W) { return (size_t)(G * W + 1) * kTeamWords * 16; }
+
+struct LaunchPlan {
+  int passes = 0;                 // multi-pass kernel: passes of 64 W M rows over a reach (0: another kernel)
+  size_t kc_scratch_elems = 0;    //   its level constants [B][4][passes * 64 W M]; none for uniform sections (fs_long.hpp recomputes them)
+  int team_size = 0;              // team kernel: G workgroups of 64 W M rows per reach (0: another kernel)
+  size_t team_mail_bytes = 0;     //   their mailboxes [B][2][G W + 1][kTeamWords]
+  // a launch of several levels: a reach that fails on a later one gets back what the launch began with (one level: nothing to keep)
+  bool keep_entry = false;        //   the state: the multi-pass kernel of the uniform section modes writes every accepted level to hk / Qk
+  bool keep_stage = false;        //   the reservoir stage: every step kernel writes back the last one it accepted
+};
+inline LaunchPlan plan_launch(const KernelKey &k, int section_mode, size_t B, size_t N, int n_steps, bool storage_downstream) {
+  LaunchPlan p;
+  const size_t grid = (size_t)64 * k.W * k.M;
+  const int grids = (int)((N + grid - 1) / grid);
+  const bool uniform = sec_is_uniform(section_mode);
+  if (k.longk) { p.passes = grids; p.kc_scratch_elems = uniform ? 0 : B * 4 * grids * grid; }
+  if (k.team) { p.team_size = grids; p.team_mail_bytes = B * 2 * team_mailbox_bytes(grids, k.W); }
+  p.keep_entry = k.longk && uniform && n_steps > 1;
+  p.keep_stage = storage_downstream && n_steps > 1;
+  return p;
 }
 
 }  // namespace fs

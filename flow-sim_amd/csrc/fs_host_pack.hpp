@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <new>
@@ -22,6 +23,9 @@ enum { FS_GEOX_SM = FS_GEO_NPARAM, FS_GEOX_SFP, FS_GEOX_TB, FS_GEOX_AM, FS_GEOX_
        FS_GEOX_KR15, FS_GEOX_NROWS };
 
 FS_ST_HD constexpr bool bc_is_storage(int kind) { return kind == FS_BC_STORAGE || kind == FS_BC_STORAGE_CURVE; }
+// the section modes of one closed form per reach, and those with a table row per node (FS_SEC_IRREGULAR: and polylines)
+constexpr bool sec_is_uniform(int sec) { return sec == FS_SEC_RECT_UNIFORM || sec == FS_SEC_TRAP_UNIFORM; }
+constexpr bool sec_has_tables(int sec) { return sec == FS_SEC_TABLE || sec == FS_SEC_IRREGULAR; }
 
 // The caller's TrapezoidalSection table [FS_GEO_NPARAM][N] plus the rows of what follows from it alone
 // (FS_GEOX_*: side-slope roots, bankfull geometry, reciprocal / -1.5-power roughnesses), computed here
@@ -86,6 +90,20 @@ struct PolyTableLimits {
   size_t max_bytes = (size_t)8 << 30;        // FS_POLY_TABLE_MAX_BYTES
 };
 
+inline PolyTableLimits poly_limits_from_environment() {
+  PolyTableLimits how;
+  if (const char *env = std::getenv("FS_POLY_TABLE_MAX_BYTES")) how.max_bytes = (size_t)std::strtoull(env, nullptr, 10);
+  how.force_walk = std::getenv("FS_POLY_WALK") != nullptr;
+  return how;
+}
+
+// no stage tables for n_sets channels of N nodes with max_pts stations?  *table_mib: what the tables take, whole MiB
+inline bool poly_tables_walk(size_t n_sets, size_t N, int32_t max_pts, const PolyTableLimits &how, size_t *table_mib) {
+  const double table_bytes = (double)n_sets * (double)N * (double)poly_table_stride(max_pts) * sizeof(double);
+  if (table_mib) *table_mib = (size_t)(table_bytes / (1 << 20));
+  return how.force_walk || table_bytes > (double)how.max_bytes;
+}
+
 // what set_irregular uploads: n_sets channels (1: shared by the batch; B: one per reach), each packed and extended
 struct IrregularPlan {
   std::vector<double> xt, zt, lim;    // [n_sets][P][N], [n_sets][P][N], [n_sets][2][N]
@@ -102,9 +120,7 @@ inline std::string plan_irregular(const double *table, const int32_t *n_pts, int
   out.xt.assign(n_sets * P * N, 0.0); out.zt.assign(n_sets * P * N, 0.0); out.lim.assign(n_sets * 2 * N, 0.0);
   out.tabs.resize(n_sets * per);
   const size_t tstride = (size_t)poly_table_stride(max_pts);
-  const double table_bytes = (double)n_sets * (double)N * (double)tstride * sizeof(double);
-  out.walk = how.force_walk || table_bytes > (double)how.max_bytes;
-  out.table_mib = (size_t)(table_bytes / (1 << 20));
+  out.walk = poly_tables_walk(n_sets, N, max_pts, how, &out.table_mib);
   out.tz.clear();
   try {
     if (!out.walk) out.tz.assign(n_sets * N * tstride, std::numeric_limits<double>::infinity());
@@ -208,17 +224,22 @@ inline const char *check_bc(int side, int kind, const double *params, int n_para
   return nullptr;
 }
 
-// the [5][B] array the kernels of boundary classes 0 and -1 read (theta, dt, dx, tolerance, max_iter): per-reach values where the
-// caller gave them (per_reach[i] not empty), the batch's elsewhere.  Empty: nothing is per reach.
-inline std::vector<double> merge_reach_scheme(const std::vector<double> per_reach[5], const double wide[5], size_t B) {
-  bool any = false;
-  for (int i = 0; i < 5; ++i) any = any || !per_reach[i].empty();
+// the first `rows` of the scheme values (theta, dt, dx, tolerance, max_iter) as a [rows][B] array: per-reach values where the caller
+// gave them (per_reach[i] not empty), the batch's elsewhere.  Unless `always`, empty where nothing is per reach.
+inline std::vector<double> reach_scheme_rows(const std::vector<double> *per_reach, const double *wide, int rows, size_t B, bool always) {
+  bool any = always;
+  for (int i = 0; i < rows; ++i) any = any || !per_reach[i].empty();
   std::vector<double> v;
   if (!any) return v;
-  v.resize(5 * B);
-  for (int i = 0; i < 5; ++i)
+  v.resize(rows * B);
+  for (int i = 0; i < rows; ++i)
     for (size_t r = 0; r < B; ++r) v[i * B + r] = per_reach[i].empty() ? wide[i] : per_reach[i][r];
   return v;
+}
+
+// the [5][B] array the kernels of boundary classes 0 and -1 read.  Empty: nothing is per reach.
+inline std::vector<double> merge_reach_scheme(const std::vector<double> per_reach[5], const double wide[5], size_t B) {
+  return reach_scheme_rows(per_reach, wide, 5, B, false);
 }
 
 }  // namespace fs

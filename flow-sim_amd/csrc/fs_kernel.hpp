@@ -109,7 +109,6 @@ constexpr int kTeamSlots = 64;   // (member, wave) segments of a team: the top t
 // 158 795 ticks in 0.079 ms of HIP-event time).  Eight seconds: a team's members start in ticket order as CUs become free, so the wait is bounded by the
 // longest kernel of a co-tenant that holds the CUs meanwhile, not by anything of this library's own
 constexpr unsigned long long kTeamPatience = 16000000000ull;
-constexpr int kTeamWords = 12;   // per slot: the segment (8), the wave's residual sum (1), two ints (monitor word, boundary flag), pad
 
 template <typename R, int SEC> struct Geometry;
 
@@ -479,9 +478,9 @@ __global__ __launch_bounds__(64 * W, (min_waves<R, SEC, M, W, BCK, TEAM>())) voi
   const int G = kTeam ? a.team_size : 1;
   const int reach = kTeam ? job / G : job, member = kTeam ? job - reach * G : 0;
   const int gt = member * T + t;                 // the lane's place in the reach's lane grid (t itself unless the reach is a team's)
-  // the reach's mailbox of one iteration parity as a raw buffer ((G W + 1) slots of kTeamWords (value, tag) pairs)
+  // the reach's mailbox of one iteration parity as a raw buffer ((G W + 1) slots of kTeamWords (value, tag) pairs: fs_dispatch.hpp)
   auto mbox = [&](int par) __attribute__((always_inline)) {
-    const size_t bytes = (size_t)(G * W + 1) * kTeamWords * 16;
+    const size_t bytes = team_mailbox_bytes(G, W);
     char *base = reinterpret_cast<char *>(a.team_mail) + ((size_t)reach * 2 + par) * bytes;
     return __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)bytes, 0x27000);
   };

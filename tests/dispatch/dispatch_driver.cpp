@@ -4,6 +4,10 @@
 //   dispatch_driver grid OUT                 the chosen index (or -1) of every query of the grid, int16, to the file OUT
 //   dispatch_driver query dtype sec N usk dsk need_diag need_any hetero
 //                                            the chosen index and, on the next line, the reason where there is none
+//   dispatch_driver plan IN                  IN: one launch per line: entry sec N B n_steps storage_downstream.  Prints per line whether
+//                                            the entry fits a batch of its own kind with N nodes, then fs::plan_launch: passes,
+//                                            kc_scratch_elems, team_size, team_mail_bytes, keep_entry, keep_stage, and the bytes of one
+//                                            mailbox as the team kernel strides them (fs::team_mailbox_bytes)
 // The overrides come from the environment, as in the library (FS_KERNEL_INDEX, FS_KERNEL_SHAPE, FS_KERNEL_GENERAL, FS_NO_TEAM, FS_TEAM_M).
 #include <cstdint>
 #include <cstdio>
@@ -60,6 +64,24 @@ int main(int argc, char **argv) {
     std::printf("%d\n%s\n", chosen, why.c_str());
     return 0;
   }
-  std::fprintf(stderr, "usage: %s table | grid OUT | query dtype sec N usk dsk need_diag need_any hetero\n", argv[0]);
+  if (argc == 3 && !std::strcmp(argv[1], "plan")) {
+    FILE *f = std::fopen(argv[2], "r");
+    if (!f) return 2;
+    int entry, sec, n_steps, storage;
+    long long B, N;
+    while (std::fscanf(f, "%d %d %lld %lld %d %d", &entry, &sec, &N, &B, &n_steps, &storage) == 6) {
+      if (entry < 0 || entry >= kNumKeys) return 2;
+      const fs::KernelKey &k = kKeys[entry].key;
+      fs::Query q;      // a batch the entry was compiled for: its type, mode and boundary pair (any pair: flow in, normal depth out)
+      q.dtype = k.dtype; q.sec = k.sec; q.N = (int)N; q.usk = FS_BC_FLOW_HYDROGRAPH; q.dsk = k.bck >= 2 ? k.bck - 2 : FS_BC_NORMAL_DEPTH;
+      q.need_diag = k.diag != 0;
+      const fs::LaunchPlan p = fs::plan_launch(k, sec, (size_t)B, (size_t)N, n_steps, storage != 0);
+      std::printf("%d %d %zu %d %zu %d %d %zu\n", fs::fits(k, q, o) ? 1 : 0, p.passes, p.kc_scratch_elems, p.team_size, p.team_mail_bytes,
+                  p.keep_entry ? 1 : 0, p.keep_stage ? 1 : 0, fs::team_mailbox_bytes(p.team_size, k.W));
+    }
+    std::fclose(f);
+    return 0;
+  }
+  std::fprintf(stderr, "usage: %s table | grid OUT | query dtype sec N usk dsk need_diag need_any hetero | plan IN\n", argv[0]);
   return 1;
 }

@@ -9,8 +9,10 @@
 //                                      wide side kind n_params per_reach has_params has_target B tables params...
 //                                      per side n_params has_target B tables kinds[B] params[n_params][B]
 //                                      scheme B mask wide[5] values[5][B]         (mask bit i: row i is per reach)
+//                                      walk n_sets N max_pts force_walk max_bytes
 //                                    Prints per case the text of fs::check_bc / fs::check_bc_per_reach or "ok" (per reach: followed by
-//                                    any_storage, some_host_rows and the representative kind), or the rows of fs::merge_reach_scheme.
+//                                    any_storage, some_host_rows and the representative kind), or the rows of fs::merge_reach_scheme,
+//                                    or what fs::poly_tables_walk says and its MiB of tables.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -112,6 +114,14 @@ static int run_checks(const char *in) {
       if (m.empty()) std::printf("none");
       for (double val : m) std::printf("%a ", val);
       std::printf("\n");
+    } else if (what == "walk") {
+      const size_t n_sets = (size_t)next(), N = (size_t)next();
+      const int32_t max_pts = (int32_t)next();
+      fs::PolyTableLimits how;
+      how.force_walk = next() != 0; how.max_bytes = (size_t)next();
+      size_t mib = 0;
+      const bool walk = fs::poly_tables_walk(n_sets, N, max_pts, how, &mib);
+      std::printf("%d %zu\n", walk ? 1 : 0, mib);
     } else if (!what.empty()) {
       return 2;
     }

@@ -20,7 +20,6 @@ The bound is derived, not tuned.  ratio = max_k |residual_k| / (dt dx sqrt(N - 1
     irr_levee (polyline) N = 11    2.6e-7                     5.5e-7"""
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -29,8 +28,8 @@ from conftest import GOLDEN, ROOT
 from oracle import preissmann_oracle as O
 
 import derived_reference as D
+import host_driver
 
-CSRC = os.path.join(ROOT, "flow-sim_amd", "csrc")
 DRIVER = os.path.join(ROOT, "tests", "balance", "balance_driver.cpp")
 NAN = float("nan")
 LANES = 64
@@ -135,21 +134,14 @@ def numbers(a):
 @pytest.fixture(scope="module")
 def driver_output(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("balance")
-    exe = str(tmp / "balance_driver")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off", "-fsanitize=address,undefined",
-           "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-I", CSRC, "-o", exe, DRIVER]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = host_driver.build(DRIVER, tmp, extra_flags=["-ffp-contract=off"])
     lines = [f"W {name} {len(t)} {V} {numbers(t)}" for name, (t, V) in row_cases().items()]
     lines += [f"B {name} {len(ev)} {theta!r} {dt!r} {numbers(ev)} {numbers(vol)} {numbers(qi)} {numbers(qo)}"
               for name, (ev, vol, qi, qo, theta, dt) in balance_cases().items()]
     path = tmp / "records.txt"
     path.write_text("\n".join(lines) + "\n")
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe, str(path)], capture_output=True, text=True, env=env, timeout=60)
-    assert r.returncode == 0 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
     got = {}
-    for line in r.stdout.splitlines():
+    for line in host_driver.run(exe, [path], timeout=60).splitlines():
         f = line.split()
         got[f[1]] = np.array([float(v) for v in f[2:]])
     assert len(got) == len(lines)

@@ -25,7 +25,7 @@ from fixture_batch import boundary_spec, merge_specs
 from flowsim_amd import BoundarySpec
 from flowsim_amd import _abi as A
 from flowsim_amd import _pack
-from host_pack_driver import CSRC, build_driver, line, run_driver
+from host_driver import PACK_DRIVER, build, line, run
 from oracle import preissmann_oracle as O
 
 RECORD = os.path.join(GOLDEN, "batch_pack", "record.json")
@@ -263,7 +263,7 @@ def test_the_library_accepts_what_python_packs(tmp_path):
         lines.append(check_line(form, side, B, packed))
     fin = tmp_path / "checks.txt"
     fin.write_text("\n".join(lines) + "\n")
-    out = run_driver(build_driver(tmp_path, [CSRC]), ["checks", str(fin)]).splitlines()
+    out = run(build(PACK_DRIVER, tmp_path), ["checks", fin], timeout=600).splitlines()
     assert len(out) == len(todo)
     wrong = [(name, got) for (name, form, _, _, _, spec, answer), got in zip(todo, out) if got != expected(form, spec, answer)]
     assert not wrong, (len(wrong), wrong[:5])

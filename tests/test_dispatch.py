@@ -3,7 +3,8 @@ instantiation lists (fs_entry_list.hpp) - until now the choice was only seen thr
 
 tests/dispatch/dispatch_driver.cpp is built with the system compiler under AddressSanitizer and UBSan and answers for a grid of
 queries: both arithmetic types x the four section modes x 19 node counts x every pair of boundary kinds x need_diag x need_any x
-the four hetero values = 243 200 queries, under each of ten settings of the environment's overrides.
+the four hetero values = 243 200 queries, under each of ten settings of the environment's overrides.  Its `plan` command answers
+what a launch of an entry reserves and keeps (fs::plan_launch), held to the layouts the kernels address as written out in plan_check.
 
 tests/golden/dispatch/choices.npz is the record they are held against: the 115 keys in table order ("keys": dtype, sec, M, W, full, bck,
 diag, longk, tail, team), the chosen index or -1 of every query under every setting ("choice_<setting>"), and the tables of the
@@ -22,7 +23,8 @@ import pytest
 
 from conftest import ROOT
 
-CSRC = os.path.join(ROOT, "flow-sim_amd", "csrc")
+from host_driver import CSRC, build, run
+
 DRIVER = os.path.join(ROOT, "tests", "dispatch", "dispatch_driver.cpp")
 RECORD = os.path.join(ROOT, "tests", "golden", "dispatch", "choices.npz")
 HIPCC = "/opt/rocm/bin/hipcc"
@@ -44,23 +46,8 @@ RECT, TRAP, TABLE, IRREGULAR = 0, 1, 2, 3
 FLOW, NORMAL_DEPTH, RATING_BLEND = 0, 3, 6
 
 
-def build_driver(out_dir, include_dirs):
-    exe = os.path.join(str(out_dir), "dispatch_driver")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-           "-fno-omit-frame-pointer"]
-    for d in include_dirs:
-        cmd += ["-I", str(d)]
-    r = subprocess.run(cmd + ["-o", exe, DRIVER], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
 def run_driver(exe, args, env_extra):
-    env = {k: v for k, v in os.environ.items() if k not in OVERRIDE_VARS}
-    env.update(env_extra, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe, *args], capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
-    return r.stdout
+    return run(exe, args, env_extra, drop_env=OVERRIDE_VARS, timeout=300)
 
 
 def grid_choices(exe, setting, tmp):
@@ -79,7 +66,7 @@ def query(exe, dtype, sec, N, usk, dsk, need_diag=0, need_any=0, hetero=0, env=N
 def driver(tmp_path_factory):
     if shutil.which("g++") is None:
         pytest.skip("no system C++ compiler")
-    return build_driver(tmp_path_factory.mktemp("dispatch"), [CSRC])
+    return build(DRIVER, tmp_path_factory.mktemp("dispatch"))
 
 
 @pytest.fixture(scope="module")
@@ -141,7 +128,7 @@ def test_the_order_of_preference_in_plain_cases(driver, record):
     def chosen(sec, N, dsk, history, **kw):
         i, why = query(driver, F64, sec, N, FLOW, dsk, need_diag=int(history), **kw)
         assert i >= 0, why
-        return dict(zip(("dtype", "sec", "M", "W", "full", "bck", "diag", "longk", "tail", "team"), keys[i].tolist()))
+        return dict(zip(KEY_FIELDS, keys[i].tolist()))
 
     want = {   # N -> (M, W, full, class, diag without history)
         4096: (16, 4, 1, cls, 0), 4000: (16, 4, 0, cls, 0), 2048: (16, 2, 1, cls, 0), 1024: (16, 1, 1, cls, 0), 512: (8, 1, 1, cls, 0),
@@ -193,10 +180,81 @@ def test_the_record_catches_a_mutation(record, tmp_path, name):
     assert src.count(old) == 1, name
     with open(tmp_path / "fs_dispatch.hpp", "w") as f:
         f.write(src.replace(old, new))
-    exe = build_driver(tmp_path, [tmp_path, CSRC])          # the copy first: the driver's #include "fs_dispatch.hpp" finds it
+    exe = build(DRIVER, tmp_path, [tmp_path, CSRC])          # the copy first: the driver's #include "fs_dispatch.hpp" finds it
     moved = {s: int(np.sum(grid_choices(exe, s, tmp_path) != record["choice_" + s])) for s in CHOOSING}
     print(name, moved)
     assert moved["none"] > 0, moved
+
+
+# ---- the launch plan (fs::plan_launch): what launch_steps reserves and keeps for the entry a batch got ----
+KEY_FIELDS = ("dtype", "sec", "M", "W", "full", "bck", "diag", "longk", "tail", "team")
+SLOT = 12 * 16      # fs_kernel.hpp, KernelArgs::team_mail: [B][2][G W + 1][kTeamWords = 12] of 16-byte (value, tag) words
+
+
+def plan_cases(keys):
+    """(entry, sec, N, B, n_steps, storage_downstream): every team and multi-pass entry where a rounding slip in ceil(N / grid) shows -
+    one row past a lane grid, two grids, one row short of the capacity, the capacity - and one single-workgroup entry per section mode"""
+    sizes, single = [], {}
+    for i, row in enumerate(keys.tolist()):
+        k = dict(zip(KEY_FIELDS, row))
+        grid = 64 * k["W"] * k["M"]
+        if k["team"] or k["longk"]:
+            sizes += [(i, k["sec"], N) for N in (grid + 1, 2 * grid, grid * 64 // k["W"] - 1, grid * 64 // k["W"])]
+        elif not k["full"] and k["tail"] < 0:
+            single.setdefault(k["sec"], (i, k["sec"], grid))
+    return [(*s, B, n_steps, storage) for s in sizes + sorted(single.values()) for B in (1, 3) for n_steps in (1, 2) for storage in (0, 1)]
+
+
+def plan_check(exe, keys, tmp):
+    """(the cases that fit their entry, those of them whose plan is not what the layout comments of fs_kernel.hpp - KernelArgs:
+    kc_scratch, passes, team_size, team_mail - and the two restore kernels of fs_abi.hip say)"""
+    cases = plan_cases(keys)
+    with open(tmp / "plans.txt", "w") as f:
+        f.write("".join(" ".join(map(str, c)) + "\n" for c in cases))
+    out = [list(map(int, ln.split())) for ln in run_driver(exe, ["plan", tmp / "plans.txt"], {}).splitlines()]
+    assert len(out) == len(cases)
+    fit, bad = [], []
+    for case, (fits, *got, stride) in zip(cases, out):      # got: passes, kc_scratch_elems, team_size, team_mail_bytes, keep_entry, keep_stage
+        (i, sec, N, B, n_steps, storage), k = case, dict(zip(KEY_FIELDS, keys[case[0]].tolist()))
+        if not fits:
+            continue
+        grid, W, uniform = 64 * k["W"] * k["M"], k["W"], sec in (RECT, TRAP)
+        G = -(-N // grid)
+        assert G <= 64 // W
+        want = [G * k["longk"], B * 4 * G * grid * (k["longk"] and not uniform), G * k["team"], B * 2 * (G * W + 1) * SLOT * k["team"],
+                int(k["longk"] and uniform and n_steps > 1), int(storage and n_steps > 1)]
+        # the end of the last slot a team addresses - reach B - 1, parity 1, the upstream row's slot G W - with mailboxes `stride` bytes apart
+        last_end = (((B - 1) * 2 + 1) * stride + G * W * SLOT + SLOT) * k["team"]
+        fit.append(case)
+        if got != want or last_end != got[3]:
+            bad.append((case, got, want, last_end))
+    return fit, bad
+
+
+def test_the_launch_plan_is_what_the_kernels_address(driver, record, tmp_path):
+    """crossed with B in {1, 3}, n_steps in {1, 2} and a storage boundary downstream or none.  A single-workgroup entry gets no
+    passes, scratch, team or entry state; its reservoir stage is kept like every kernel's (restore_failed_stage), by the same rule."""
+    keys = record["keys"]
+    fit, bad = plan_check(driver, keys, tmp_path)
+    kinds = {(int(keys[c[0]][7]), int(keys[c[0]][9]), c[1]) for c in fit}
+    assert {(0, 0, sec) for sec in (RECT, TRAP, TABLE, IRREGULAR)} <= kinds and {(1, 0, RECT), (1, 0, TABLE), (0, 1, RECT)} <= kinds
+    assert {c[0] for c in fit} == {c[0] for c in plan_cases(keys)}, "an entry none of whose sizes fits it"
+    print(len(fit), "cases fit,", len({c[0] for c in fit}), "entries")
+    assert not bad, (len(bad), bad[:3])
+
+
+def test_the_plan_check_catches_a_mailbox_one_slot_short(record, tmp_path):
+    """fs_dispatch.hpp copied with G W slots per mailbox in place of G W + 1 (none for the upstream row): every team case fails"""
+    if shutil.which("g++") is None:
+        pytest.skip("no system C++ compiler")
+    old, new = "(size_t)(G * W + 1) * kTeamWords * 16", "(size_t)(G * W) * kTeamWords * 16"
+    src = open(os.path.join(CSRC, "fs_dispatch.hpp")).read()
+    assert src.count(old) == 1
+    with open(tmp_path / "fs_dispatch.hpp", "w") as f:
+        f.write(src.replace(old, new))
+    fit, bad = plan_check(build(DRIVER, tmp_path, [tmp_path, CSRC]), record["keys"], tmp_path)
+    team = [c for c in fit if record["keys"][c[0]][9]]
+    assert team and [b[0] for b in bad] == team, (len(bad), len(team))
 
 
 MINIMAL = {"1": ["-DFS_MINIMAL=1"], "2": ["-DFS_MINIMAL=2"], "3": ["-DFS_MINIMAL=3"], "1_no_tail": ["-DFS_MINIMAL=1", "-DFS_NO_TAIL"],

@@ -3,14 +3,14 @@ tests/envelope/envelope_driver.cpp is built here with the system compiler under 
 columns of the reference's own histories (tests/golden/akbari.npz, irr_levee.npz, bc_compound_normal.npz) and on made-up series, and
 held to np.max / argmax / min / argmin and to a written-out crossing loop."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT
 
-CSRC = os.path.join(ROOT, "flow-sim_amd", "csrc")
+import host_driver
+
 DRIVER = os.path.join(ROOT, "tests", "envelope", "envelope_driver.cpp")
 FIXTURES = ("akbari", "irr_levee", "bc_compound_normal")
 FIELDS = ("depth", "flow", "derived_level", "derived_velocity", "derived_froude_number", "derived_top_width")
@@ -70,19 +70,12 @@ def cases():
 @pytest.fixture(scope="module")
 def driver_output(tmp_path_factory, cases):
     tmp = tmp_path_factory.mktemp("envelope")
-    exe = str(tmp / "envelope_driver")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off", "-fsanitize=address,undefined",
-           "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-I", CSRC, "-o", exe, DRIVER]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = host_driver.build(DRIVER, tmp, extra_flags=["-ffp-contract=off"])
     lines = [f"E {name} {len(v)} {float(thr)!r} {numbers(v)}" for name, (v, thr) in cases.items()]
     path = tmp / "records.txt"
     path.write_text("\n".join(lines) + "\n")
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe, str(path)], capture_output=True, text=True, env=env, timeout=60)
-    assert r.returncode == 0 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
     got = {}
-    for line in r.stdout.splitlines():
+    for line in host_driver.run(exe, [path], timeout=60).splitlines():
         f = line.split()
         got[f[1]] = np.array([float(v) for v in f[2:]])
     assert len(got) == len(lines)

@@ -4,14 +4,14 @@ the system compiler under AddressSanitizer and UBSan, run as a program over the 
 reference's own GerdHydrograph.build, tools/gen_pool_routing_golden.py) and held to the reference's release and stage and to the
 evaluation counts of scipy's brentq, level by level."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT
 
-CSRC = os.path.join(ROOT, "flow-sim_amd", "csrc")
+import host_driver
+
 DRIVER = os.path.join(ROOT, "tests", "forcing", "forcing_driver.cpp")
 # GERD's outlets as fs_batch_route_pool takes them (C, crest, ramp_top, 0): cases/gerd_roseires/gerd_discharge.py
 WEIRS = np.array([[196.4017, 624.9, 640.0, 0.0], [447.3594, 640.0, 640.0, 0.0], [654.6723, 642.0, 642.0, 0.0]])
@@ -30,11 +30,7 @@ def fx():
 @pytest.fixture(scope="module")
 def driver_output(tmp_path_factory, fx):
     tmp = tmp_path_factory.mktemp("forcing")
-    exe = str(tmp / "forcing_driver")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off", "-fsanitize=address,undefined",
-           "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-I", CSRC, "-o", exe, DRIVER]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = host_driver.build(DRIVER, tmp, extra_flags=["-ffp-contract=off"])
     tab = fx["inflow_table"]
     levels = fx["release"].shape[0]
     lines = [f"POOL {len(fx['curve_stage'])} {len(WEIRS)} {len(tab)} {levels} 3600.0 {BASE_FLOW!r} {VOL_SCALE!r} {Z_LO!r} {Z_HI!r} "
@@ -44,11 +40,8 @@ def driver_output(tmp_path_factory, fx):
     lines.append("CHECKS")
     path = tmp / "records.txt"
     path.write_text("\n".join(lines) + "\n")
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe, str(path)], capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
     got = {}
-    for line in r.stdout.splitlines():
+    for line in host_driver.run(exe, [path], timeout=120).splitlines():
         f = line.split()
         if f[0] == "K":
             got[("K", f[1])] = " ".join(f[2:])

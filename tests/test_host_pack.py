@@ -29,7 +29,7 @@ from conftest import GOLDEN
 from flowsim_amd import _abi as A
 from oracle import preissmann_oracle as O
 
-from host_pack_driver import CSRC, build_driver, line, run_driver
+from host_driver import CSRC, PACK_DRIVER, build, line, run
 import poly_edges as PE
 
 RECORD = os.path.join(GOLDEN, "host_pack", "record.json")
@@ -119,7 +119,7 @@ def run_poly(exe, tmp, name, sets, walk, cap):
         for i in range(4):
             f.write(np.stack([s[i] for s in sets]).astype(np.float64).tobytes())
         f.write(np.stack([s[4] for s in sets]).astype(np.int32).tobytes())
-    got = {"input": hashlib.sha256(open(fin, "rb").read()).hexdigest(), "status": run_driver(exe, ["poly", fin, fout]).strip()}
+    got = {"input": hashlib.sha256(open(fin, "rb").read()).hexdigest(), "status": run(exe, ["poly", fin, fout], timeout=600).strip()}
     if got["status"].startswith("ok"):
         out = np.fromfile(fout, dtype=np.float64)
         stride = ((P + 16) & ~15) + 32 * P
@@ -136,7 +136,7 @@ def run_table(exe, tmp, name, tab):
     fin, fout = (os.path.join(str(tmp), name + e) for e in (".tin", ".tout"))
     with open(fin, "wb") as f:
         f.write(np.array([tab.shape[1]], dtype=np.int64).tobytes() + np.ascontiguousarray(tab).tobytes())
-    run_driver(exe, ["table", fin, fout])
+    run(exe, ["table", fin, fout], timeout=600)
     out = np.fromfile(fout, dtype=np.float64)
     assert out.size == 21 * tab.shape[1]
     return {"input": sha(tab), "ext": sha(out)}
@@ -202,9 +202,36 @@ def run_checks(exe, tmp):
     fin = os.path.join(str(tmp), "checks.txt")
     with open(fin, "w") as f:
         f.write("\n".join(lines) + "\n")
-    out = run_driver(exe, ["checks", fin]).splitlines()
+    out = run(exe, ["checks", fin], timeout=600).splitlines()
     assert len(out) == len(lines)
     return {"input": hashlib.sha256("\n".join(lines).encode()).hexdigest(), "lines": out}
+
+
+# fs::poly_tables_walk: (n_sets, N, max_pts, force_walk, max_bytes) -> "walk MiB".  Sixteen stations take (32 + 32 * 16) * 8 = 4 352
+# bytes of tables per node, two channels of 24 nodes 208 896 bytes; the comparison with the bound is a strict >.
+WALK = {
+    (2, 24, 16, 0, 208897): "0 0",                # the tables one byte below the bound
+    (2, 24, 16, 0, 208896): "0 0",                # at it: tables still
+    (2, 24, 16, 0, 208895): "1 0",                # one byte above: the edge walk
+    (1, 1, 2, 1, DEFAULT_CAP): "1 0",             # FS_POLY_WALK with 640 bytes of tables
+    (1, 1, 2, 0, DEFAULT_CAP): "0 0",
+    # around the default bound of 8 GiB (no table has an odd byte count: the nearest are 2^33 - 512 and 2^33 + 3 840 bytes), in whole MiB
+    (1, 1973790, 16, 0, DEFAULT_CAP): "0 8191",
+    (1, 1973791, 16, 0, DEFAULT_CAP): "1 8192",
+    (1973791, 1, 16, 0, DEFAULT_CAP + 3840): "0 8192",
+    (1, 1973791, 16, 0, DEFAULT_CAP + 3839): "1 8192",
+}
+
+
+def test_tables_or_the_edge_walk(tmp_path):
+    """the one decision both irregular setters of fs_abi.hip and plan_irregular take; the expected answers are written out above"""
+    if shutil.which("g++") is None:
+        pytest.skip("no system C++ compiler")
+    fin = os.path.join(str(tmp_path), "walk.txt")
+    with open(fin, "w") as f:
+        f.write("".join(line("walk", *case) + "\n" for case in WALK))
+    out = run(build(PACK_DRIVER, tmp_path), ["checks", fin], timeout=600).splitlines()
+    assert out == list(WALK.values()), [(c, g, w) for (c, w), g in zip(WALK.items(), out) if g != w]
 
 
 def encode(lines):
@@ -230,7 +257,7 @@ def measured(tmp_path_factory):
     if shutil.which("g++") is None:
         pytest.skip("no system C++ compiler")
     tmp = tmp_path_factory.mktemp("host_pack")
-    return measure(build_driver(tmp, [CSRC]), tmp)
+    return measure(build(PACK_DRIVER, tmp), tmp)
 
 
 def test_the_inputs_are_the_recorded_ones(measured, record):
@@ -307,7 +334,7 @@ def test_the_record_catches_a_mutation(record, tmp_path, name):
     assert src.count(old) == 1, name
     with open(tmp_path / "fs_host_pack.hpp", "w") as f:
         f.write(src.replace(old, new))
-    exe = build_driver(tmp_path, [tmp_path, CSRC])          # the copy first: the driver's #include "fs_host_pack.hpp" finds it
+    exe = build(PACK_DRIVER, tmp_path, [tmp_path, CSRC])          # the copy first: the driver's #include "fs_host_pack.hpp" finds it
     if name == "zero_padding":
         moved = [n for n, c in poly_cases().items() if not n.startswith("bad/")
                  and any(run_poly(exe, tmp_path, n, *c).get(k) != record["poly"][n].get(k) for k in ("xt", "zt"))]

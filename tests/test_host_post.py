@@ -4,13 +4,12 @@ tests/host_post/host_post_driver.cpp is built here with the system compiler unde
 The texts and the arithmetic it is held to are written out below as the entry points of fs_abi.hip stated them before the header
 existed."""
 import os
-import subprocess
 
 import pytest
 
 from conftest import ROOT
 
-CSRC = os.path.join(ROOT, "flow-sim_amd", "csrc")
+import host_driver
 DRIVER = os.path.join(ROOT, "tests", "host_post", "host_post_driver.cpp")
 INT32_MAX = 2 ** 31 - 1
 MAXQ, NSTAT, NCROSS, CROSSING, NQUANT = 16, 4, 3, 64, 6
@@ -105,11 +104,7 @@ LOOKUP_SHAPES = [(n_q, B) for n_q in (1, 5) for B in (1, 3)]
 @pytest.fixture(scope="module")
 def answers(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("host_post")
-    exe = str(tmp / "host_post_driver")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-           "-fno-omit-frame-pointer", "-I", CSRC, "-o", exe, DRIVER]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = host_driver.build(DRIVER, tmp)
     requests = ["consts"] + list(RANGE) + list(QUANT) + list(LOOKUP_ARGS) + [f"qindex {q}" for q in QINDEX]
     requests += [f"rows {mask} {c}" for mask in range(1, 64) for c in (0, 1)]
     requests += [f"rowof {m} {c} {q} {s}" for m, c, q, s, _ in row_queries()]
@@ -117,10 +112,7 @@ def answers(tmp_path_factory):
     requests += [f"lookup {n_q} {B}" for n_q, B in LOOKUP_SHAPES]
     path = tmp / "requests.txt"
     path.write_text("\n".join(requests) + "\n")
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe, str(path)], capture_output=True, text=True, env=env, timeout=60)
-    assert r.returncode == 0 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
-    lines = r.stdout.split("\n")[:-1]
+    lines = host_driver.run(exe, [path], timeout=60).split("\n")[:-1]
     assert len(lines) == len(requests)
     return dict(zip(requests, lines))
 

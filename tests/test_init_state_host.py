@@ -9,7 +9,6 @@ gen_init_state_golden.py) pin the host mirror here and the device march in tests
 import json
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -19,7 +18,8 @@ from conftest import GOLDEN, ROOT
 from oracle import preissmann_oracle as O
 from oracle.gen_random_sweep import build_from_recipe
 
-CSRC = os.path.join(ROOT, "flow-sim_amd", "csrc")
+import host_driver
+
 DRIVER = os.path.join(ROOT, "tests", "init_state", "brent_driver.cpp")
 
 sq = math.sqrt
@@ -36,16 +36,8 @@ FUNCTIONS = {
 
 
 def test_brent_root_is_scipys_brentq(tmp_path):
-    exe = str(tmp_path / "brent_driver")
-    # -ffp-contract=off: the functions must round as Python rounds them
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off", "-fsanitize=address,undefined",
-           "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-I", CSRC, "-o", exe, DRIVER]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=60)
-    assert r.returncode == 0 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
-    got = {f[0]: (float(f[1]), int(f[2]), int(f[3])) for f in (line.split() for line in r.stdout.splitlines())}
+    exe = host_driver.build(DRIVER, tmp_path, extra_flags=["-ffp-contract=off"])      # the functions must round as Python rounds them
+    got = {f[0]: (float(f[1]), int(f[2]), int(f[3])) for f in (line.split() for line in host_driver.run(exe, [], timeout=60).splitlines())}
     assert sorted(got) == sorted(FUNCTIONS)
     for name, (f, a, b) in FUNCTIONS.items():
         root, evals, bracketed = got[name]

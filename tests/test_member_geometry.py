@@ -7,7 +7,6 @@ definition itself against a literal double loop, what the binding hands to the l
 the oracle (tests/member_cases.py)."""
 import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,14 +14,12 @@ import pytest
 from conftest import ROOT
 from flowsim_amd import _abi as A
 from flowsim_amd import _pack
-from oracle import preissmann_oracle as O
 
+import host_driver
 import member_cases as MC
 import poly_edges as PE
 
-CSRC = os.path.join(ROOT, "flow-sim_amd", "csrc")
 DRIVER = os.path.join(ROOT, "tests", "member_geo", "member_geo_driver.cpp")
-ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
 NSUB, ZLO = 22, 23
 
 
@@ -34,18 +31,11 @@ def kp(P):
 def driver(tmp_path_factory):
     if shutil.which("g++") is None:
         pytest.skip("no system C++ compiler")
-    exe = str(tmp_path_factory.mktemp("member_geo") / "member_geo_driver")
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-I", CSRC, "-o", exe, DRIVER],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
+    return host_driver.build(DRIVER, tmp_path_factory.mktemp("member_geo"))
 
 
 def run(exe, *args):
-    r = subprocess.run([exe, *args], capture_output=True, text=True, env=ENV, timeout=600)
-    assert r.returncode == 0 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
-    return r.stdout
+    return host_driver.run(exe, args, timeout=600)
 
 
 def hexes(values):

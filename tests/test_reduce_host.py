@@ -5,7 +5,6 @@ example.npz, gerd.npz, gerd_full.npz) and held to numpy and to the reference's l
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,7 +13,8 @@ from conftest import GOLDEN, ROOT
 from flowsim_amd import _abi as A
 from flowsim_amd.ensemble import summary_text
 
-CSRC = os.path.join(ROOT, "flow-sim_amd", "csrc")
+import host_driver
+
 DRIVER = os.path.join(ROOT, "tests", "reduce", "reduce_driver.cpp")
 EPS = 2.0 ** -52
 SUMMARY_CASES = ("akbari", "example", "gerd_full")
@@ -45,11 +45,7 @@ def numbers(a):
 @pytest.fixture(scope="module")
 def driver_output(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("reduce")
-    exe = str(tmp / "reduce_driver")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off", "-fsanitize=address,undefined",
-           "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-I", CSRC, "-o", exe, DRIVER]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = host_driver.build(DRIVER, tmp, extra_flags=["-ffp-contract=off"])
     lines = []
     for name in SUMMARY_CASES:
         cols = columns(name)
@@ -60,11 +56,8 @@ def driver_output(tmp_path_factory):
         lines.append(f"L {name} {len(xp)} {len(QUERIES)} {numbers(xp)} {numbers(fp)} {numbers(QUERIES)} {numbers(TARGET)}")
     path = tmp / "records.txt"
     path.write_text("\n".join(lines) + "\n")
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe, str(path)], capture_output=True, text=True, env=env, timeout=60)
-    assert r.returncode == 0 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
     got = {}
-    for line in r.stdout.splitlines():
+    for line in host_driver.run(exe, [path], timeout=60).splitlines():
         f = line.split()
         got[(f[0], f[1])] = np.array([float(v) for v in f[2:]])
     assert len(got) == len(lines)

@@ -10,7 +10,6 @@ polyline and of the strip's sub-polyline, the number of wetted runs against subc
 constants, the +inf padding, and un-packing the device layout gives back each node's block."""
 import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -19,9 +18,9 @@ from conftest import GOLDEN, ROOT
 from oracle import irregular_oracle as IO
 from oracle import preissmann_oracle as O
 
+import host_driver
 import poly_edges as PE
 
-CSRC = os.path.join(ROOT, "flow-sim_amd", "csrc")
 DRIVER = os.path.join(ROOT, "tests", "stage_table", "stage_table_driver.cpp")
 BLOCK, NSUB, ZLO, ZHI, NL, STRIP = 32, 22, 23, 24, 25, 7
 REL = 1e-12
@@ -35,12 +34,7 @@ def kp(P):
 def driver(tmp_path_factory):
     if shutil.which("g++") is None:
         pytest.skip("no system C++ compiler")
-    exe = str(tmp_path_factory.mktemp("stage_table") / "stage_table_driver")
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-I", CSRC, "-o", exe, DRIVER],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
+    return host_driver.build(DRIVER, tmp_path_factory.mktemp("stage_table"))
 
 
 def build_tables(exe, geo, tmp):
@@ -57,9 +51,7 @@ def build_tables(exe, geo, tmp):
     fin, fout = os.path.join(tmp, "in.txt"), os.path.join(tmp, "out.bin")
     with open(fin, "w") as f:
         f.write("\n".join(lines) + "\n")
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
+    host_driver.run(exe, [fin, fout], timeout=300)
     stride = kp(P) + P * BLOCK
     out = np.fromfile(fout, dtype=np.float64)
     assert out.size == 2 * N * stride
