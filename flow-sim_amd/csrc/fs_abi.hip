@@ -26,6 +26,7 @@
 #include "fs_entries.hpp"
 #include "fs_envelope.hpp"
 #include "fs_forcing.hpp"
+#include "fs_gauge.hpp"
 #include "fs_host_pack.hpp"
 #include "fs_host_post.hpp"
 #include "fs_init_state.hpp"
@@ -48,7 +49,7 @@ struct TraceRange {
 FS_ACTIVE_LIST(FS_DECLARE)
 #else
 // an experiment build is this translation unit alone, with a few step kernels: it has no initial-condition kernels (fs_part_init.hip)
-// no post-processing kernels (fs_part_reduce.hip, fs_part_envelope.hip, fs_part_balance.hip), no forcing kernels (fs_part_forcing.hip) and no geometry kernels
+// no post-processing kernels (fs_part_reduce.hip, fs_part_envelope.hip, fs_part_balance.hip, fs_part_gauges.hip), no forcing kernels (fs_part_forcing.hip) and no geometry kernels
 // (fs_part_geometry.hip), and fs_batch_init_state, fs_batch_summarize, fs_batch_set_bc_sampled ... say so
 namespace fs {
 bool launch_envelope(const EnvelopeArgs<double> &, int, hipStream_t) { return false; }
@@ -60,6 +61,10 @@ bool launch_reach_integrals(const IntegralArgs<float> &, hipStream_t) { return f
 bool launch_balance(const ReduceArgs<double> &, const BalanceArgs &, hipStream_t) { return false; }
 bool launch_balance(const ReduceArgs<float> &, const BalanceArgs &, hipStream_t) { return false; }
 bool launch_clear_integrals(double *, size_t, int32_t *, size_t, hipStream_t) { return false; }
+bool launch_gauge_gather(const GaugeArgs<double> &, bool, hipStream_t) { return false; }
+bool launch_gauge_gather(const GaugeArgs<float> &, bool, hipStream_t) { return false; }
+bool launch_gauge_score(const ReduceArgs<double> &, const ScoreArgs &, hipStream_t) { return false; }
+bool launch_gauge_members(const int32_t *, const int32_t *, const int32_t *, const double *, int, int, int, int, int, int32_t *, hipStream_t) { return false; }
 bool launch_member_sections(const MemberGeoArgs &, hipStream_t) { return false; }
 bool launch_member_tables(const MemberGeoArgs &, hipStream_t) { return false; }
 bool launch_sample_target(const SampleArgs<double> &, hipStream_t) { return false; }
@@ -269,6 +274,13 @@ struct fs_batch : Timeline {
   fs::DeviceBuffer integ_thr;           // the threshold fs_batch_reach_integrals was handed, in the batch's type: [N] or [B][N]
   fs::DeviceBuffer bal_scheme;          // double [3][B]: theta, dt, dx of each reach as the caller gave them in fp64 (rs_host, else the batch's)
   bool bal_scheme_stale = true;         // the scheme changed since bal_scheme was uploaded
+  fs::DeviceBuffer gauge;               // double [n_gauges][max_levels][FS_GAUGE_NROWS][B]: the gauge rows, NaN where never evaluated (fs_batch_set_gauges)
+  fs::DeviceBuffer gauge_mark;          // int32 [max_levels][B]: bit g set where gauge g's row holds values
+  fs::DeviceBuffer gauge_node, gauge_weight;      // int32 / double [n_gauges], or [B][n_gauges] with gauge_per_reach
+  fs::DeviceBuffer gauge_members;       // int32 [B]: fs_batch_gauge_bands' status of each member at the gauge it was asked for
+  int n_gauges = 0;
+  bool gauge_per_reach = false;
+  std::vector<char> gauge_levels;       // [max_levels]: 1 where fs_batch_gauges has evaluated the level since the last reset
   int env_quantities = 0;               // FS_ENV_* mask of the envelope the handle holds (0: none)
   bool env_crossings = false;           // ... and whether it has crossing rows
   fs::DeviceBuffer frc_in[2][6];        // double / int32: what fs_batch_set_bc_sampled was handed per side (times, values, table_of, scale, offset, shift)
@@ -655,6 +667,11 @@ int begin_at_level0(fs_batch *b) {
   if (b->integ) {      // no row holds integrals of the new run
     fs::launch_clear_integrals(b->integ.get<double>(), L * FS_INT_NROWS * B, b->integ_mark.get<int32_t>(), L * B, b->stream);
     HIP_TRY(hipGetLastError());
+  }
+  if (b->gauge) {      // ... and no row holds a gauge's values
+    fs::launch_clear_integrals(b->gauge.get<double>(), (size_t)b->n_gauges * L * FS_GAUGE_NROWS * B, b->gauge_mark.get<int32_t>(), L * B, b->stream);
+    HIP_TRY(hipGetLastError());
+    std::fill(b->gauge_levels.begin(), b->gauge_levels.end(), 0);
   }
   b->level = 0; b->iterating = false; b->restart_level = 0;
   b->have_state = true;
@@ -1542,12 +1559,42 @@ int fs_batch_summarize(fs_batch *b, int32_t first, int32_t n, double *out) {
   return fetch(b, out, b->red_out[0].get(), bytes);
 }
 
-int fs_batch_lookup(fs_batch *b, int32_t first, int32_t n, int32_t x_row, int32_t y_row, const double *y_offset,
-                    const double *xq, int32_t n_q, const double *target, double *values, double *rmse, int32_t *info) {
-  if (!b) return fail("fs_batch_lookup: null handle");
-  if (!values && !rmse && !info) return fail("fs_batch_lookup: no output requested (values, rmse and info are all NULL)");
-  if (refuse(fs::check_lookup_args(x_row, y_row, xq, n_q, target, rmse != nullptr))) return -1;
-  if (check_reduce_range(b, "fs_batch_lookup", first, n)) return -1;
+// ---- the block a lookup or band call reads: the hydrograph block in the batch's type (fs_batch_lookup, fs_batch_bands), or a block of
+// its shape in doubles - the integral block, one gauge's part of the gauge block - on which the shipped kernels run through a
+// ReduceArgs<double> that points at it ----
+enum class RowSource { kHydrographs, kIntegrals, kGauge };
+
+static const double *source_block(const fs_batch *b, RowSource source, int32_t gauge) {
+  if (source == RowSource::kIntegrals) return b->integ.get<const double>();
+  return b->gauge.get<const double>() + (size_t)gauge * b->d.max_levels * FS_GAUGE_NROWS * b->d.n_reaches;
+}
+
+static fs::ReduceArgs<double> block_args(const fs_batch *b, const double *block, const int32_t *status, int32_t first, int32_t n) {
+  return fs::ReduceArgs<double>{block, status, b->iters.get<const int32_t>(), b->d.n_reaches, b->level, first, n};
+}
+
+// the handle has gauges and `gauge` is one of them
+static int check_gauge(const fs_batch *b, const char *entry, int32_t gauge) {
+  if (b->n_gauges == 0 || !b->gauge) return fail(std::string(entry) + ": this batch has no gauges (fs_batch_set_gauges comes first)");
+  if (gauge < 0 || gauge >= b->n_gauges)
+    return fail(std::string(entry) + ": gauge " + std::to_string(gauge) + " is not one of 0 .. " + std::to_string(b->n_gauges - 1));
+  return 0;
+}
+
+// fs_batch_lookup and fs_batch_gauge_lookup: lookup_kernel and lookup_finish_kernel over two rows of every level of the range
+static int lookup_rows(fs_batch *b, const char *entry, RowSource source, int32_t gauge, int32_t first, int32_t n, int32_t x_row, int32_t y_row,
+                       const double *y_offset, const double *xq, int32_t n_q, const double *target, double *values, double *rmse, int32_t *info) {
+  if (!b) return fail(std::string(entry) + ": null handle");
+  if (!values && !rmse && !info) return fail(std::string(entry) + ": no output requested (values, rmse and info are all NULL)");
+  const bool gauges = source == RowSource::kGauge;
+  if (gauges ? refuse(fs::check_lookup_args(x_row, y_row, xq, n_q, target, rmse != nullptr, entry, "FS_GAUGE_DEPTH .. FS_GAUGE_VELOCITY"))
+             : refuse(fs::check_lookup_args(x_row, y_row, xq, n_q, target, rmse != nullptr))) return -1;
+  if (gauges && check_gauge(b, entry, gauge)) return -1;
+  if (check_reduce_range(b, entry, first, n)) return -1;
+  if (gauges)      // np.interp over rows that hold NaN promises nothing
+    for (int32_t k = first; k < first + n; ++k)
+      if (!b->gauge_levels[(size_t)k])
+        return fail(std::string(entry) + ": level " + std::to_string(k) + " of the range was never evaluated (fs_batch_gauges comes first)");
   FS_ON_DEVICE(b);
   TraceRange range_("flowsim:reduce");
   const size_t B = b->d.n_reaches;
@@ -1563,12 +1610,24 @@ int fs_batch_lookup(fs_batch *b, int32_t first, int32_t n, int32_t x_row, int32_
   l.y_offset = y_offset ? b->red_in[0].get<const double>() : nullptr;
   l.xq = b->red_in[1].get<const double>(); l.target = rmse ? b->red_in[2].get<const double>() : nullptr;
   l.values = blk + lay.values; l.rmse = rmse ? blk + lay.rmse : nullptr; l.info = info ? (int32_t *)(blk + lay.info) : nullptr;
-  if (post_launch(b, "fs_batch_lookup", 0, [&](auto real) { return fs::launch_lookup(reduce_args<decltype(real)>(b, first, n), l, b->stream); }))
-    return -1;
+  if (post_launch(b, entry, 0, [&](auto real) {
+        if (!gauges) return fs::launch_lookup(reduce_args<decltype(real)>(b, first, n), l, b->stream);
+        return fs::launch_lookup(block_args(b, source_block(b, source, gauge), b->status.get<const int32_t>(), first, n), l, b->stream);
+      })) return -1;
   if (values && fetch(b, values, l.values, lay.n_values * sizeof(double))) return -1;
   if (rmse && fetch(b, rmse, l.rmse, B * sizeof(double))) return -1;
   if (info && fetch(b, info, l.info, B * sizeof(int32_t))) return -1;
   return 0;
+}
+
+int fs_batch_lookup(fs_batch *b, int32_t first, int32_t n, int32_t x_row, int32_t y_row, const double *y_offset,
+                    const double *xq, int32_t n_q, const double *target, double *values, double *rmse, int32_t *info) {
+  return lookup_rows(b, "fs_batch_lookup", RowSource::kHydrographs, -1, first, n, x_row, y_row, y_offset, xq, n_q, target, values, rmse, info);
+}
+
+int fs_batch_gauge_lookup(fs_batch *b, int32_t gauge, int32_t first, int32_t n, int32_t x_row, int32_t y_row, const double *y_offset,
+                          const double *xq, int32_t n_q, const double *target, double *values, double *rmse, int32_t *info) {
+  return lookup_rows(b, "fs_batch_gauge_lookup", RowSource::kGauge, gauge, first, n, x_row, y_row, y_offset, xq, n_q, target, values, rmse, info);
 }
 
 int fs_batch_envelope_device(fs_batch *b, int32_t first, int32_t n, int32_t quantities, const double *threshold,
@@ -1744,42 +1803,162 @@ int fs_batch_get_reach_integrals(fs_batch *b, int32_t first, int32_t n, double *
 
 void *fs_batch_reach_integrals_device_ptr(fs_batch *b) { return b ? b->integ.get() : nullptr; }
 
-// fs_batch_bands and fs_batch_integral_bands: bands_kernel over the four rows of every level of the range - of the hydrograph block, or
-// (integrals; the call is then timed) of the integral block, which has its shape: a ReduceArgs<double> that points at it
-static int band_rows(fs_batch *b, const char *entry, bool integrals, int32_t first, int32_t n, const double *q, int32_t n_q, double *moments,
-                     double *quantiles, int32_t *n_members) {
+// fs_batch_bands, fs_batch_integral_bands and fs_batch_gauge_bands: bands_kernel over the four rows of every level of the range - of the
+// hydrograph block, or (the call is then timed) of the integral block or of one gauge's block, which have its shape.  A gauge's bands
+// leave out, with the failed members, those that do not have the gauge: gauge_members_kernel writes the status bands_kernel reads.
+static int band_rows(fs_batch *b, const char *entry, RowSource source, int32_t gauge, int32_t first, int32_t n, const double *q, int32_t n_q,
+                     double *moments, double *quantiles, int32_t *n_members) {
   if (!b) return fail(std::string(entry) + ": null handle");
   if (!moments && !quantiles && !n_members) return fail(std::string(entry) + ": no output requested (moments, quantiles and n_members are all NULL)");
+  if (source == RowSource::kGauge && check_gauge(b, entry, gauge)) return -1;
   if (refuse(fs::check_quantile_levels(entry, q, n_q)) || check_reduce_range(b, entry, first, n)) return -1;
   FS_ON_DEVICE(b);
   TraceRange range_("flowsim:reduce");
-  if (integrals && ready_integrals(b, entry)) return -1;
+  if (source == RowSource::kIntegrals && ready_integrals(b, entry)) return -1;
+  if (source == RowSource::kGauge) HIP_TRY(b->gauge_members.ensure((size_t)b->d.n_reaches * sizeof(int32_t)));
   const bool want_q = quantiles && n_q > 0;
   HIP_TRY(hipStreamSynchronize(b->stream));
   if (want_q && upload_f64(b->red_in[1], q, (size_t)n_q)) return -1;
-  static_assert(FS_INT_NROWS == 4, "bands_kernel walks the four rows of a level of the hydrograph block");
+  static_assert(FS_INT_NROWS == 4 && FS_GAUGE_NROWS == 4, "bands_kernel walks the four rows of a level of the hydrograph block");
   const fs::BandLayout lay = fs::band_layout((size_t)n, 4, want_q ? (size_t)n_q : 0, false);
   HIP_TRY(b->red_out[2].reserve(lay.bytes));
   double *blk = b->red_out[2].get<double>();
   fs::BandArgs p;
   point_bands(p, lay, blk, b->red_in[1].get<const double>(), n_q, moments != nullptr, n_members != nullptr);
-  if (post_launch(b, entry, integrals ? 1 : 0, [&](auto real) {
-        if (!integrals) return fs::launch_bands(reduce_args<decltype(real)>(b, first, n), p, b->stream);
-        const fs::ReduceArgs<double> a{b->integ.get<const double>(), b->status.get<const int32_t>(), b->iters.get<const int32_t>(), b->d.n_reaches,
-                                       b->level, first, n};
-        return fs::launch_bands(a, p, b->stream);
+  const int launches = source == RowSource::kHydrographs ? 0 : source == RowSource::kIntegrals ? 1 : 2;
+  if (post_launch(b, entry, launches, [&](auto real) {
+        if (source == RowSource::kHydrographs) return fs::launch_bands(reduce_args<decltype(real)>(b, first, n), p, b->stream);
+        const int32_t *status = b->status.get<const int32_t>();
+        if (source == RowSource::kGauge) {
+          if (!fs::launch_gauge_members(status, b->reach_nodes.get<const int32_t>(), b->gauge_node.get<const int32_t>(),
+                                        b->gauge_weight.get<const double>(), b->n_gauges, gauge, b->gauge_per_reach ? 1 : 0, b->d.n_nodes,
+                                        b->d.n_reaches, b->gauge_members.get<int32_t>(), b->stream)) return false;
+          status = b->gauge_members.get<const int32_t>();
+        }
+        return fs::launch_bands(block_args(b, source_block(b, source, gauge), status, first, n), p, b->stream);
       })) return -1;
   return fetch_bands(b, lay, blk, moments, quantiles, nullptr, n_members);
 }
 
 int fs_batch_bands(fs_batch *b, int32_t first, int32_t n, const double *q, int32_t n_q, double *moments, double *quantiles,
                    int32_t *n_members) {
-  return band_rows(b, "fs_batch_bands", false, first, n, q, n_q, moments, quantiles, n_members);
+  return band_rows(b, "fs_batch_bands", RowSource::kHydrographs, -1, first, n, q, n_q, moments, quantiles, n_members);
 }
 
 int fs_batch_integral_bands(fs_batch *b, int32_t first, int32_t n, const double *q, int32_t n_q, double *moments, double *quantiles,
                             int32_t *n_members) {
-  return band_rows(b, "fs_batch_integral_bands", true, first, n, q, n_q, moments, quantiles, n_members);
+  return band_rows(b, "fs_batch_integral_bands", RowSource::kIntegrals, -1, first, n, q, n_q, moments, quantiles, n_members);
+}
+
+int fs_batch_gauge_bands(fs_batch *b, int32_t gauge, int32_t first, int32_t n, const double *q, int32_t n_q, double *moments,
+                         double *quantiles, int32_t *n_members) {
+  return band_rows(b, "fs_batch_gauge_bands", RowSource::kGauge, gauge, first, n, q, n_q, moments, quantiles, n_members);
+}
+
+// ---- interior gauges (fs_gauge.hpp) ----
+
+int fs_batch_set_gauges(fs_batch *b, int32_t n_gauges, const int32_t *node, const double *weight, int32_t per_reach) {
+  if (!b) return fail("fs_batch_set_gauges: null handle");
+  const size_t B = b->d.n_reaches, L = b->d.max_levels;
+  const size_t count = n_gauges > 0 ? (size_t)n_gauges * (per_reach ? B : 1) : 0;
+  if (refuse(fs::check_gauge_list("fs_batch_set_gauges", n_gauges, node, weight, count, b->d.n_nodes))) return -1;
+  FS_ON_DEVICE(b);
+  HIP_TRY(hipStreamSynchronize(b->stream));      // an earlier call's kernels are through with the positions and the block
+  b->n_gauges = 0; b->gauge_per_reach = false; b->gauge_levels.clear();
+  if (n_gauges == 0) {
+    for (fs::DeviceBuffer *p : {&b->gauge, &b->gauge_mark, &b->gauge_node, &b->gauge_weight, &b->gauge_members}) p->reset();
+    return 0;
+  }
+  const fs::GaugeLayout lay{(size_t)n_gauges, L, B};
+  struct Want { fs::DeviceBuffer *buf; size_t bytes; const char *what; };
+  const Want wants[] = {{&b->gauge, lay.block() * sizeof(double), "the gauge block [n_gauges][max_levels][4][B] of doubles"},
+                        {&b->gauge_mark, lay.marks() * sizeof(int32_t), "the gauge marks [max_levels][B] of int32"}};
+  for (const Want &w : wants) {
+    const hipError_t e = w.buf->ensure(w.bytes);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      b->gauge.reset(); b->gauge_mark.reset();
+      return fail(std::string("fs_batch_set_gauges: cannot allocate ") + w.what + ", " + std::to_string(w.bytes) + " bytes: " + hipGetErrorString(e));
+    }
+  }
+  HIP_TRY(b->gauge_node.ensure(count * sizeof(int32_t)));
+  HIP_TRY(b->gauge_weight.ensure(count * sizeof(double)));
+  HIP_TRY(hipMemcpy(b->gauge_node.get(), node, count * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b->gauge_weight.get(), weight, count * sizeof(double), hipMemcpyHostToDevice));
+  if (!fs::launch_clear_integrals(b->gauge.get<double>(), lay.block(), b->gauge_mark.get<int32_t>(), lay.marks(), b->stream)) {
+    b->gauge.reset(); b->gauge_mark.reset();
+    return fail(std::string("fs_batch_set_gauges") + kNoReduceKernels);
+  }
+  HIP_TRY(hipGetLastError());
+  b->n_gauges = n_gauges; b->gauge_per_reach = per_reach != 0;
+  b->gauge_levels.assign(L, 0);
+  return 0;
+}
+
+int fs_batch_gauges(fs_batch *b, int32_t first, int32_t n) {
+  if (!b) return fail("fs_batch_gauges: null handle");
+  if (check_gauge(b, "fs_batch_gauges", 0)) return -1;
+  if (!b->have_geo) return fail("fs_batch_gauges: the geometry must be set first");
+  const bool current = first == -1;
+  if (current) {
+    if (n != 1) return fail("fs_batch_gauges: first = -1 evaluates the current state, one row: n must be 1");
+    if (!b->have_state) return fail("fs_batch_gauges: no state yet");
+    if (b->iterating) return fail("fs_batch_gauges: a level opened with fs_batch_iterate must be closed first");
+  } else {
+    if (!b->hist_h) return fail("fs_batch_gauges: batch was created without FS_FLAG_HISTORY (first = -1 evaluates the current state)");
+    if (check_reduce_range(b, "fs_batch_gauges", first, n, "the history before it was not restored")) return -1;
+  }
+  FS_ON_DEVICE(b);
+  TraceRange range_("flowsim:gauges");
+  const size_t BN = (size_t)b->d.n_reaches * b->d.n_nodes;
+  const int32_t row0 = current ? b->level : first;
+  if (post_launch(b, "fs_batch_gauges", 1, [&](auto real) {      // fs_batch_last_step_ms() then reports this kernel
+        using R = decltype(real);
+        fs::GaugeArgs<R> a{b->d.n_reaches, b->d.n_nodes, b->d.section_mode, b->n_gauges,
+                           current ? b->hk.get<const R>() : b->hist_h.get<const R>() + (size_t)first * BN,
+                           current ? b->Qk.get<const R>() : b->hist_Q.get<const R>() + (size_t)first * BN, current ? (int64_t)0 : (int64_t)BN,
+                           section_tables<R>(b), b->reach_nodes.get<const int32_t>(), reduce_args<R>(b, row0, n),
+                           b->gauge_node.get<const int32_t>(), b->gauge_weight.get<const double>(), b->gauge.get<double>(),
+                           b->gauge_mark.get<int32_t>(), b->d.max_levels};
+        return fs::launch_gauge_gather(a, b->gauge_per_reach, b->stream);
+      })) return -1;
+  std::fill(b->gauge_levels.begin() + row0, b->gauge_levels.begin() + row0 + n, 1);
+  return 0;
+}
+
+int fs_batch_get_gauges(fs_batch *b, int32_t gauge, int32_t first, int32_t n, double *out) {
+  if (!b || !out) return fail("fs_batch_get_gauges: null argument");
+  if (check_gauge(b, "fs_batch_get_gauges", gauge) || check_levels(b, "fs_batch_get_gauges", first, n)) return -1;
+  FS_ON_DEVICE(b);
+  const size_t B = b->d.n_reaches;
+  return fetch(b, out, source_block(b, RowSource::kGauge, gauge) + (size_t)first * FS_GAUGE_NROWS * B, (size_t)n * FS_GAUGE_NROWS * B * sizeof(double));
+}
+
+void *fs_batch_gauges_device_ptr(fs_batch *b, int32_t gauge) {
+  if (!b || !b->gauge || gauge < 0 || gauge >= b->n_gauges) return nullptr;
+  return const_cast<double *>(source_block(b, RowSource::kGauge, gauge));
+}
+
+int fs_batch_gauge_score(fs_batch *b, int32_t gauge, int32_t signal, int32_t first, int32_t n, const double *observed,
+                         int32_t observed_per_reach, double *out) {
+  if (!b) return fail("fs_batch_gauge_score: null handle");
+  if (!observed || !out) return fail("fs_batch_gauge_score: null observations or output");
+  if (check_gauge(b, "fs_batch_gauge_score", gauge)) return -1;
+  if (signal < 0 || signal >= FS_GAUGE_NROWS)
+    return fail("fs_batch_gauge_score: signal " + std::to_string(signal) + " is not one of FS_GAUGE_DEPTH .. FS_GAUGE_VELOCITY (0 .. 3)");
+  if (check_reduce_range(b, "fs_batch_gauge_score", first, n)) return -1;
+  FS_ON_DEVICE(b);
+  TraceRange range_("flowsim:gauges");
+  const size_t B = b->d.n_reaches, bytes = (size_t)FS_GS_NROWS * B * sizeof(double);
+  HIP_TRY(hipStreamSynchronize(b->stream));      // an earlier call's kernels are through with the observations
+  if (upload_f64(b->red_in[0], observed, (size_t)n * (observed_per_reach ? B : 1))) return -1;
+  HIP_TRY(b->red_out[0].reserve(bytes));
+  const fs::ScoreArgs p{source_block(b, RowSource::kGauge, gauge), b->gauge_mark.get<const int32_t>(), gauge, signal, b->red_in[0].get<const double>(),
+                        observed_per_reach ? 1 : 0, b->red_out[0].get<double>()};
+  if (post_launch(b, "fs_batch_gauge_score", 1, [&](auto) {
+        return fs::launch_gauge_score(block_args(b, p.gauge, b->status.get<const int32_t>(), first, n), p, b->stream);
+      })) return -1;
+  return fetch(b, out, p.out, bytes);
 }
 
 void *fs_batch_hydrograph_device_ptr(fs_batch *b) { return b ? b->hydro.get() : nullptr; }

@@ -1,5 +1,5 @@
 // fs_host_post.hpp - what the post-processing entry points of the ABI (fs_abi.hip: summarize, lookup, bands, envelope, profile bands,
-// reach integrals, water balance, integral bands) decide before anything is launched: the checks of their ranges and quantile levels,
+// reach integrals, water balance, integral bands, gauge bands and lookups) decide before anything is launched: the checks of their ranges and quantile levels,
 // the rows of an envelope, and where the outputs of a call lie in the handle's result block.  Plain C++17 with no HIP header:
 // tests/host_post/ builds it with the system compiler under AddressSanitizer / UBSan.  A check returns the error text, or nothing.
 #pragma once
@@ -34,12 +34,14 @@ inline std::string check_quantile_levels(const char *entry, const double *q, int
   return {};
 }
 
-// what fs_batch_lookup is handed besides its range
-inline std::string check_lookup_args(int32_t x_row, int32_t y_row, const double *xq, int32_t n_q, const double *target, bool want_rmse) {
-  if (x_row < 0 || x_row > 3 || y_row < 0 || y_row > 3) return "fs_batch_lookup: x_row and y_row are 0..3 (h[0], Q[0], h[N-1], Q[N-1])";
-  if (n_q < 1 || n_q > 65535) return "fs_batch_lookup: n_q must be 1 .. 65535";
-  if (!xq) return "fs_batch_lookup: null query abscissae";
-  if (want_rmse && !target) return "fs_batch_lookup: rmse needs a target";
+// what fs_batch_lookup is handed besides its range (entry, rows: fs_batch_gauge_lookup's name and what its rows 0..3 are)
+inline std::string check_lookup_args(int32_t x_row, int32_t y_row, const double *xq, int32_t n_q, const double *target, bool want_rmse,
+                                     const char *entry = "fs_batch_lookup", const char *rows = "h[0], Q[0], h[N-1], Q[N-1]") {
+  const std::string e(entry);
+  if (x_row < 0 || x_row > 3 || y_row < 0 || y_row > 3) return e + ": x_row and y_row are 0..3 (" + rows + ")";
+  if (n_q < 1 || n_q > 65535) return e + ": n_q must be 1 .. 65535";
+  if (!xq) return e + ": null query abscissae";
+  if (want_rmse && !target) return e + ": rmse needs a target";
   return {};
 }
 

@@ -47,6 +47,11 @@ ENV_CROSS_ROWS = ("first", "last", "count")
 # fs_batch_reach_integrals: the rows of a level of the integral block (FS_INT_VOLUME ..); fs_batch_water_balance: its totals (FS_BAL_SPANS ..)
 INT_ROWS = ("volume", "surface", "length_over", "balance")
 BAL_ROWS = ("spans", "first_level", "last_level", "storage_change", "net_inflow", "inflow", "residual", "worst", "worst_level", "relative")
+# fs_batch_gauges: the rows of a level of a gauge's block (FS_GAUGE_DEPTH ..), x_row / y_row of fs_batch_gauge_lookup and the signals of
+# fs_batch_gauge_score; fs_batch_gauge_score: its rows (FS_GS_COUNT ..)
+GAUGE_ROWS = ("depth", "flow", "stage", "velocity")
+GAUGE_MAX = 32
+GS_ROWS = ("count", "bias", "rmse", "nse", "peak_sim", "peak_sim_level", "peak_error", "peak_lag")
 ABI_VERSION = 3
 
 
@@ -121,6 +126,13 @@ SIGNATURES = {
     "fs_batch_get_reach_integrals": (C.c_int, [_P, C.c_int32, C.c_int32, _D]),
     "fs_batch_reach_integrals_device_ptr": (_P, [_P]),
     "fs_batch_integral_bands": (C.c_int, [_P, C.c_int32, C.c_int32, _D, C.c_int32, _D, _D, _I]),
+    "fs_batch_set_gauges": (C.c_int, [_P, C.c_int32, _I, _D, C.c_int32]),
+    "fs_batch_gauges": (C.c_int, [_P, C.c_int32, C.c_int32]),
+    "fs_batch_get_gauges": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _D]),
+    "fs_batch_gauges_device_ptr": (_P, [_P, C.c_int32]),
+    "fs_batch_gauge_bands": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _D, C.c_int32, _D, _D, _I]),
+    "fs_batch_gauge_lookup": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D, _D, C.c_int32, _D, _D, _D, _I]),
+    "fs_batch_gauge_score": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D, C.c_int32, _D]),
     "fs_batch_hydrograph_device_ptr": (_P, [_P]),
     "fs_batch_stream": (_P, [_P]),
     "fs_batch_last_step_ms": (C.c_double, [_P]),

@@ -378,3 +378,86 @@ def balance_chunks(n_steps, every):
     if n_steps < 0 or every < 1:
         raise ValueError("balance_chunks: n_steps >= 0 and every >= 1 required")
     return [every] * (n_steps // every) + ([n_steps % every] if n_steps % every else [])
+
+
+# -- interior gauges -------------------------------------------------------------------------------
+def gauge_positions(chainage, dx, nodes):
+    """(node int32, weight float64) of fs_batch_set_gauges for gauges at the distances `chainage` from the upstream end: shared [G]
+    when chainage is [G] and dx, nodes are scalars; per reach [B, G] when chainage is [B, G] or dx or nodes are [B] (chainage [G] is
+    then every reach's).  x / dx within 4 eps max(1, x / dx) of an integer IS that node (weight 0.0); the end of the reach is
+    (nodes - 1, 0.0); x outside [0, (nodes - 1) dx] raises."""
+    x = np.asarray(chainage, dtype=np.float64)
+    dx = np.asarray(dx, dtype=np.float64)
+    nodes = np.asarray(nodes)
+    if x.ndim not in (1, 2) or dx.ndim > 1 or nodes.ndim > 1:
+        raise ValueError("gauge_positions: chainage is [G] or [B, G], dx and nodes are scalars or [B]")
+    if nodes.dtype.kind not in "iu":
+        raise ValueError("gauge_positions: nodes must be integers")
+    if np.any(nodes < 2) or np.any(~(dx > 0.0)):
+        raise ValueError("gauge_positions: nodes >= 2 and dx > 0 required")
+    sizes = {a.shape[0] for a in (dx, nodes) if a.ndim == 1} | ({x.shape[0]} if x.ndim == 2 else set())
+    if len(sizes) > 1:
+        raise ValueError(f"gauge_positions: chainage, dx and nodes disagree on the number of reaches: {sorted(sizes)}")
+    if sizes:
+        B = sizes.pop()
+        x = np.broadcast_to(x, (B, x.shape[-1]))
+        dx, nodes = np.broadcast_to(dx, (B,))[:, None], np.broadcast_to(nodes, (B,))[:, None]
+    if np.any(~np.isfinite(x)):
+        raise ValueError("gauge_positions: chainage must be finite")
+    last = (nodes - 1).astype(np.float64)
+    outside = (x < 0.0) | (x > last * dx)
+    if np.any(outside):
+        raise ValueError(f"gauge_positions: chainage {x[outside].ravel()[0]!r} is outside the reach, [0, (nodes - 1) dx]")
+    s = x / dx
+    near = np.rint(s)
+    s = np.where(np.abs(s - near) <= 4.0 * np.finfo(np.float64).eps * np.maximum(1.0, np.abs(s)), near, s)
+    s = np.minimum(np.abs(s), last)              # (x = (nodes - 1) dx whose quotient rounds up a little is the last node; -0.0 is node 0)
+    node = np.floor(s)
+    weight = s - node
+    return np.ascontiguousarray(node, dtype=np.int32), np.ascontiguousarray(weight + 0.0, dtype=np.float64)
+
+
+def gauge_arrays(node, weight, B):
+    """(node int32, weight float64, per_reach) of fs_batch_set_gauges: [G] shared, or [B, G]"""
+    node, weight = np.asarray(node, dtype=np.int32), np.asarray(weight, dtype=np.float64)
+    if node.shape != weight.shape or node.ndim not in (1, 2) or (node.ndim == 2 and node.shape[0] != B):
+        raise ValueError(f"gauges: node and weight are both [G] or both [B, G] = [{B}, G], not {list(node.shape)} and {list(weight.shape)}")
+    return np.ascontiguousarray(node), np.ascontiguousarray(weight), int(node.ndim == 2)
+
+
+def gauge_row(name):
+    """FS_GAUGE_* of a name of _abi.GAUGE_ROWS (an integer 0 .. 3 passes)"""
+    if isinstance(name, str):
+        if name not in A.GAUGE_ROWS:
+            raise ValueError(f"unknown gauge signal {name!r}: one of {', '.join(A.GAUGE_ROWS)}")
+        return A.GAUGE_ROWS.index(name)
+    return int(name)
+
+
+def gauge_observed(observed, n, B):
+    """(float64 [n] or [n, B], per_reach) of fs_batch_gauge_score; NaN entries stay: they mean "no observation" """
+    o = np.ascontiguousarray(observed, dtype=np.float64)
+    if o.shape not in ((n,), (n, B)):
+        raise ValueError(f"observed must be [n] = [{n}] or [n, B] = [{n}, {B}], not {list(o.shape)}")
+    return o, int(o.ndim == 2)
+
+
+def gauge_options(gauges):
+    """(chainage, every, quantiles, observed, signal, rows) of the runners' gauges= keyword: dict(chainage=, every=1,
+    quantiles=(0.05, 0.5, 0.95), observed=None, signal="stage", rows=True)"""
+    unknown = set(gauges) - {"chainage", "every", "quantiles", "observed", "signal", "rows"}
+    if unknown:
+        raise ValueError(f"gauges: unknown keys {sorted(unknown)}")
+    if "chainage" not in gauges:
+        raise ValueError("gauges: chainage is required")
+    chainage = np.asarray(gauges["chainage"], dtype=np.float64)
+    if chainage.ndim != 1 or not 1 <= len(chainage) <= A.GAUGE_MAX:
+        raise ValueError(f"gauges: chainage is [G] with 1 <= G <= {A.GAUGE_MAX}")
+    every = gauges.get("every", 1)
+    if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or every < 1:
+        raise ValueError(f"gauges: every must be an integer >= 1, not {every!r}")
+    signal = gauges.get("signal", "stage")
+    gauge_row(signal)
+    observed = gauges.get("observed")
+    return (chainage, int(every), quantile_levels(gauges.get("quantiles", (0.05, 0.5, 0.95))),
+            None if observed is None else np.asarray(observed, dtype=np.float64), signal, bool(gauges.get("rows", True)))

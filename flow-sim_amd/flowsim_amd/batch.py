@@ -63,6 +63,7 @@ class PreissmannBatch:
         self.history = history
         self._max_pts = 0           # stations per polyline row of the geometry on the device (stage_table)
         self._envelope = ((), False)      # what the envelope on the handle holds: quantity names, crossing rows
+        self.gauge_positions = None       # (node, weight) of set_gauges
 
     # -- lifetime -------------------------------------------------------------------------
     def close(self):
@@ -495,6 +496,85 @@ class PreissmannBatch:
     def reach_integrals_device_ptr(self):
         """device pointer to the integral block [max_levels, 4, B] float64 (None before the first evaluation)"""
         return self._lib.fs_batch_reach_integrals_device_ptr(self._h)
+
+    # -- interior gauges: station series, their bands across the members and fit scores ---------------------
+    def set_gauges(self, chainage=None, node=None, weight=None, dx=None, nodes=None):
+        """Gauges inside the reach, each between node and node + 1 at weight in [0, 1) of the way: node, weight [G] shared by the
+        batch or [B, G] per reach; or chainage [G] / [B, G], distances from the upstream end, with dx (scalar or [B]: the node
+        spacing) and nodes (scalar or [B]: the reaches' own node counts; None: N) through _pack.gauge_positions.  Allocates the batch's gauge block [G, L, 4, B] on the device, every row NaN; no gauges
+        (empty arrays) frees it.  Returns (node, weight) as set."""
+        if chainage is not None:
+            if node is not None or weight is not None or dx is None:
+                raise ValueError("set_gauges: chainage comes with dx, and without node and weight")
+            node, weight = P.gauge_positions(chainage, dx, self.N if nodes is None else nodes)
+        elif node is None or weight is None:
+            raise ValueError("set_gauges: give chainage and dx, or node and weight")
+        node, weight, per_reach = P.gauge_arrays(node, weight, self.B)
+        A.check(self._lib.fs_batch_set_gauges(self._h, int(node.shape[-1]), _iptr(node), _dptr(weight), per_reach), "set_gauges")
+        self.gauge_positions = (node, weight)
+        return node, weight
+
+    def gauges(self, first=0, n=None, current=False):
+        """Fills the rows [first, first + n) of every gauge from the stored history (needs history=True): per (level, member) depth,
+        flow, stage and velocity at the gauge, evaluated at its two nodes as derive() evaluates them and interpolated in float64.
+        current=True fills the row of the current level from the current state instead - no history needed, no wait for the device:
+        a batch without history is marked between two step(..., sync=False) calls.  Returns None; gauge_rows() downloads."""
+        first, n = P.integral_range(first, n, self.level, current)
+        A.check(self._lib.fs_batch_gauges(self._h, first, n), "gauges")
+
+    def gauge_rows(self, g, first=0, n=None):
+        """the rows [first, first + n) of gauge g as they stand: [n, 4, B] in the order of _abi.GAUGE_ROWS; NaN where never evaluated,
+        from a failed member's failing level on, and for a member whose reach does not have the gauge"""
+        n = self._span(first, n)
+        out = np.empty((n, len(A.GAUGE_ROWS), self.B))
+        A.check(self._lib.fs_batch_get_gauges(self._h, int(g), int(first), int(n), _dptr(out)), "get_gauges")
+        return out
+
+    def gauge_bands(self, g, quantiles=(0.05, 0.5, 0.95), first=0, n=None):
+        """bands() on gauge g's block: across the members, per level and row of _abi.GAUGE_ROWS, dict(min, max, mean, std [n, 4],
+        quantiles [n, 4, n_q], n_members [n]).  Failed members and members without the gauge are left out; a level that a remaining
+        member has not evaluated is NaN."""
+        n = self._span(first, n)
+        q = P.quantile_levels(quantiles)
+        mom = np.empty((n, 4, 4))
+        qu = np.empty((n, 4, len(q)))
+        cnt = np.empty(n, dtype=np.int32)
+        A.check(self._lib.fs_batch_gauge_bands(self._h, int(g), int(first), int(n), _opt(q if len(q) else None), len(q), _dptr(mom),
+                                               _opt(qu if len(q) else None), _iptr(cnt)), "gauge_bands")
+        return dict(min=mom[:, :, 0], max=mom[:, :, 1], mean=mom[:, :, 2], std=mom[:, :, 3], quantiles=qu, n_members=cnt)
+
+    def gauge_lookup(self, g, x_row, y_row, xq, y_offset=None, target=None, first=0, n=None):
+        """lookup() on gauge g's block: np.interp(xq, x_series, y_series + y_offset) for every member, the rows being names or
+        indices of _abi.GAUGE_ROWS (a rating at the gauge: x_row="flow", y_row="stage").  Every level of the range must have been
+        evaluated.  dict(values [n_q, B], rmse [B] or None, monotone [B])."""
+        n = self._span(first, n)
+        xq = np.ascontiguousarray(xq, dtype=np.float64).reshape(-1)
+        off = P.opt_per_reach(y_offset, self.B)
+        tgt = None if target is None else np.ascontiguousarray(target, dtype=np.float64).reshape(-1)
+        if tgt is not None and tgt.shape != xq.shape:
+            raise ValueError("gauge_lookup: target must have the shape of xq")
+        values = np.empty((len(xq), self.B))
+        rmse = None if tgt is None else np.empty(self.B)
+        info = np.empty(self.B, dtype=np.int32)
+        A.check(self._lib.fs_batch_gauge_lookup(self._h, int(g), int(first), int(n), P.gauge_row(x_row), P.gauge_row(y_row), _opt(off),
+                                                _dptr(xq), len(xq), _opt(tgt), _dptr(values), _opt(rmse), _iptr(info)), "gauge_lookup")
+        return dict(values=values, rmse=rmse, monotone=(info & 1) == 0)
+
+    def gauge_score(self, g, signal, observed, first=0, n=None):
+        """The fit of every member to a record at gauge g: `signal` (a name or index of _abi.GAUGE_ROWS) over the levels
+        [first, first + n) against observed [n] (shared) or [n, B]; NaN: no observation at that level.  dict name -> [B] with the
+        names of _abi.GS_ROWS: count of the levels that entered (inside the member's completed rows, evaluated, observed), bias,
+        rmse, nse (Nash-Sutcliffe), the simulated peak and its level (relative to `first`), peak error and peak lag in levels."""
+        n = self._span(first, n)
+        obs, per_reach = P.gauge_observed(observed, n, self.B)
+        out = np.empty((len(A.GS_ROWS), self.B))
+        A.check(self._lib.fs_batch_gauge_score(self._h, int(g), P.gauge_row(signal), int(first), int(n), _dptr(obs), per_reach, _dptr(out)),
+                "gauge_score")
+        return {k: out[i] for i, k in enumerate(A.GS_ROWS)}
+
+    def gauges_device_ptr(self, g):
+        """device pointer to gauge g's block [max_levels, 4, B] float64 (None: no such gauge)"""
+        return self._lib.fs_batch_gauges_device_ptr(self._h, int(g))
 
     def last_step_ms(self):
         return self._lib.fs_batch_last_step_ms(self._h)

@@ -20,17 +20,33 @@ def _add_envelope(out, b, envelope, nt):
                             for name in env if name not in ("levels", "crossing")}
 
 
-def _step(b, n_steps, balance, history):
-    """the runners' time loop: one launch; with balance= on a batch WITHOUT history, chunks of `every` levels with the state marked
-    (PreissmannBatch.reach_integrals(current=True)) before the first and after each - stream-ordered, the host does not wait"""
-    if balance is None or history:
+def _step(b, n_steps, balance, history, gauges=None, dx=None):
+    """the runners' time loop: one launch; with balance= or gauges= on a batch WITHOUT history, chunks of `every` levels with the state
+    marked (PreissmannBatch.reach_integrals(current=True), PreissmannBatch.gauges(current=True)) before the first and after each -
+    stream-ordered, the host does not wait.  One chunk loop serves both keywords.  gauges=: the gauges are set here, at the chainages
+    given, dx apart the nodes."""
+    every = threshold = None
+    if balance is not None:
+        every, threshold, _ = P.balance_options(balance)
+    if gauges is not None:
+        chainage, g_every = P.gauge_options(gauges)[:2]
+        if every is not None and g_every != every:
+            raise ValueError(f"balance= and gauges= mark the state at the same chunk boundaries: every={every} and every={g_every} differ")
+        every = g_every
+        b.set_gauges(chainage=chainage, dx=dx)
+    if every is None or history:
         b.step(n_steps)
         return
-    every, threshold, _ = P.balance_options(balance)
-    b.reach_integrals(threshold=threshold, current=True)
+
+    def mark():
+        if balance is not None:
+            b.reach_integrals(threshold=threshold, current=True)
+        if gauges is not None:
+            b.gauges(current=True)
+    mark()
     for chunk in P.balance_chunks(n_steps, every):
         b.step(chunk, sync=False)
-        b.reach_integrals(threshold=threshold, current=True)
+        mark()
     b.sync()
 
 
@@ -43,8 +59,27 @@ def _add_balance(out, b, balance, nt, history):
     out["balance"] = dict(rows=rows, totals=totals, bands=b.integral_bands(quantiles, 0, nt))
 
 
+def _add_gauges(out, b, gauges, nt, history):
+    """out['gauges'] of the runners' gauges= keyword: dict(node, weight, rows [G, nt, 4, B] when asked for, bands: one
+    PreissmannBatch.gauge_bands per gauge, score: one gauge_score per gauge when observed [G, nt] is given)"""
+    chainage, _, quantiles, observed, signal, rows = P.gauge_options(gauges)
+    G = len(chainage)
+    if observed is not None and observed.shape != (G, nt):
+        raise ValueError(f"gauges: observed must be [G, nt] = [{G}, {nt}], not {list(observed.shape)}")
+    if history:
+        b.gauges(0, nt)
+    node, weight = b.gauge_positions
+    res = dict(node=node, weight=weight)
+    if rows:
+        res["rows"] = np.stack([b.gauge_rows(g, 0, nt) for g in range(G)])
+    res["bands"] = [b.gauge_bands(g, quantiles, 0, nt) for g in range(G)]
+    if observed is not None:
+        res["score"] = [b.gauge_score(g, signal, observed[g], 0, nt) for g in range(G)]
+    out["gauges"] = res
+
+
 def run_manning_ensemble(solver, n_main_values, tolerance=1e-4, max_iter=100, dtype="f64", device=0, monitor=True, initial="host",
-                         summaries=False, score=None, bands=None, hydrographs=True, envelope=None, balance=None):
+                         summaries=False, score=None, bands=None, hydrographs=True, envelope=None, balance=None, gauges=None):
     """`solver`: a set-up (not yet run) PreissmannSolver whose channel provides geometry, boundaries
     and initial conditions; the initial conditions are shared by all members (the reference's
     members start from the same downstream level and the same flow; their GVF profiles differ
@@ -73,6 +108,13 @@ def run_manning_ensemble(solver, n_main_values, tolerance=1e-4, max_iter=100, dt
     chunks of `every` levels and the state is marked after each, so that the balance closes over each chunk and the rows between
     two marks are NaN.  With balance=None nothing changes.
 
+    Stations inside the reach: gauges=dict(chainage=, every=1, quantiles=(0.05, 0.5, 0.95), observed=None, signal="stage", rows=True)
+    adds 'gauges' = dict(node, weight: where the chainages [G] fall between the nodes; rows [G, nt, 4, B]: depth, flow, stage and
+    velocity at every gauge (rows=False leaves them on the device); bands: per gauge, gauge_bands across the members; score: per
+    gauge, gauge_score of `signal` against observed [G, nt], NaN where there is no observation).  With a history (envelope=) the
+    whole range is evaluated after the run; without one the state is marked at the chunk boundaries balance= marks it at (the two
+    must agree on `every`) and the rows between two marks are NaN.  With gauges=None nothing changes.
+
     Returns dict(hydrographs[nt, 4, B], iterations[nt, B], status[B]) and what the keywords above add."""
     if initial not in ("host", "gvf"):
         raise ValueError("initial must be 'host' or 'gvf'")
@@ -91,7 +133,7 @@ def run_manning_ensemble(solver, n_main_values, tolerance=1e-4, max_iter=100, dt
             b.set_state(ch.initial_conditions[:, 0], ch.initial_conditions[:, 1])
         else:
             b.set_state(ics[:, :, 0], ics[:, :, 1])
-        _step(b, nt - 1, balance, envelope is not None)
+        _step(b, nt - 1, balance, envelope is not None, gauges, solver.spatial_step)
         out = dict(iterations=b.iterations(0, nt), status=b.status())
         if hydrographs:
             out = dict(hydrographs=b.hydrographs(0, nt), **out)
@@ -106,12 +148,14 @@ def run_manning_ensemble(solver, n_main_values, tolerance=1e-4, max_iter=100, dt
             _add_envelope(out, b, envelope, nt)
         if balance is not None:
             _add_balance(out, b, balance, nt, envelope is not None)
+        if gauges is not None:
+            _add_gauges(out, b, gauges, nt, envelope is not None)
         return out
 
 
 def run_scenario_ensemble(solver, pool, inflow_table, inflow_scale=None, inflow_shift=None, pool_level=None, weir_scale=None, n_main=None,
                           initial="gvf", tolerance=1e-4, max_iter=100, dtype="f64", device=0, monitor=True, summaries=False, score=None,
-                          bands=None, hydrographs=True, envelope=None, balance=None):
+                          bands=None, hydrographs=True, envelope=None, balance=None, gauges=None):
     """Scenario ensembles: members that differ in what the reach is forced with - the inflow into the reservoir upstream of it
     (`inflow_table` [K, 2], time [s] and flow, per member multiplied by inflow_scale and delayed by inflow_shift [s]), the pool
     level the reservoir starts from (pool_level, required; it is also the member's hold level), the outlets in service (weir_scale
@@ -153,7 +197,7 @@ def run_scenario_ensemble(solver, pool, inflow_table, inflow_scale=None, inflow_
         flow0 = b.bc_target(A.UPSTREAM, 0, 1)[0]
         b.set_boundary(A.DOWNSTREAM, boundary_to_spec(ch.downstream_boundary, L, solver.time_step))
         b.init_state("GVF_equation", flow0, depth_ds=ch.downstream_boundary.initial_depth)
-        _step(b, nt - 1, balance, envelope is not None)
+        _step(b, nt - 1, balance, envelope is not None, gauges, solver.spatial_step)
         out = dict(iterations=b.iterations(0, nt), status=b.status(), initial_flow=flow0, pool=routed)
         if hydrographs:
             out = dict(hydrographs=b.hydrographs(0, nt), **out)
@@ -168,11 +212,13 @@ def run_scenario_ensemble(solver, pool, inflow_table, inflow_scale=None, inflow_
             _add_envelope(out, b, envelope, nt)
         if balance is not None:
             _add_balance(out, b, balance, nt, envelope is not None)
+        if gauges is not None:
+            _add_gauges(out, b, gauges, nt, envelope is not None)
         return out
 
 
 def run_geometry_ensemble(solver, dz_left=None, dz_main=None, dz_right=None, n_scale=None, tolerance=1e-4, max_iter=100, dtype="f64",
-                          device=0, monitor=True, summaries=False, score=None, bands=None, hydrographs=True, envelope=None, balance=None):
+                          device=0, monitor=True, summaries=False, score=None, bands=None, hydrographs=True, envelope=None, balance=None, gauges=None):
     """Geometry ensembles of a surveyed river: members that differ in the bed level of the main channel, the elevation of the left
     and right floodplain (levees included) and the three roughnesses.  `solver`: a set-up (not yet run) PreissmannSolver whose
     channel has polyline sections at every node; member r is that channel with the main-channel / left / right vertices of node i
@@ -209,7 +255,7 @@ def run_geometry_ensemble(solver, dz_left=None, dz_main=None, dz_right=None, n_s
         else:
             b.init_state(method, ch.initial_flow_rate, depth_ds=ch.downstream_boundary.initial_depth,
                          depth_us=ch.upstream_boundary.initial_depth if method == "linear" else None)
-        _step(b, nt - 1, balance, envelope is not None)
+        _step(b, nt - 1, balance, envelope is not None, gauges, solver.spatial_step)
         out = dict(iterations=b.iterations(0, nt), status=b.status())
         if hydrographs:
             out = dict(hydrographs=b.hydrographs(0, nt), **out)
@@ -224,6 +270,8 @@ def run_geometry_ensemble(solver, dz_left=None, dz_main=None, dz_right=None, n_s
             _add_envelope(out, b, envelope, nt)
         if balance is not None:
             _add_balance(out, b, balance, nt, envelope is not None)
+        if gauges is not None:
+            _add_gauges(out, b, gauges, nt, envelope is not None)
         return out
 
 

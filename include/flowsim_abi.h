@@ -534,6 +534,54 @@ void *fs_batch_reach_integrals_device_ptr(fs_batch *b);
 int fs_batch_integral_bands(fs_batch *b, int32_t first, int32_t n, const double *q, int32_t n_q, double *moments, double *quantiles,
                             int32_t *n_members);
 
+/* ---- Interior gauges: station series, their bands across the members and fit scores ----
+ * A gauge sits between node `node` and node + 1 of a reach, at weight in [0, 1) of the way: fs_batch_set_gauges takes node[G] and
+ * weight[G] shared by the batch, or [B][G] with per_reach != 0 (ragged batches, per-reach dx), 0 <= G <= FS_GAUGE_MAX.  It checks
+ * what the host can know - 0 <= node < n_nodes, weights finite and in [0, 1), node + 1 < n_nodes where the weight is not 0 - then
+ * allocates the block gauge[G][max_levels][FS_GAUGE_NROWS][B] of doubles (gauge g's part has the shape of the hydrograph block,
+ * member minor) and the marks [max_levels][B], one int32 per (level, member) whose bit g says that gauge g's row holds values, and
+ * sets every row to NaN and every mark to 0.  G = 0 frees both.  fs_batch_set_state*, fs_batch_init_state and fs_batch_restart
+ * reset every row and mark in the same way.
+ *
+ * fs_batch_gauges: fills the rows first .. first + n - 1 of every gauge from the stored history (FS_FLAG_HISTORY; ranges as
+ * fs_batch_reach_integrals).  first = -1 (n = 1) fills the row of the batch's current level from the current state instead and needs
+ * no history: a batch that keeps none marks its state between two fs_batch_step calls (refused while a level opened by
+ * fs_batch_iterate is open).  Per (level, member, gauge) the four quantities are evaluated at node and, where the weight is not 0, at
+ * node + 1 as fs_batch_derive evaluates them - depth h, flow Q, stage h + z, velocity Q / A - in the batch dtype, widened to double,
+ * and the row is a + weight (b - a) in fp64, the product rounded before the sum.  With weight 0 the row is a itself and node + 1 is
+ * not read: a gauge may sit on a reach's last node.  NaN rows with mark bit 0: those of a failed reach from its failing level on, and
+ * at every level those of a reach that does not have the gauge (node, or node + 1 with a weight that is not 0, at or beyond its own
+ * node count, fs_batch_set_reach_nodes).  A row's bits depend on (level, member, gauge) alone: not on B, on the member's place in the
+ * batch, on the range asked for, or on the source (history row or current state).  The call is stream-ordered, does not wait for the
+ * device, and fs_batch_last_step_ms then reports its kernel.
+ *
+ * fs_batch_get_gauges: out[n][FS_GAUGE_NROWS][B], the rows first .. first + n - 1 (any rows of 0 .. max_levels - 1) of one gauge;
+ * fs_batch_gauges_device_ptr: its [max_levels][FS_GAUGE_NROWS][B] doubles on the device (NULL: no such gauge).
+ * fs_batch_gauge_bands: fs_batch_bands on one gauge's block (the same kernel): moments[n][4][4], quantiles[n][4][n_q], n_members[n].
+ * Failed members and members that do not have the gauge are left out; a level that a remaining member has not evaluated reports NaN.
+ * fs_batch_gauge_lookup: fs_batch_lookup on one gauge's block (the same kernels), x_row and y_row being FS_GAUGE_*; a range in which
+ * some level was never evaluated is refused.
+ * fs_batch_gauge_score: per member, one signal (FS_GAUGE_*) of one gauge against observed[n], or [n][B] with observed_per_reach != 0;
+ * a NaN in observed means "no observation".  A level counts when it is inside the member's completed rows, marked and observed.  Over
+ * the m counted levels, in level order and in fp64 with every product rounded: out[FS_GS_NROWS][B] = m; sum(sim - obs) / m;
+ * sqrt(sum((sim - obs)^2) / m); 1 - sum((sim - obs)^2) / sum((obs - mean(obs))^2) (whatever IEEE gives for a zero denominator); the
+ * simulated peak and its level (first index of the maximum, relative to `first`); simulated minus observed peak; simulated minus
+ * observed peak level.  m = 0: count 0, levels -1, the rest NaN.  A NaN simulated value at a counted level propagates as in numpy. */
+enum { FS_GAUGE_DEPTH = 0, FS_GAUGE_FLOW, FS_GAUGE_STAGE, FS_GAUGE_VELOCITY, FS_GAUGE_NROWS };
+#define FS_GAUGE_MAX 32
+enum { FS_GS_COUNT = 0, FS_GS_BIAS, FS_GS_RMSE, FS_GS_NSE, FS_GS_PEAK_SIM, FS_GS_PEAK_SIM_LEVEL, FS_GS_PEAK_ERROR, FS_GS_PEAK_LAG,
+       FS_GS_NROWS };
+int fs_batch_set_gauges(fs_batch *b, int32_t n_gauges, const int32_t *node, const double *weight, int32_t per_reach);
+int fs_batch_gauges(fs_batch *b, int32_t first, int32_t n);
+int fs_batch_get_gauges(fs_batch *b, int32_t gauge, int32_t first, int32_t n, double *out);
+void *fs_batch_gauges_device_ptr(fs_batch *b, int32_t gauge);
+int fs_batch_gauge_bands(fs_batch *b, int32_t gauge, int32_t first, int32_t n, const double *q, int32_t n_q, double *moments,
+                         double *quantiles, int32_t *n_members);
+int fs_batch_gauge_lookup(fs_batch *b, int32_t gauge, int32_t first, int32_t n, int32_t x_row, int32_t y_row, const double *y_offset,
+                          const double *xq, int32_t n_q, const double *target, double *values, double *rmse, int32_t *info);
+int fs_batch_gauge_score(fs_batch *b, int32_t gauge, int32_t signal, int32_t first, int32_t n, const double *observed,
+                         int32_t observed_per_reach, double *out);
+
 /* zero-copy access for device-side consumers (RCCL gather of hydrographs): device pointer to the
  * [max_levels][4][B] hydrograph block in the batch dtype, and the handle's hipStream_t */
 void *fs_batch_hydrograph_device_ptr(fs_batch *b);
