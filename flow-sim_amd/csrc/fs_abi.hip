@@ -27,6 +27,7 @@
 #include "fs_envelope.hpp"
 #include "fs_forcing.hpp"
 #include "fs_gauge.hpp"
+#include "fs_assim.hpp"
 #include "fs_host_pack.hpp"
 #include "fs_host_post.hpp"
 #include "fs_init_state.hpp"
@@ -49,7 +50,7 @@ struct TraceRange {
 FS_ACTIVE_LIST(FS_DECLARE)
 #else
 // an experiment build is this translation unit alone, with a few step kernels: it has no initial-condition kernels (fs_part_init.hip)
-// no post-processing kernels (fs_part_reduce.hip, fs_part_envelope.hip, fs_part_balance.hip, fs_part_gauges.hip), no forcing kernels (fs_part_forcing.hip) and no geometry kernels
+// no post-processing kernels (fs_part_reduce.hip, fs_part_envelope.hip, fs_part_balance.hip, fs_part_gauges.hip, fs_part_assim.hip), no forcing kernels (fs_part_forcing.hip) and no geometry kernels
 // (fs_part_geometry.hip), and fs_batch_init_state, fs_batch_summarize, fs_batch_set_bc_sampled ... say so
 namespace fs {
 bool launch_envelope(const EnvelopeArgs<double> &, int, hipStream_t) { return false; }
@@ -65,6 +66,8 @@ bool launch_gauge_gather(const GaugeArgs<double> &, bool, hipStream_t) { return 
 bool launch_gauge_gather(const GaugeArgs<float> &, bool, hipStream_t) { return false; }
 bool launch_gauge_score(const ReduceArgs<double> &, const ScoreArgs &, hipStream_t) { return false; }
 bool launch_gauge_members(const int32_t *, const int32_t *, const int32_t *, const double *, int, int, int, int, int, int32_t *, hipStream_t) { return false; }
+bool launch_assimilate(const AssimArgs<double> &, hipStream_t) { return false; }
+bool launch_assimilate(const AssimArgs<float> &, hipStream_t) { return false; }
 bool launch_member_sections(const MemberGeoArgs &, hipStream_t) { return false; }
 bool launch_member_tables(const MemberGeoArgs &, hipStream_t) { return false; }
 bool launch_sample_target(const SampleArgs<double> &, hipStream_t) { return false; }
@@ -280,6 +283,11 @@ struct fs_batch : Timeline {
   fs::DeviceBuffer gauge_members;       // int32 [B]: fs_batch_gauge_bands' status of each member at the gauge it was asked for
   int n_gauges = 0;
   bool gauge_per_reach = false;
+  fs::DeviceBuffer assim_part;          // double [chunks][2][n_obs + 2][N]: the partial sums of the last fs_batch_assimilate (grown, never shrunk)
+  fs::DeviceBuffer assim_out;           // double: its prior [4][N], then its cross covariances [2][n_obs][N]
+  fs::DeviceBuffer assim_cols;          // double: its S, then its Z, both [B][bucket]
+  fs::DeviceBuffer assim_taper;         // double [n_obs][N]: the taper it was handed
+  fs::DeviceBuffer assim_flags;         // int32: the active flags [B], then the clamped counts [B]
   std::vector<char> gauge_levels;       // [max_levels]: 1 where fs_batch_gauges has evaluated the level since the last reset
   int env_quantities = 0;               // FS_ENV_* mask of the envelope the handle holds (0: none)
   bool env_crossings = false;           // ... and whether it has crossing rows
@@ -1959,6 +1967,76 @@ int fs_batch_gauge_score(fs_batch *b, int32_t gauge, int32_t signal, int32_t fir
         return fs::launch_gauge_score(block_args(b, p.gauge, b->status.get<const int32_t>(), first, n), p, b->stream);
       })) return -1;
   return fetch(b, out, p.out, bytes);
+}
+
+// ---- assimilation of gauge observations (fs_assim.hpp) ----
+
+int fs_batch_assimilate(fs_batch *b, int32_t n_obs, const int32_t *gauge, const int32_t *signal, const double *value,
+                        const double *variance, const double *perturb, const double *taper, double depth_floor, double *prior,
+                        double *cross_cov, int32_t *clamped, int32_t *n_active) {
+  const char *entry = "fs_batch_assimilate";
+  if (!b) return fail("fs_batch_assimilate: null handle");
+  if (!b->have_state) return fail("fs_batch_assimilate: no state yet");
+  if (!b->have_geo) return fail("fs_batch_assimilate: the geometry must be set first");
+  if (check_gauge(b, entry, 0)) return -1;
+  if (b->gauge_per_reach) return fail("fs_batch_assimilate: the gauges were set per reach; the members of an analysis share their positions");
+  if (b->reach_nodes) return fail("fs_batch_assimilate: per-reach node counts were given; the members of an analysis are one channel, node for node");
+  if (b->iterating) return fail("fs_batch_assimilate: a level opened with fs_batch_iterate must be closed first");
+  const size_t B = b->d.n_reaches, N = b->d.n_nodes, L = b->d.max_levels;
+  if (refuse(fs::check_observations(entry, n_obs, gauge, signal, value, variance, perturb, taper, depth_floor, b->n_gauges, B, N))) return -1;
+  if (fs_batch_gauges(b, -1, 1)) return -1;                   // the row of the current level, from the current state
+  FS_ON_DEVICE(b);
+  TraceRange range_("flowsim:assimilate");
+  const size_t m = (size_t)n_obs, level = (size_t)b->level;
+  std::vector<int32_t> mark(B), active(B);
+  std::vector<double> y(m * B);
+  if (fetch(b, mark.data(), b->gauge_mark.get<const int32_t>() + level * B, B * sizeof(int32_t))) return -1;
+  for (size_t j = 0; j < m; ++j)
+    if (fetch(b, y.data() + j * B, b->gauge.get<const double>() + (((size_t)gauge[j] * L + level) * FS_GAUGE_NROWS + (size_t)signal[j]) * B,
+              B * sizeof(double))) return -1;
+  uint32_t need = 0;
+  for (size_t j = 0; j < m; ++j) need |= 1u << gauge[j];
+  int32_t first_active = -1;
+  for (size_t r = 0; r < B; ++r) {
+    active[r] = ((uint32_t)mark[r] & need) == need;
+    if (active[r] && first_active < 0) first_active = (int32_t)r;
+  }
+  std::vector<double> ybar, S, Cov, Lc, Z;
+  int32_t na = 0;
+  const std::string text = fs::analysis_coefficients(entry, n_obs, B, active.data(), [&](size_t j, size_t r) { return y[j * B + r]; }, value,
+                                                     variance, perturb, ybar, S, Cov, Lc, Z, &na);
+  if (n_active) *n_active = na;
+  if (refuse(text)) return -1;
+  // S and Z member-major, padded with zero rows to the bucket the kernels are instantiated on
+  const fs::AssimLayout lay{B, N, m};
+  std::vector<double> cols(2 * lay.columns(), 0.0);
+  for (size_t r = 0; r < B; ++r)
+    for (size_t j = 0; j < m; ++j) {
+      cols[lay.column(r) + j] = S[j * B + r];
+      cols[lay.columns() + lay.column(r) + j] = Z[j * B + r];
+    }
+  std::vector<int32_t> flags(2 * B, 0);
+  std::copy(active.begin(), active.end(), flags.begin());
+  HIP_TRY(b->assim_part.reserve(lay.partials() * sizeof(double)));
+  HIP_TRY(b->assim_out.reserve((lay.prior() + lay.cross()) * sizeof(double)));
+  if (upload_f64(b->assim_cols, cols.data(), cols.size())) return -1;
+  if (taper && upload_f64(b->assim_taper, taper, m * N)) return -1;
+  HIP_TRY(b->assim_flags.reserve(flags.size() * sizeof(int32_t)));
+  HIP_TRY(hipMemcpy(b->assim_flags.get(), flags.data(), flags.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  if (post_launch(b, entry, 3, [&](auto real) {             // fs_batch_last_step_ms() then reports the moments, combine and update kernels
+        using R = decltype(real);
+        const fs::AssimArgs<R> a{(int32_t)B, (int32_t)N, n_obs, na, first_active, b->hk.get<R>(), b->Qk.get<R>(), b->hg.get<R>(), b->Qg.get<R>(),
+                                 b->assim_flags.get<const int32_t>(), b->assim_cols.get<const double>(),
+                                 b->assim_cols.get<const double>() + lay.columns(), taper ? b->assim_taper.get<const double>() : nullptr,
+                                 depth_floor, b->assim_part.get<double>(), b->assim_out.get<double>(), b->assim_out.get<double>() + lay.prior(),
+                                 b->assim_flags.get<int32_t>() + B};
+        return fs::launch_assimilate(a, b->stream);
+      })) return -1;
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  if (prior && fetch(b, prior, b->assim_out.get<const double>(), lay.prior() * sizeof(double))) return -1;
+  if (cross_cov && fetch(b, cross_cov, b->assim_out.get<const double>() + lay.prior(), lay.cross() * sizeof(double))) return -1;
+  if (clamped && fetch(b, clamped, b->assim_flags.get<const int32_t>() + B, B * sizeof(int32_t))) return -1;
+  return 0;
 }
 
 void *fs_batch_hydrograph_device_ptr(fs_batch *b) { return b ? b->hydro.get() : nullptr; }

@@ -52,6 +52,9 @@ BAL_ROWS = ("spans", "first_level", "last_level", "storage_change", "net_inflow"
 GAUGE_ROWS = ("depth", "flow", "stage", "velocity")
 GAUGE_MAX = 32
 GS_ROWS = ("count", "bias", "rmse", "nse", "peak_sim", "peak_sim_level", "peak_error", "peak_lag")
+# fs_batch_assimilate: the most observations of one analysis, and the members per partial sum of its moments
+ASSIM_MAX_OBS = 16
+ASSIM_CHUNK = 256
 ABI_VERSION = 3
 
 
@@ -133,6 +136,7 @@ SIGNATURES = {
     "fs_batch_gauge_bands": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _D, C.c_int32, _D, _D, _I]),
     "fs_batch_gauge_lookup": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D, _D, C.c_int32, _D, _D, _D, _I]),
     "fs_batch_gauge_score": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D, C.c_int32, _D]),
+    "fs_batch_assimilate": (C.c_int, [_P, C.c_int32, _I, _I, _D, _D, _D, _D, C.c_double, _D, _D, _I, _I]),
     "fs_batch_hydrograph_device_ptr": (_P, [_P]),
     "fs_batch_stream": (_P, [_P]),
     "fs_batch_last_step_ms": (C.c_double, [_P]),

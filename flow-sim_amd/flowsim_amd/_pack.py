@@ -461,3 +461,31 @@ def gauge_options(gauges):
     observed = gauges.get("observed")
     return (chainage, int(every), quantile_levels(gauges.get("quantiles", (0.05, 0.5, 0.95))),
             None if observed is None else np.asarray(observed, dtype=np.float64), signal, bool(gauges.get("rows", True)))
+
+
+# -- assimilation of gauge observations ------------------------------------------------------------
+def pack_observations(observations, B, N, perturbations=None, taper=None, depth_floor=1e-3):
+    """(n_obs, gauge int32 [m], signal int32 [m], value [m], variance [m], perturb [m, B] | None, taper [m, N] | None, depth_floor)
+    of fs_batch_assimilate.  observations: a sequence of (gauge, signal, value, variance) - tuples or objects with those attributes
+    (assimilation.Observation) -, signal a name or index of _abi.GAUGE_ROWS.  perturbations: [m, B]; taper: [N] (every observation's)
+    or [m, N].  Shapes and the observation count are checked here; what the values may be is the library's to refuse."""
+    obs = [(o.gauge, o.signal, o.value, o.variance) if hasattr(o, "gauge") else tuple(o) for o in observations]
+    m = len(obs)
+    if not 1 <= m <= A.ASSIM_MAX_OBS:
+        raise ValueError(f"assimilate: 1 .. {A.ASSIM_MAX_OBS} observations, not {m}")
+    if any(len(o) != 4 for o in obs):
+        raise ValueError("assimilate: an observation is (gauge, signal, value, variance)")
+    gauge = np.ascontiguousarray([int(o[0]) for o in obs], dtype=np.int32)
+    signal = np.ascontiguousarray([gauge_row(o[1]) for o in obs], dtype=np.int32)
+    value = np.ascontiguousarray([float(o[2]) for o in obs], dtype=np.float64)
+    variance = np.ascontiguousarray([float(o[3]) for o in obs], dtype=np.float64)
+    if perturbations is not None:
+        perturbations = np.ascontiguousarray(perturbations, dtype=np.float64)
+        if perturbations.shape != (m, B):
+            raise ValueError(f"assimilate: perturbations are [n_obs, B] = [{m}, {B}], not {list(perturbations.shape)}")
+    if taper is not None:
+        taper = np.asarray(taper, dtype=np.float64)
+        if taper.shape not in ((N,), (m, N)):
+            raise ValueError(f"assimilate: taper is [N] = [{N}] or [n_obs, N] = [{m}, {N}], not {list(taper.shape)}")
+        taper = np.ascontiguousarray(np.broadcast_to(taper, (m, N)))
+    return m, gauge, signal, value, variance, perturbations, taper, float(depth_floor)

@@ -576,6 +576,24 @@ class PreissmannBatch:
         """device pointer to gauge g's block [max_levels, 4, B] float64 (None: no such gauge)"""
         return self._lib.fs_batch_gauges_device_ptr(self._h, int(g))
 
+    # -- assimilation of gauge observations: the analysis step of an ensemble Kalman filter -------------------
+    def assimilate(self, observations, perturbations=None, taper=None, depth_floor=1e-3):
+        """Corrects the state (and the Newton start vector) of every active member from observations of gauge signals of the
+        current state, between two step() calls: observations is a sequence of assimilation.Observation or (gauge, signal, value,
+        variance) tuples, perturbations [n_obs, B] what is added to each observation per member (None: zeros; the library draws no
+        random numbers - assimilation.perturbations does), taper [N] or [n_obs, N] in [0, 1] the localisation along the reach
+        (None: ones).  A member is active when it holds every observed gauge at the current level; failed members are not, and are
+        not written.  Returns dict(n_active, prior: dict(mean_h, var_h, mean_Q, var_Q [N]) of the active members before the
+        update, cross_cov [2, n_obs, N]: cov(h or Q at a node, observation), clamped [B]: nodes whose new depth was raised to
+        depth_floor).  History, hydrographs, level and status stay what they were: they record the forecast."""
+        m, gauge, signal, value, variance, pert, tap, floor = P.pack_observations(observations, self.B, self.N, perturbations, taper, depth_floor)
+        prior, cross = np.empty((4, self.N)), np.empty((2, m, self.N))
+        clamped, n_active = np.zeros(self.B, dtype=np.int32), C.c_int32(0)
+        A.check(self._lib.fs_batch_assimilate(self._h, m, _iptr(gauge), _iptr(signal), _dptr(value), _dptr(variance), _opt(pert), _opt(tap), floor,
+                                              _dptr(prior), _dptr(cross), _iptr(clamped), C.byref(n_active)), "assimilate")
+        return dict(n_active=int(n_active.value), prior=dict(mean_h=prior[0], var_h=prior[1], mean_Q=prior[2], var_Q=prior[3]), cross_cov=cross,
+                    clamped=clamped)
+
     def last_step_ms(self):
         return self._lib.fs_batch_last_step_ms(self._h)
 

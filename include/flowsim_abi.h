@@ -582,6 +582,57 @@ int fs_batch_gauge_lookup(fs_batch *b, int32_t gauge, int32_t first, int32_t n, 
 int fs_batch_gauge_score(fs_batch *b, int32_t gauge, int32_t signal, int32_t first, int32_t n, const double *observed,
                          int32_t observed_per_reach, double *out);
 
+/* ---- Assimilation of gauge observations: the analysis step of a stochastic ensemble Kalman filter over the members ----
+ * fs_batch_assimilate corrects the state of every member that takes part, between two fs_batch_step calls, from n_obs observations
+ * (1 .. FS_ASSIM_MAX_OBS): observation j is signal[j] (FS_GAUGE_*) of gauge[j] (of fs_batch_set_gauges, shared positions), observed as
+ * value[j] with error variance[j] (finite, > 0).  perturb [n_obs][B] (or NULL: zeros) is what the caller adds to the observation per
+ * member - the library draws no random numbers -, taper [n_obs][N] in [0, 1] (or NULL: ones) localises observation j along the reach.
+ * The members must be one channel, node for node: per-reach gauges (per_reach != 0) and per-reach node counts are refused.
+ *
+ * Refused with a text that names fs_batch_assimilate, and with the state untouched bit for bit: no state, no geometry, no gauges;
+ * per-reach gauges or node counts; a level opened by fs_batch_iterate; n_obs outside 1 .. FS_ASSIM_MAX_OBS; a gauge or signal out of
+ * range; a variance that is not finite or not > 0; a value, perturbation or taper that is not finite, a taper outside [0, 1];
+ * depth_floor negative or not finite; fewer than two active members; an active member with a NaN in an observed signal; an innovation
+ * covariance whose Cholesky factor has a pivot that is not positive and finite.
+ *
+ * Gather and active members.  The call first fills the gauge row of the current level from the current state, exactly as
+ * fs_batch_gauges(b, -1, 1) does (that row stays, also after a refusal).  Member r is ACTIVE when its mark at that level has the bit
+ * of every observed gauge: failed members are inactive, and an inactive member is never written.  n_a: the active members; y_jr: the
+ * gathered value of observation j in member r.
+ *
+ * Host part, in fp64, sequentially in member order over the active members, every product rounded (no contraction):
+ *   ybar_j = sum_r y_jr / n_a;   S_jr = y_jr - ybar_j (0 for inactive members);
+ *   C_jl = (sum_r S_jr S_lr) / (n_a - 1) + [j == l] variance_j;   C = L D L^T, the square-root-free lower Cholesky factor row by
+ *   row (L unit lower, D the pivots: L_jl = (C_jl - sum_{k<l} (L_jk D_k) L_lk) / D_l, D_j = C_jj - sum_{k<j} (L_jk D_k) L_jk, the sums
+ *   subtracted in ascending k).  The pivots are the squares of the pivots of C = G G^T; without the root, one observation is
+ *   Z = D / C in a single rounding;
+ *   D_jr = (value_j + perturb_jr) - y_jr;   Z_.r = C^-1 D_.r: w_j = D_jr - sum_{k<j} L_jk w_k, then from j = n_obs - 1 down
+ *   z_j = w_j / D_j - sum_{k>j} L_kj z_k, the inner sums subtracted in ascending k (0 for inactive members).
+ * Moments, per field f in {h, Q} and node i, in fp64: c = the value of the first active member.  The members are taken in chunks of
+ * FS_ASSIM_CHUNK by batch index; within a chunk the active members sequentially in member order: d = x_r - c; s1 += d; s2 += d d;
+ * p_j += d S_jr, every product rounded, every sum from 0.0.  The chunk partials are added in chunk order, beginning with chunk 0's.
+ *   mean = c + s1 / n_a;   var = (s2 - (s1 s1) / n_a) / (n_a - 1);   P_fji = p_j / (n_a - 1).
+ * (Subtracting c is exact algebra, since sum_r S_jr = 0; it keeps the sums conditioned on stages of hundreds of metres.)
+ * Update, for active members only: inc = sum_j (taper_ji P_fji) Z_jr in j order from 0.0, each product rounded (taper NULL: P_fji
+ * itself).  hk <- R(double(hk) + inc) and hg <- R(double(hg) + inc), R rounding to the batch dtype: the Newton start vector takes
+ * the same increment; Qk and Qg likewise.  A new depth hk below depth_floor, or NaN, becomes depth_floor in both hk and hg at that
+ * node (so does a new hg that is below the floor or NaN on its own); clamped[r] counts the nodes of hk where that happened.
+ * Inactive members keep every bit.
+ *
+ * Outputs, each optional: prior [4][N] = mean h, var h, mean Q, var Q of the active members before the update; cross_cov
+ * [2][n_obs][N] = P, before the taper; clamped [B]; *n_active (also set when the call is refused for too few active members, a NaN
+ * or a pivot).
+ *
+ * What is left alone: the history, hydrograph and storage-stage blocks, the reservoir state, the level counter and the status.  They
+ * record the forecast; the analysis acts on what is stepped next (every launch rebuilds its level constants from hk / Qk).  The
+ * discrete water balance across an analysis level therefore no longer closes: the analysis adds or removes water.
+ * fs_batch_last_step_ms then reports the moments, combine and update kernels (three launches); the call waits for the device. */
+#define FS_ASSIM_MAX_OBS 16
+#define FS_ASSIM_CHUNK   256      /* members per partial sum: part of the contract, the bits depend on it */
+int fs_batch_assimilate(fs_batch *b, int32_t n_obs, const int32_t *gauge, const int32_t *signal, const double *value,
+                        const double *variance, const double *perturb, const double *taper, double depth_floor, double *prior,
+                        double *cross_cov, int32_t *clamped, int32_t *n_active);
+
 /* zero-copy access for device-side consumers (RCCL gather of hydrographs): device pointer to the
  * [max_levels][4][B] hydrograph block in the batch dtype, and the handle's hipStream_t */
 void *fs_batch_hydrograph_device_ptr(fs_batch *b);
